@@ -18,7 +18,10 @@ N > 1: one process per GPU (torch.distributed, backend nccl == RCCL); every rank
 and *owns* G/N rows of the product bank, which are all-gathered on a side stream each step before the match (the achieved
 all-gather rate per xGMI link is reported under ``allgather``).  Rank 0 prints ONE JSON line.
 
-Extra legs (rank 0, N == 1 only):
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) only sets up, warms up, times the N steps and prints the line;
+``--dump-outputs DIR`` also writes what the last timed step computed (see ``dump_outputs``).
+
+Extra legs (``--full`` only; rank 0, N == 1 only):
   roofline      the dominant kernel of one instrumented step (HIP events bracketing every conv launch on the launch stream);
                 ``achieved`` = MFMA FLOP/s the kernel ISSUES for its algorithmic work (algorithmic / 3 for Winograd F(2x4,3x3),
                 / 2.25 for F(2x2,3x3)), ``frac`` = achieved / the dense MFMA peak of the dtype (always <= 1); the
@@ -29,6 +32,7 @@ Extra legs (rank 0, N == 1 only):
   extras        ``value_clips1`` (one clip per step) and ``full_forward_ms_per_clip`` (the drop-in ``model(images)`` forward
                 with RPN proposals, box head, NMS and mask paste on the same 10 frames).  ``--no-extras`` skips them (used for
                 the rocprofv3 kernel-stats run, so that the per-kernel averages cover the 8-clip steps only).
+  match_stage   (c3 / c4) the similarity + top-k stage of the last timed step's inputs, timed on its own.
 """
 import argparse
 import json
@@ -66,6 +70,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extra legs (roofline, CPU baseline + parity, extras, match_stage); "
+                         "a plain run times the steps and prints the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; "
+                         "a larger output as a fixed, seeded sample of its rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the value_clips1 / full_forward_ms_per_clip legs")
@@ -103,7 +113,10 @@ def parse():
     ap.add_argument("--dtype", choices=("f32", "f16", "bf16x3"), default="f32",
                     help="f32 (default, the headline: exact fp32 MFMA) | f16 (config-5 style fp16 MFMA, fp32 accumulate; "
                          "extractor + trunks in fp16, descriptors / NLB / match logits fp32) | bf16x3 (split-bf16, opt-in)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -135,7 +148,7 @@ def self_launch(args, argv=None, popen=None):
     GPUs below may already have initialised HIP in this parent (on ROCm builds without amdsmi torch.cuda.device_count() falls back to
     hipGetDeviceCount), and replacing a process that has touched the GPU takes the machine down on this pool.  `popen` is a test seam."""
     import subprocess
-    argv = sys.argv[1:] if argv is None else argv
+    argv = absolute_dump_dir(sys.argv[1:] if argv is None else argv)
     if popen is None:
         import torch
         have = args.gpus if args.stub_step else torch.cuda.device_count()
@@ -169,6 +182,17 @@ def self_launch(args, argv=None, popen=None):
         print("bench.py: the launched ranks printed no result line", file=sys.stderr)
         return 1
     return rc
+
+
+def absolute_dump_dir(argv):
+    """argv with the DIR of ``--dump-outputs DIR`` made absolute: the launched ranks run in ROOT, the caller may not."""
+    argv = list(argv)
+    for i, a in enumerate(argv):
+        if a == "--dump-outputs" and i + 1 < len(argv):
+            argv[i + 1] = os.path.abspath(argv[i + 1])
+        elif a.startswith("--dump-outputs="):
+            argv[i] = "--dump-outputs=" + os.path.abspath(a.split("=", 1)[1])
+    return argv
 
 
 def build_model(dev):
@@ -243,6 +267,8 @@ def main():
     FLOP_PER_CLIP = flop_per_clip(wl)
     if needs_self_launch(args.gpus, os.environ):       # before any HIP call in this process
         raise SystemExit(self_launch(args))
+    if not args.full:                                   # a plain run: set up, warm up, time the steps, print the line
+        args.no_roofline = args.no_cpu_baseline = args.no_extras = True
     import torch
     import torch.distributed as dist
     import seam_match_rcnn_amd.synth as synth
@@ -449,6 +475,8 @@ def main():
 
     ms_per_step = 1e3 * elapsed / args.steps
     log(f"timed: {ms_per_step:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, last)}")
     value = world * B * args.steps / elapsed                                  # whole-job clips/s
 
     allgather = None
@@ -567,7 +595,7 @@ def main():
                                      "(clips_per_step_per_gpu x frames images in ONE model(images) call), best of 2 after a warm-up")
 
     match_stage = None
-    if rank == 0 and not stub and wl["rank"] == "topk" and not args.graph:
+    if args.full and rank == 0 and not stub and wl["rank"] == "topk" and not args.graph:
         # configs[2]/[3]: the similarity + top-k stage on its own (HIP events on the launch stream), this rank's sequences vs the bank
         with torch.no_grad():
             desc, bank = last[1][0].contiguous(), last[5]
@@ -655,6 +683,54 @@ def main():
         dist.destroy_process_group()
     if failed:
         raise SystemExit("bench.py: " + failed)
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_TOTAL_BYTES = 60 * 2 ** 20        # --dump-outputs: array bytes of all files together (< 64 MB with the headers)
+
+
+def step_outputs(last):
+    """What one step hands its caller (run_step's tuple) as name -> tensor: forward_fixed_rois's per-ROI outputs joined over the
+    step's images, the aggregator's outputs (reference names), the match logits, the top-k and the gathered bank.  Outputs the
+    step did not compute (None, or empty as x3_2 / x5 when every ROI is a street ROI) are left out."""
+    import torch
+    res, out, x5, idx, score, bank = last
+    named = {}
+    for key in ("roi_features", "match_features", "masks"):
+        parts = [r[key] for r in (res or []) if key in r]
+        if parts:
+            named[key] = torch.cat(parts)
+    if out is not None:
+        named.update(zip(("x3_1b", "x3_2", "x5", "x3_1_seq", "x3_1_mask", "x3_1_ids"), out))
+    named.update(match_logits=x5, topk_idx=idx, topk_score=score, bank=bank)
+    return {k: v for k, v in named.items() if isinstance(v, torch.Tensor) and v.numel() > 0}
+
+
+def dump_outputs(directory, last):
+    """Write step_outputs(last) as DIR/<name>.npy: floating outputs as float32, integer / bool ones as float64 (exact).
+    DUMP_TOTAL_BYTES is shared out smallest output first (each takes what it needs, up to an equal share of what is left); an
+    output larger than its share is written as the rows (dim 0) np.random.default_rng(0) picks -- a function of the shapes alone,
+    so two builds of the project write the same rows.  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    named = step_outputs(last)
+    os.makedirs(directory, exist_ok=True)
+    left, written = DUMP_TOTAL_BYTES, {}
+    for i, name in enumerate(sorted(named, key=lambda k: named[k].numel() * (4 if named[k].is_floating_point() else 8))):
+        t = named[name]
+        dtype, size = (torch.float32, 4) if t.is_floating_point() else (torch.float64, 8)
+        share = left // (len(named) - i)
+        if t.numel() // t.shape[0] * size > share:
+            t = t.reshape(-1)                                               # (rows larger than the share: sample elements)
+        n, row_bytes = t.shape[0], t.numel() // t.shape[0] * size
+        if n * row_bytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(n, share // row_bytes, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.detach().to(dtype).cpu().contiguous().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 # ------------------------------------------------------------------------------------------------ roofline

@@ -100,6 +100,29 @@ def test_self_launch_branch_with_one_rank():
     assert "self-launch" in r.stderr
 
 
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs DIR: the stub step returns the gathered bank alone, so DIR holds exactly that table, in float32."""
+    import numpy as np
+    import seam_match_rcnn_amd.synth as synth
+    r = _run(["--gpus", "1", "--stub-step", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip())
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["bank.npy"]
+    bank = np.load(tmp_path / "out" / "bank.npy")
+    assert bank.dtype == np.float32 and np.array_equal(bank, synth.gallery(7, 1000))
+
+
+def test_dump_dir_is_absolute_for_the_launched_ranks():
+    got = bench.absolute_dump_dir(["--gpus", "2", "--dump-outputs", "out", "--dump-outputs=o2"])
+    assert got == ["--gpus", "2", "--dump-outputs", os.path.abspath("out"), "--dump-outputs=" + os.path.abspath("o2")]
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--stub-step", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr and r.stdout.strip() == ""
+
+
 def test_rank_count_mismatch_is_an_error():
     r = _run(["--gpus", "3", "--stub-step", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "--gpus 3" in r.stderr

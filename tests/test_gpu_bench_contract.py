@@ -25,7 +25,8 @@ def run(cmd, **env):
 
 
 def test_bench_line_and_roofline_fields():
-    d = run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--clips", "1", "--cpu-frames", "1", "--cpu-runs", "2"])
+    """--full: the line of a plain run plus the roofline, CPU baseline, parity and extras legs."""
+    d = run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--clips", "1", "--cpu-frames", "1", "--cpu-runs", "2"])
     assert KEYS <= set(d)
     assert d["metric"].startswith("video-clips/sec") and d["unit"] == "clips/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -63,6 +64,28 @@ def test_bench_line_and_roofline_fields():
     assert d["hbm_gb"]["device_allocs_in_timed_region"] >= 0 and d["hbm_gb"]["reserved_growth_in_timed_region"] >= 0.0
 
 
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run prints the headline line without the --full legs; --dump-outputs writes what the last timed step returned:
+    float32 / float64 arrays, at most 64 MB, and a top-k that is the oracle's ranking of the dumped match logits."""
+    import numpy as np
+    import torch
+    from oracle import heads as OH
+    d = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--clips", "1", "--dump-outputs", str(tmp_path)])
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1) < 1e-2
+    assert not {"roofline", "cpu_baseline", "parity", "value_clips1", "full_forward_ms_per_clip", "match_stage"} & set(d)
+    files = sorted(tmp_path.iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 * 2 ** 20
+    out = {f.stem: np.load(f) for f in files}
+    assert all(f.suffix == ".npy" for f in files) and all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert all(np.isfinite(a).all() for a in out.values())
+    assert out["x3_1b"].shape == (32, 256) and out["match_features"].shape == (320, 256) and out["bank"].shape == (1000, 256)
+    assert out["match_logits"].shape == (32, 1000, 2) and out["topk_idx"].shape == (32, 20) and out["topk_score"].shape == (32, 20)
+    idx, score = OH.rank_topk(torch.from_numpy(out["match_logits"]), 20)
+    assert np.array_equal(out["topk_idx"], idx.numpy().astype(np.float64))
+    np.testing.assert_allclose(out["topk_score"], score.numpy(), rtol=1e-5, atol=1e-6)
+
+
 def test_timed_region_does_not_grow_the_allocator():
     """Default line (two body streams, side-stream tensors record_stream-ed): with the host held two steps ahead of the device and three
     warm-up steps the caching allocator has reached its plateau before timing starts -- no hipMalloc inside the timed region (before
@@ -79,8 +102,8 @@ def test_timed_region_does_not_grow_the_allocator():
 
 def test_bench_large_gallery_workload_c3():
     """configs[2]: 20 000-product gallery ranked without the [S,G,2] logits in HBM; parity of the ranking vs the oracle."""
-    d = run([sys.executable, "bench.py", "--workload", "c3", "--steps", "2", "--warmup", "1", "--clips", "1", "--cpu-frames", "1",
-             "--cpu-runs", "1", "--no-roofline"])
+    d = run([sys.executable, "bench.py", "--full", "--workload", "c3", "--steps", "2", "--warmup", "1", "--clips", "1", "--cpu-frames",
+             "1", "--cpu-runs", "1", "--no-roofline"])
     assert d["config"]["gallery"] == 20000 and "20k gallery" in d["metric"] and "configs[2]" in d["config"]["workload"]
     assert d["parity"]["ok"] is True and d["parity"]["topk_set_overlap"] >= 0.99 and d["parity"]["topk_equal"] is True
     m = d["match_stage"]                              # the MFMA similarity + top-k stage, timed on its own
@@ -109,8 +132,8 @@ def test_self_launch_branch_on_the_gpu():
     """`python bench.py --gpus N` starts its own ranks (child torch.distributed.run, before any HIP call in the parent) and relays
     rank 0's line; with one GPU the same branch is taken through SEAM_BENCH_SELF_LAUNCH=1.  --force-collective makes the single
     rank run the N > 1 step (RCCL group, side-stream all-gather, rank reductions, roofline leg on the collective path)."""
-    d = run([sys.executable, "bench.py", "--gpus", "1", "--force-collective", "--workload", "c4", "--steps", "2", "--warmup", "1",
-             "--clips", "1", "--no-cpu-baseline", "--no-extras"], SEAM_BENCH_SELF_LAUNCH="1")
+    d = run([sys.executable, "bench.py", "--full", "--gpus", "1", "--force-collective", "--workload", "c4", "--steps", "2", "--warmup",
+             "1", "--clips", "1", "--no-cpu-baseline", "--no-extras"], SEAM_BENCH_SELF_LAUNCH="1")
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["data"] == "synthetic"
     assert d["bank_identical_on_all_ranks"] is True and len(d["ms_per_step_per_rank"]) == 1
     assert d["allgather"]["median_us_slowest_rank"] > 0
