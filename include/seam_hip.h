@@ -29,6 +29,10 @@ typedef void* seam_stream_t; /* hipStream_t */
 
 /* ABI version (major*1000 + minor). */
 int seam_version(void);
+/* host helper: 1 when __umulhi(n, ceil(2^32 / d)) == n / d for every n < n_max (csrc/seam_fastdiv.h:
+ * (n_max - 1) * (ceil(2^32 / d) * d - 2^32) < 2^32; d == 1 counts as exact, d == 0 never) -- the rule
+ * every launcher applies before it hands a kernel such a multiplier */
+int seam_fastdiv_exact(unsigned d, unsigned long long n_max);
 /* hipGetErrorString for a code returned by any entry point. */
 const char* seam_error_string(int code);
 
@@ -247,6 +251,9 @@ int seam_maxpool2d_f32(const float* x, float* y, int N, int H, int W, int C, int
 
 int seam_maxpool2d_f16(const void* x, void* y, int N, int H, int W, int C, int k, int stride,
                        int pad, seam_stream_t stream);   /* fp16, C % 8 == 0 */
+/* host helper: 1 when the launcher takes the 3x3/s2/p1 kernel with 32-bit multiply-high index
+ * divisions (both exact by seam_fastdiv_exact), 0 when it takes the generic 64-bit kernel */
+int seam_maxpool2d_fast(int N, int H, int W, int C, int k, int stride, int pad, int f16);
 
 /* FPN top-down [TV]: lat[n,h,w,:] += top[n, floor(h*Ht/H), floor(w*Wt/W), :] (nearest). */
 int seam_upsample_add_f32(float* lat, const float* top, int N, int H, int W, int Ht, int Wt, int C,

@@ -30,6 +30,7 @@ class TrunkLayer(C.Structure):
 # name -> (restype, argtypes); mirrors include/seam_hip.h one to one
 SIGNATURES = {
     "seam_version": (_i, []),
+    "seam_fastdiv_exact": (_i, [C.c_uint, C.c_ulonglong]),
     "seam_error_string": (C.c_char_p, [_i]),
     "seam_option_count": (_i, []),
     "seam_option_name": (C.c_char_p, [_i]),
@@ -103,6 +104,7 @@ SIGNATURES = {
     "seam_avgpool_f16": (_i, [_p, _p, _i, _i, _i, _p]),
     "seam_mask_select_f16": (_i, [_p, _p, _p, _i, _i, _p]),
     "seam_maxpool2d_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_maxpool2d_fast": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "seam_upsample_add_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "seam_roi_align_f32": (_i, [_p, _p, _p, _p, C.POINTER(_i), _i, _f, _f, _f, _f, _i, _p, _p, _p, _i, _i, _i, _p]),
     "seam_nchw_to_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _p]),

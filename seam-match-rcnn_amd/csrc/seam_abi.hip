@@ -1,6 +1,7 @@
 // seam_abi.hip -- version / error helpers and the launchers' variant selectors of the C ABI (include/seam_hip.h).
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 
 namespace seam_opt {
@@ -21,6 +22,8 @@ int find(const char* name) {
 extern "C" {
 
 int seam_version(void) { return 1001; }   // 1.001
+
+int seam_fastdiv_exact(unsigned d, unsigned long long n_max) { return seam_fastdiv::exact(d, n_max) ? 1 : 0; }
 
 const char* seam_error_string(int code) { return hipGetErrorString((hipError_t)code); }
 

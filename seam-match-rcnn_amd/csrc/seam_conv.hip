@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -78,6 +79,7 @@ struct ConvArgs {
 // rl = row index local to the tile's first image (0 <= rl < Ho*Wo + tile rows) -> images past that one, ho, wo
 __device__ __forceinline__ void split_row(const ConvArgs& p, int HoWo, int rl, int& nl, int& ho, int& wo) {
     if (p.div_fast) {
+        // rl < Ho*Wo + 256 by HoWo (only when HoWo < 256), rm < Ho*Wo by Wo: exact by set_row_split()'s div_fast
         nl = HoWo >= 256 ? (rl >= HoWo ? 1 : 0) : (HoWo == 1 ? rl : (int)__umulhi((unsigned)rl, p.m_HoWo));
         const int rm = rl - nl * HoWo;
         ho = p.Wo == 1 ? rm : (int)__umulhi((unsigned)rm, p.m_Wo);
@@ -991,14 +993,14 @@ inline void choose_tile(int prec, int M, int K, int& best_bm, int& best_bn, int 
 
 struct DualSrc { const void* x2; int H2, W2, C2, stride2; };
 
-// multipliers of split_row(): exact while the operand times the divisor stays below 2^32 -- rl < Ho*Wo + 256 against Ho*Wo (used
-// only when Ho*Wo < 256), rm < Ho*Wo against Wo
+// multipliers of split_row(), exact by seam_fastdiv.h's rule -- rl < Ho*Wo + 256 against Ho*Wo (used only when Ho*Wo < 256),
+// rm < Ho*Wo against Wo; otherwise split_row() divides
 inline void set_row_split(ConvArgs& a) {
     const unsigned long long howo = (unsigned long long)a.Ho * a.Wo;
-    auto magic = [](unsigned long long d) -> unsigned { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); };
-    a.m_HoWo = magic(howo);
-    a.m_Wo = magic((unsigned long long)a.Wo);
-    a.div_fast = (a.Ho > 0 && a.Wo > 0 && howo * (unsigned long long)a.Wo < (1ull << 32)) ? 1 : 0;
+    a.m_HoWo = seam_fastdiv::magic(howo);
+    a.m_Wo = seam_fastdiv::magic((unsigned long long)a.Wo);
+    a.div_fast = (a.Ho > 0 && a.Wo > 0 && (howo >= 256 || seam_fastdiv::exact(howo, howo + 256)) &&
+                  seam_fastdiv::exact((unsigned long long)a.Wo, howo)) ? 1 : 0;
 }
 
 template <typename T>

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seam_fastdiv.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -232,9 +234,9 @@ __global__ void maxpool3s2_kernel(const T* __restrict__ x, T* __restrict__ y, in
     const int cv = C / E;
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;           // (ho, wo, c) of image blockIdx.y
     if (i >= (unsigned)(Ho * Wo * cv)) return;
-    const unsigned pix = cv == 1 ? i : __umulhi(i, m_cv);
+    const unsigned pix = cv == 1 ? i : __umulhi(i, m_cv);               // i < per_img: exact by maxpool_fast()
     const int c = (int)(i - pix * cv);
-    const int ho = (int)(Wo == 1 ? pix : __umulhi(pix, m_Wo));
+    const int ho = (int)(Wo == 1 ? pix : __umulhi(pix, m_Wo));         // pix < Ho * Wo: exact by maxpool_fast()
     const int wo = (int)pix - ho * Wo;
     const T* xi = x + (size_t)blockIdx.y * H * W * C + c * E;
     int hs[3], ws[3];
@@ -373,17 +375,27 @@ int preprocess(const float* img, void* out, int in_h, int in_w, int out_h, int o
     return (int)hipGetLastError();
 }
 
+// maxpool3s2_kernel divides i < per_img by cv and pix < Ho * Wo by Wo with __umulhi: only when both are exact (seam_fastdiv.h);
+// otherwise the generic kernel (64-bit / and %).  The stem's C = 64 (cv = 8 or 16, e = 0) always takes the fast path.
+template <typename T>
+bool maxpool_fast(int N, int H, int W, int C, int k, int stride, int pad) {
+    if (C <= 0 || C % Vec16<T>::N || k != 3 || stride != 2 || pad != 1 || H < 2 || W < 2 || N < 1 || N > 65535) return false;
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    const unsigned long long cv = (unsigned long long)(C / Vec16<T>::N), per_img = (unsigned long long)Ho * Wo * cv;
+    return per_img < (1ull << 31) && (unsigned long long)H * W * C < (1ull << 31) &&
+           seam_fastdiv::exact(cv, per_img) && seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)Ho * Wo);
+}
+
 template <typename T>
 int maxpool(const void* x, void* y, int N, int H, int W, int C, int k, int stride, int pad, void* stream) {
     if (C % Vec16<T>::N) return (int)hipErrorInvalidValue;
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     const size_t total = (size_t)N * Ho * Wo * (C / Vec16<T>::N);
     const size_t per_img = (size_t)Ho * Wo * (C / Vec16<T>::N);
-    if (k == 3 && stride == 2 && pad == 1 && H >= 2 && W >= 2 && N <= 65535 && per_img < (1u << 31) && (size_t)H * W * C < (1u << 31)) {
+    if (maxpool_fast<T>(N, H, W, C, k, stride, pad)) {
         const unsigned cv = (unsigned)(C / Vec16<T>::N);
-        auto magic = [](unsigned d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); };
         hipLaunchKernelGGL(maxpool3s2_kernel<T>, dim3((unsigned)((per_img + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)x, (T*)y, H, W, C, Ho, Wo, magic(cv), magic((unsigned)Wo));
+                           (const T*)x, (T*)y, H, W, C, Ho, Wo, seam_fastdiv::magic(cv), seam_fastdiv::magic((unsigned)Wo));
         return (int)hipGetLastError();
     }
     hipLaunchKernelGGL(maxpool_kernel<T>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, N,
@@ -479,6 +491,9 @@ int seam_maxpool2d_f32(const float* x, float* y, int N, int H, int W, int C, int
 }
 int seam_maxpool2d_f16(const void* x, void* y, int N, int H, int W, int C, int k, int stride, int pad, void* stream) {
     return maxpool<_Float16>(x, y, N, H, W, C, k, stride, pad, stream);
+}
+int seam_maxpool2d_fast(int N, int H, int W, int C, int k, int stride, int pad, int f16) {
+    return f16 ? maxpool_fast<_Float16>(N, H, W, C, k, stride, pad) : maxpool_fast<float>(N, H, W, C, k, stride, pad);
 }
 
 int seam_upsample_add_f32(float* lat, const float* top, int N, int H, int W, int Ht, int Wt, int C, void* stream) {

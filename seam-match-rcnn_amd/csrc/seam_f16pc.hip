@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 #if defined(SEAM_F16PC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/f16pc_abl.sh)
@@ -105,6 +106,7 @@ struct F16Args {
     unsigned long long* trace;   // SEAM_F16PC_TRACE builds only
 };
 
+// a / d for a < the bound f16pc_plan() checks for that divisor (seam_fastdiv.h)
 __device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 // wave-uniform geometry of one tile
@@ -700,8 +702,6 @@ __global__ void f16pc_pack_kernel(const float* __restrict__ w, _Float16* __restr
     }
 }
 
-inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
-
 // fills `a` for a supported shape; 0 = supported
 int f16pc_plan(F16Args& a, int N, int H, int W, int C, int K, int pad) {
     const bool c64 = C == 64 && K == 64;          // conv3x3_f16pc64: one chunk, one n-tile, large maps only
@@ -747,6 +747,16 @@ int f16pc_plan(F16Args& a, int N, int H, int W, int C, int K, int pad) {
     const long total = (long)a.tiles_m * a.tiles_n;
     if (total >= (1L << 24)) return 1;
     a.total_tiles = (int)total;
+    // fdivu numerator bounds: a tile index (< T + 2 * grid, tiles requested past a block's last one included) by tiles_n; tm < tiles_m
+    // by per_img; rb < per_img by bx; an output slot (< 256) by Ho*Wo, rm < Ho*Wo by Wo; a patch pixel (< 32 * NP) by PHi*PWi, PWi, 18
+    using seam_fastdiv::exact;
+    const unsigned long long tile_max = 2ull * total + (1ull << 16), pix_max = 32ull * NP;
+    if (!exact(a.tiles_n, tile_max) || !exact(a.per_img, a.tiles_m) || !exact(a.bx, a.per_img) || !exact(a.PHi * a.PWi, pix_max) ||
+        !exact(a.PWi, pix_max) || !exact(18, pix_max))
+        return 1;
+    if (a.mode == 1 && (!exact(a.Ho * a.Wo, 256) || !exact(a.Wo, a.Ho * a.Wo)))      // f16_slot() divides in mode 1 only
+        return 1;
+    using seam_fastdiv::magic;
     a.m_tiles_n = magic(a.tiles_n); a.m_bx = magic(a.bx); a.m_per_img = magic(a.per_img); a.m_PWi = magic(a.PWi);
     a.m_HoWo = magic(a.Ho * a.Wo); a.m_Wo = magic(a.Wo); a.m_slotpix = magic(a.PHi * a.PWi);
     return 0;

@@ -28,6 +28,7 @@
 #include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 #include <type_traits>
 
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(64 * PW_WAVES, 1) void pw_sw_kernel(const PwArgs p)
                     const int rl = min(row0 - img0 * HoWo + 16 * ih + 8 * q + (lane >> 3), p.M - 1 - img0 * HoWo);
                     const int nl = rl >= HoWo ? 1 : 0;
                     const int rm = rl - nl * HoWo;
-                    const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);
+                    const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);     // rm < Ho*Wo, Wo >= 2: exact by seam_conv1x1_sw_f32's check
                     const int wo = rm - ho * p.Wo;
                     const int ht = min((int)floorf((float)ho * fh), p.rH - 1);
                     const int wt = min((int)floorf((float)wo * fw), p.rW - 1);
@@ -287,8 +288,6 @@ __global__ __launch_bounds__(64 * PW_WAVES, 1) void pw_sw_kernel(const PwArgs p)
     }
 }
 
-inline unsigned magic_u32(unsigned long long d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); }
-
 // 0 = not served by this kernel (the caller falls back to the implicit GEMM); otherwise MT * 100 + NT
 inline int pw_config(int M, int C1, int C2, int K) {
     const int Ct = C1 + C2;
@@ -319,15 +318,16 @@ int seam_conv1x1_sw_f32(const float* x, const float* x2, const float* w, const f
     const int cfg = pw_config(M, C1, C2, K);
     if (!cfg || !shift || (C2 > 0 && (!x2 || res_mode)) || (res_mode && !residual) || res_mode < 0 || res_mode > 2)
         return (int)hipErrorInvalidValue;
-    if (res_mode == 2 && (Ho <= 0 || Wo <= 0 || rH <= 0 || rW <= 0 || M % (Ho * Wo) || Ho * Wo < 64 ||
-                          (unsigned long long)Ho * Wo * Wo >= (1ull << 32)))
+    // (the epilogue's ho = rm / Wo is a multiply-high division without a Wo == 1 branch)
+    if (res_mode == 2 && (Ho <= 0 || Wo <= 1 || rH <= 0 || rW <= 0 || M % (Ho * Wo) || Ho * Wo < 64 ||
+                          !seam_fastdiv::exact((unsigned)Wo, (unsigned long long)Ho * Wo)))
         return (int)hipErrorInvalidValue;
     PwArgs a;
     a.x = x; a.x2 = x2; a.w = w; a.shift = shift; a.res = residual; a.y = y;
     a.M = M; a.C1 = C1; a.C2 = C2; a.K = K; a.relu = relu;
     a.Ho = Ho; a.Wo = Wo; a.rH = rH; a.rW = rW;
-    a.m_HoWo = res_mode == 2 ? magic_u32((unsigned long long)Ho * Wo) : 0;
-    a.m_Wo = res_mode == 2 ? magic_u32((unsigned long long)Wo) : 0;
+    a.m_HoWo = res_mode == 2 ? seam_fastdiv::magic((unsigned long long)Ho * Wo) : 0;
+    a.m_Wo = res_mode == 2 ? seam_fastdiv::magic((unsigned long long)Wo) : 0;
     const int MT = cfg / 100, NT = cfg % 100;
     a.ns = K / (32 * NT);
     const int Ct = C1 + C2;

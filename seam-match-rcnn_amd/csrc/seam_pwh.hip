@@ -25,6 +25,7 @@
 #include <atomic>
 #include <stdint.h>
 #include <type_traits>
+#include "seam_fastdiv.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(64 * PWH_WAVES, 1) void pw_swh_kernel(const PwhArgs
                 const int rl = min(row0 - img0 * HoWo + 16 * ih + (lane >> 2), p.M - 1 - img0 * HoWo);
                 const int nl = rl >= HoWo ? 1 : 0;
                 const int rm = rl - nl * HoWo;
-                const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);
+                const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);         // rm < Ho*Wo, Wo >= 2: exact by seam_conv1x1_swh_f16's check
                 const int wo = rm - ho * p.Wo;
                 const int ht = min((int)floorf((float)ho * fh), p.rH - 1);
                 const int wt = min((int)floorf((float)wo * fw), p.rW - 1);
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(64 * PWH_WAVES, 1) void stem_swh_kernel(const StemA
             const int rl = rem0 + 16 * ih + (lane >> 2);                    // position relative to image n0's padded grid (may run into n0 + 1)
             const int nl = rl >= HpWp ? 1 : 0;
             const int rm = rl - nl * HpWp;
-            const int yy = (int)__umulhi((unsigned)rm, p.m_Wp);
+            const int yy = (int)__umulhi((unsigned)rm, p.m_Wp);           // rm < Hp*Wp: exact by seam_stem_s2d_swh_f16's check
             const int xx = rm - yy * p.Wp;
             const bool ok = yy < p.Ho && xx < p.Wo && n0 + nl < p.N;
             const long long d = ((long long)(n0 + nl) * p.Ho + yy) * p.Wo + xx - base_d;
@@ -468,15 +469,16 @@ int seam_conv1x1_swh_f16(const void* x, const void* x2, const void* w, const flo
     const int cfg = pwh_config(M, C1, C2, K);
     if (!cfg || (C2 > 0 && !x2) || relu < 0 || relu > 1 || res_mode < 0 || res_mode > 2 || (res_mode != 0) != (residual != nullptr))
         return (int)hipErrorInvalidValue;
-    if (res_mode == 2 && (Ho <= 0 || Wo <= 0 || rH <= 0 || rW <= 0 || M % ((long long)Ho * Wo) || (long long)Ho * Wo < 128 ||
-                          (unsigned long long)Ho * Wo * Wo >= (1ull << 32) || (M / ((long long)Ho * Wo)) * rH * rW * K * 2 >= (1ll << 31)))
+    // (the epilogue's ho = rm / Wo is a multiply-high division without a Wo == 1 branch)
+    if (res_mode == 2 && (Ho <= 0 || Wo <= 1 || rH <= 0 || rW <= 0 || M % ((long long)Ho * Wo) || (long long)Ho * Wo < 128 ||
+                          !seam_fastdiv::exact((unsigned)Wo, (unsigned long long)Ho * Wo) || (M / ((long long)Ho * Wo)) * rH * rW * K * 2 >= (1ll << 31)))
         return (int)hipErrorInvalidValue;
     PwhArgs a;
     a.x = (const _Float16*)x; a.x2 = (const _Float16*)x2; a.w = (const _Float16*)w; a.scale = scale; a.shift = shift;
     a.res = (const _Float16*)residual; a.y = (_Float16*)y;
     a.M = (int)M; a.C1 = C1; a.C2 = C2; a.K = K; a.relu = relu;
     a.Ho = Ho; a.Wo = Wo; a.rH = rH; a.rW = rW;
-    a.m_Wo = res_mode == 2 && Wo > 1 ? (unsigned)(((1ull << 32) + (unsigned)Wo - 1) / (unsigned)Wo) : 0;
+    a.m_Wo = res_mode == 2 ? seam_fastdiv::magic((unsigned)Wo) : 0;
     const int MT = cfg / 100, NT = cfg % 100;
     a.ns = K / (32 * NT);
     const int Ct = C1 + C2;
@@ -533,10 +535,10 @@ int seam_stem_s2d_swh_f16(const void* xpad, const void* w, const float* scale, c
     a.N = N; a.Ho = Ho; a.Wo = Wo; a.Hp = Ho + 3; a.Wp = Wo + 3; a.relu = relu;
     a.Mp = (long long)N * a.Hp * a.Wp;
     // (a 128-position tile must lie in one image or run into the next one only: Hp * Wp >= 128)
-    if ((long long)a.Hp * a.Wp < 128 || (long long)a.Hp * a.Wp >= (1ll << 31) / 2 || (unsigned long long)a.Hp * a.Wp * a.Wp >= (1ull << 32))
+    if ((long long)a.Hp * a.Wp < 128 || (long long)a.Hp * a.Wp >= (1ll << 31) / 2 || !seam_fastdiv::exact((unsigned)a.Wp, (unsigned long long)a.Hp * a.Wp))
         return (int)hipErrorInvalidValue;
     a.m_HpWp = 0;
-    a.m_Wp = (unsigned)(((1ull << 32) + (unsigned)a.Wp - 1) / (unsigned)a.Wp);
+    a.m_Wp = seam_fastdiv::magic((unsigned)a.Wp);
     const size_t lds = (size_t)64 * (256 * 2 + 16) + PWH_WAVES * TBUF + 2 * 64 * 4;
     const long long tiles = (a.Mp + 127) / 128;
     long long nblk = (tiles + PWH_WAVES - 1) / PWH_WAVES;

@@ -25,6 +25,7 @@
 #include <atomic>
 #include <stdint.h>
 #include <type_traits>
+#include "seam_fastdiv.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -66,6 +67,7 @@ struct PwhpcArgs {
     unsigned m_tiles_n;
 };
 
+// a tile index (< total_tiles + 2 * grid) / tiles_n: exact by pwhpc_plan()'s check (seam_fastdiv.h)
 __device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
@@ -318,8 +320,6 @@ __global__ void pwhpc_pack_kernel(const float* __restrict__ w, _Float16* __restr
     }
 }
 
-inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
-
 int pwhpc_plan(PwhpcArgs& a, long long M, int C, int K) {
     if (M <= 0 || C < 512 || (C % 256) || K < 128 || (K % 128)) return 1;      // an even number of 128-channel chunks
     if (M * (long long)(C > K ? C : K) * 2 >= (1LL << 40)) return 1;
@@ -330,7 +330,8 @@ int pwhpc_plan(PwhpcArgs& a, long long M, int C, int K) {
     const long long tiles = ((M + BM - 1) / BM) * a.tiles_n;
     if (tiles >= (1LL << 24)) return 1;
     a.total_tiles = (int)tiles;
-    a.m_tiles_n = magic(a.tiles_n);
+    if (!seam_fastdiv::exact(a.tiles_n, 2ull * tiles + (1ull << 16))) return 1;
+    a.m_tiles_n = seam_fastdiv::magic(a.tiles_n);
     return 0;
 }
 

@@ -35,6 +35,7 @@
 #include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 #if defined(SEAM_PWPC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/pwpc_abl.sh)
@@ -87,6 +88,7 @@ struct PwpcArgs {
     unsigned long long* trace;   // SEAM_PWPC_TRACE builds only
 };
 
+// a tile index (< total_tiles + 2 * grid) / tiles_n: exact by pwpc_plan()'s check (seam_fastdiv.h)
 __device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
@@ -360,8 +362,6 @@ __global__ void pwpc_pack_kernel(const float* __restrict__ w, float* __restrict_
     }
 }
 
-inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
-
 int pwpc_plan(PwpcArgs& a, long long M, int C, int K) {
     if (M <= 0 || C < 256 || (C % 128) || K < 128 || (K % 128)) return 1;       // (an even number of 64-channel chunks)
     if ((unsigned long long)BM * C * 4 >= kOob || (unsigned long long)BM * K * 4 >= kOob) return 1;
@@ -370,7 +370,8 @@ int pwpc_plan(PwpcArgs& a, long long M, int C, int K) {
     if (total >= (1LL << 24) || M >= (1LL << 31)) return 1;
     a.M = (int)M; a.C = C; a.K = K;
     a.tiles_n = K / 128; a.nchunks = C / 64; a.total_tiles = (int)total;
-    a.m_tiles_n = magic(a.tiles_n);
+    if (!seam_fastdiv::exact(a.tiles_n, 2ull * total + (1ull << 16))) return 1;
+    a.m_tiles_n = seam_fastdiv::magic(a.tiles_n);
     return 0;
 }
 

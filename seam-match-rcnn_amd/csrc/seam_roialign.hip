@@ -38,9 +38,11 @@ struct RoiArgs {
 };
 
 __device__ __forceinline__ int map_level(float x1, float y1, float x2, float y2, int k_min) {
-    // LevelMapper: floor(4 + log2(sqrt(area)/224) + 1e-6), clamped to [k_min, k_min+3]
+    // LevelMapper: floor(4 + log2(sqrt(area)/224) + 1e-6), clamped to [k_min, k_min+3], every step an fp32 operation rounded
+    // correctly (the host's torch.log2 and the oracle): log2 in fp64, rounded once -- the fast log2f is an ulp off at some
+    // sizes within a few ulps of 112 / 224 / 448 * 2^-1e-6 and moved those boxes one level down
     const float s = sqrtf((x2 - x1) * (y2 - y1));
-    float l = floorf(4.f + log2f(s / 224.f) + 1e-6f);
+    float l = floorf(4.f + (float)log2((double)(s / 224.f)) + 1e-6f);
     l = fminf(fmaxf(l, (float)k_min), (float)(k_min + 3));
     return (int)l - k_min;
 }

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "seam_fastdiv.h"
 #include "seam_opts.h"
 #if defined(SEAM_W24PC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/w24pc_abl.sh)
@@ -166,7 +167,8 @@ struct Wino24Args {
     unsigned long long* trace;   // SEAM_W24PC_TRACE builds only: s_memtime stamps of one block's waves 0 and 4 (else null)
 };
 
-// a / d for 0 <= a, a * d < 2^32, with m = ceil(2^32 / d) (d >= 2) -- one v_mul_hi_u32 / s_mul_hi_u32
+// a / d with m = ceil(2^32 / d) (d >= 2) -- one v_mul_hi_u32 / s_mul_hi_u32; exact for the numerator bound wino24_plan() checks
+// for each divisor (seam_fastdiv.h)
 __device__ __forceinline__ int fdiv(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 constexpr int NPIXMAX = 384;                       // raw patch pixels per buffer (3 x 16-byte loads per thread per chunk)
@@ -1528,8 +1530,20 @@ int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, long&
         a.part_q = (int)(pp.blocks / parts); a.part_r = (int)(pp.blocks % parts);
         if (a.nsplit > 1) blocks = 8L * (a.part_q + (a.part_r ? 1 : 0)) * a.tns;
     }
-    if (blocks >= (1L << 24)) return (int)hipErrorInvalidValue;     // also keeps every fdiv operand inside a * d < 2^32
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
+    if (blocks >= (1L << 24)) return (int)hipErrorInvalidValue;
+    // fdiv numerator bounds: a tile index (< blocks + grid, grid < 2^16) by tiles_n, a block's j by tns; tm by per_img; rb < per_img
+    // by bx; stacked: a tile row R < (tm + 1) * TY by tiles_y, a patch row (< 2^15 + pitch) by pitch; a slot id, patch pixel (< 2^16)
+    // by TX, PW
+    {
+        using seam_fastdiv::exact;
+        const unsigned long long tile_max = (unsigned long long)blocks + (1ull << 16), tm_max = tile_max / a.tiles_n + 1;
+        bool ok = exact(a.tiles_n, tile_max) && exact(a.tns, tile_max) && exact(a.per_img, tm_max);
+        if (a.stack) ok = ok && exact(tiles_y, (tm_max + 1) * a.TY[0]) && exact(2 * tiles_y + 2, (1ull << 15) + 2 * tiles_y + 2);
+        for (int r = 0; r < 3; ++r)
+            ok = ok && exact(a.bx[r], a.per_img) && exact(a.TX[r], 1ull << 16) && exact(4 * a.TX[r] + 2, 1ull << 16);
+        if (!ok) return (int)hipErrorInvalidValue;
+    }
+    using seam_fastdiv::magic;
     a.m_tns = magic(a.tns);
     a.m_tiles_n = magic(a.tiles_n); a.m_per_img = magic(a.per_img); a.m_tys = magic(tiles_y); a.m_pitch = magic(2 * tiles_y + 2);
     for (int r = 0; r < 3; ++r) { a.m_bx[r] = magic(a.bx[r]); a.m_TX[r] = magic(a.TX[r]); a.m_PW[r] = magic(4 * a.TX[r] + 2); }
