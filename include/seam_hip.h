@@ -392,6 +392,17 @@ int seam_rank_of_scores_f32(const float* score, const int64_t* target, int64_t* 
  * (evaluate_movingfashion.py:205-209): a [Na,4], b [Nb,4] xyxy -> out [Na,Nb]. */
 int seam_box_iou_f32(const float* a, const float* b, float* out, int Na, int Nb, seam_stream_t stream);
 
+/* Multi-DeepFashion2 ground-truth selection (evaluate_multiDF2.py:43-57,75-89), one launch for the N images of a product:
+ * in image n (detections det_off[n] .. det_off[n+1]-1 of det_boxes [Dtot,4] xyxy / det_scores [Dtot], GT boxes
+ * gt_off[n] .. gt_off[n+1]-1 of gt_boxes [Gtot,4] xyxy) the detection with score >= score_threshold whose pycocotools
+ * bbIou with GT row gt_row[n] (negative = from the end) is largest, first maximum over the thresholded subsequence.
+ * sel_idx[n]: index into the image's full detection list, sel_pos[n]: position inside the kept subsequence; both -1 when
+ * nothing is kept or status[n] != 0.  status[n]: 0, 1 = the image has no GT box, 2 = gt_row outside its GT rows (the GT is
+ * only consulted when some detection is kept).  det_off / gt_off: N+1 int32 offsets on the device. */
+int seam_gt_select_f32(const float* det_boxes, const float* det_scores, const int* det_off, const float* gt_boxes,
+                       const int* gt_off, const int* gt_row, float score_threshold, int* sel_idx, int* sel_pos, int* status,
+                       int N, seam_stream_t stream);
+
 /* Fused pairwise logits + top-k (a13 + a14 in one pass; no [Q,G,2] round trip through HBM):
  * same ranking rule and bit-identical x1-x0 as seam_pair_logits_f32 + seam_rank_topk_f32.
  * k <= 256, k <= G; ws: >= seam_pair_topk_workspace_floats(Q,G,k) floats of scratch. */

@@ -124,6 +124,7 @@ SIGNATURES = {
     "seam_score_reduce_seg_f32": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "seam_rank_of_scores_f32": (_i, [_p, _p, _p, _i, _i, _p]),
     "seam_box_iou_f32": (_i, [_p, _p, _p, _i, _i, _p]),
+    "seam_gt_select_f32": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _p]),
     "seam_pair_topk_workspace_floats": (_i64, [_i, _i, _i]),
     "seam_pair_topk_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "seam_match_trunk_workspace_floats": (_i64, [_i]),

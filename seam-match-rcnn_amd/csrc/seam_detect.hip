@@ -315,6 +315,76 @@ __global__ void box_iou_kernel(const float* __restrict__ a, const float* __restr
     out[i] = inter / (ap + aq - inter);
 }
 
+// pycocotools bbIou (maskApi.c) as evaluate_multiDF2.py:50-54,83-87 calls it: both boxes turned into xywh in fp32 (the
+// reference does that in NumPy on fp32 arrays), then widened to double.  g = the ground-truth box (bbIou's "dt"), d = the
+// detection (its "gt"); iscrowd is 0.  No clamping of negative extents: the arithmetic is copied literally, and contraction
+// into FMAs is off so that every product and sum rounds as the C code's does.
+__device__ __forceinline__ double bb_iou(float4 g, float4 d) {
+#pragma clang fp contract(off)
+    const float gw = g.z - g.x, gh = g.w - g.y, dw = d.z - d.x, dh = d.w - d.y;
+    const double gx = g.x, gy = g.y, dx = d.x, dy = d.y;
+    const double w = fmin((double)gw + gx, (double)dw + dx) - fmax(gx, dx);
+    if (w <= 0.0) return 0.0;
+    const double h = fmin((double)gh + gy, (double)dh + dy) - fmax(gy, dy);
+    if (h <= 0.0) return 0.0;
+    const double ga = (double)gw * (double)gh, da = (double)dw * (double)dh;
+    const double inter = w * h;
+    return inter / (ga + da - inter);
+}
+
+// evaluate_multiDF2.py:43-57,75-89: in every image, the detection with score >= thr that best overlaps the product's GT box
+// (first maximum over the thresholded subsequence, np.argmax).  One wave64 per image: lanes stride over the image's
+// detections, the position inside the kept subsequence comes from ballot + popcount, a shuffle reduction orders the
+// candidates by (IoU desc, position asc).  The GT row is consulted only when something is kept (the reference skips the
+// image before it looks at the GT): no kept detection -> (-1, -1, 0); no GT box -> status 1; row outside the GT rows -> 2.
+constexpr int kGtSelWaves = 4;
+__global__ __launch_bounds__(64 * kGtSelWaves) void gt_select_kernel(
+    const float* __restrict__ det_boxes, const float* __restrict__ det_scores, const int* __restrict__ det_off,
+    const float* __restrict__ gt_boxes, const int* __restrict__ gt_off, const int* __restrict__ gt_row, float thr,
+    int* __restrict__ sel_idx, int* __restrict__ sel_pos, int* __restrict__ status, int N) {
+    const int img = blockIdx.x * kGtSelWaves + (int)(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (img >= N) return;                                    // uniform over the wave
+    const int d0 = det_off[img], d1 = det_off[img + 1];
+    const int g0 = gt_off[img], ng = gt_off[img + 1] - g0;
+    int row = gt_row[img];
+    if (row < 0) row += ng;                                  // -1 = the last row, as NumPy indexes
+    const int code = ng <= 0 ? 1 : (row < 0 || row >= ng) ? 2 : 0;
+    const float4 g = code == 0 ? reinterpret_cast<const float4*>(gt_boxes)[g0 + row] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    double best = -1.0;
+    int best_pos = INT32_MAX, best_idx = -1, kept = 0;
+    for (int base = d0; base < d1; base += 64) {             // trip count uniform over the wave
+        const int d = base + lane;
+        const bool keep = d < d1 && det_scores[d] >= thr;
+        const uint64_t m = __ballot(keep);
+        if (keep && code == 0) {
+            const double iou = bb_iou(g, reinterpret_cast<const float4*>(det_boxes)[d]);
+            if (iou > best) {                                // a lane's positions ascend: keep its first maximum
+                best = iou;
+                best_pos = kept + __popcll(m & below);
+                best_idx = d - d0;
+            }
+        }
+        kept += __popcll(m);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ob = __shfl_xor(best, off);
+        const int op = __shfl_xor(best_pos, off), oi = __shfl_xor(best_idx, off);
+        if (ob > best || (ob == best && op < best_pos)) {
+            best = ob;
+            best_pos = op;
+            best_idx = oi;
+        }
+    }
+    if (lane == 0) {
+        const bool ok = kept > 0 && code == 0;
+        sel_idx[img] = ok ? best_idx : -1;
+        sel_pos[img] = ok ? best_pos : -1;
+        status[img] = kept > 0 ? code : 0;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -367,6 +437,16 @@ int seam_paste_masks_f32(const float* masks, const float* boxes, float* out, int
 int seam_box_iou_f32(const float* a, const float* b, float* out, int Na, int Nb, void* stream) {
     if (Na <= 0 || Nb <= 0) return 0;
     hipLaunchKernelGGL(box_iou_kernel, dim3((Na * Nb + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, out, Na, Nb);
+    return (int)hipGetLastError();
+}
+
+int seam_gt_select_f32(const float* det_boxes, const float* det_scores, const int* det_off, const float* gt_boxes,
+                       const int* gt_off, const int* gt_row, float score_threshold, int* sel_idx, int* sel_pos, int* status,
+                       int N, void* stream) {
+    if (N <= 0) return 0;
+    hipLaunchKernelGGL(gt_select_kernel, dim3((N + kGtSelWaves - 1) / kGtSelWaves), dim3(64 * kGtSelWaves), 0,
+                       (hipStream_t)stream, det_boxes, det_scores, det_off, gt_boxes, gt_off, gt_row, score_threshold,
+                       sel_idx, sel_pos, status, N);
     return (int)hipGetLastError();
 }
 

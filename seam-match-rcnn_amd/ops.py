@@ -1060,6 +1060,40 @@ def box_iou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def gt_select(det_boxes: torch.Tensor, det_scores: torch.Tensor, det_off, gt_boxes: torch.Tensor, gt_off, gt_row: torch.Tensor,
+              score_threshold: float):
+    """Multi-DF2 ground-truth selection for N images in one launch (``seam_gt_select_f32``; ref evaluate_multiDF2.py:43-57,75-89):
+    detections det_boxes [Dtot,4] / det_scores [Dtot] and GT boxes gt_boxes [Gtot,4] (xyxy, the images concatenated, device),
+    their boundaries det_off / gt_off [N+1] (host sequences, checked here and uploaded with the launch) and gt_row int32 [N]
+    (device; negative = from the end) -> (sel_idx, sel_pos, status) int32 [N] on the device.  Per image: the kept detection
+    (score >= threshold, compared in fp32 as torch compares) with the largest pycocotools bbIou against its GT row, first maximum,
+    as an index into the image's detections and as a position in the kept subsequence (-1 / -1 when nothing is kept); status
+    1 = no GT box, 2 = row out of range (the GT is consulted only when something is kept)."""
+    import numpy as np
+    det_boxes, det_scores = _req(det_boxes, name="det_boxes"), _req(det_scores, name="det_scores")
+    gt_boxes, gt_row = _req(gt_boxes, name="gt_boxes"), _req(gt_row, torch.int32, "gt_row")
+    n = gt_row.numel()
+    if det_boxes.dim() != 2 or det_boxes.shape[1] != 4 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4:
+        raise ValueError("gt_select: det_boxes and gt_boxes must be [*,4]")
+    if det_scores.numel() != det_boxes.shape[0]:
+        raise ValueError("gt_select: det_scores must hold one score per detection")
+    det_boxes = det_boxes if det_boxes.data_ptr() % 16 == 0 else det_boxes.clone()      # the kernel reads boxes as float4
+    gt_boxes = gt_boxes if gt_boxes.data_ptr() % 16 == 0 else gt_boxes.clone()
+    offs = []
+    for o, total, what in ((det_off, det_boxes.shape[0], "det_off"), (gt_off, gt_boxes.shape[0], "gt_off")):
+        o = np.asarray(o, dtype=np.int64).reshape(-1)
+        if o.size != n + 1 or o[0] != 0 or (np.diff(o) < 0).any() or int(o[-1]) > total or total >= 2 ** 31:
+            raise ValueError(f"gt_select: {what} must be N+1 non-decreasing int32 offsets from 0 inside the table")
+        offs.append(o)
+    offs_d = torch.as_tensor(np.concatenate(offs).astype(np.int32)).to(det_boxes.device, non_blocking=False)
+    outs = torch.empty((3, n), dtype=torch.int32, device=det_boxes.device)
+    _native.check(_native.lib().seam_gt_select_f32(_ptr(det_boxes), _ptr(det_scores), _ptr(offs_d[:n + 1]), _ptr(gt_boxes),
+                                                   _ptr(offs_d[n + 1:]), _ptr(gt_row), float(score_threshold), _ptr(outs[0]),
+                                                   _ptr(outs[1]), _ptr(outs[2]), n, _stream()),
+                  "seam_gt_select_f32")
+    return outs[0], outs[1], outs[2]
+
+
 PAIR_MFMA = True       # large banks: candidates on the fp32 matrix cores (seam_pair_topk_mfma_f32); False: the chunked VALU path
 
 
