@@ -591,7 +591,10 @@ int seam_match_trunk_f32(const float* roi, const seam_trunk_layer_t* conv, const
  * seam_conv_wgrad_f32: dw [K,C,R,S] (OIHW) = sum_{n,ho,wo} dy[n,ho,wo,k] * x[n,ho*stride+r-pad,wo*stride+s-pad,c]
  *   for x NHWC [N,H,W,C], dy NHWC [N,Ho,Wo,K]; C,K multiples of 4.  fp32-MFMA GEMM split over the pixel
  *   axis; ws: >= seam_conv_wgrad_workspace_floats(M = N*Ho*Wo, C, K, R, S) floats.  (Linear: R=S=1, H=W=1.)
- * seam_colsum_f32: out[k] = sum_m x[m,k]  (bias gradients); ws: >= seam_colsum_workspace_floats(M,K) floats. */
+ *   Refused (non-zero return, nothing launched or written): N <= 0, Ho <= 0, Wo <= 0, C % 4, K % 4, and either
+ *   operand of 2^31 bytes or more -- M*K*4 >= 2^31 (dy) or N*H*W*C*4 >= 2^31 (x): the kernel's buffer offsets are 32-bit.
+ * seam_colsum_f32: out[k] = sum_m x[m,k]  (bias gradients); ws: >= seam_colsum_workspace_floats(M,K) floats.
+ *   M = 0 writes zeros; K <= 0 returns 0 and writes nothing. */
 int64_t seam_conv_wgrad_workspace_floats(int M, int C, int K, int R, int S);
 int seam_conv_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
                         int R, int S, int stride, int pad, float* ws, seam_stream_t stream);
@@ -599,13 +602,17 @@ int64_t seam_colsum_workspace_floats(int M, int K);
 int seam_colsum_f32(const float* x, float* out, int M, int K, float* ws, seam_stream_t stream);
 
 /* Backward of conv_seq's last ReLU -> AvgPool2d(6,6) -> ReLU (models/match_head.py:56-60):
- * dy[n,hw,c] = y[n,hw,c] > 0 ? dpool[n,c] / HW : 0   (y = the ReLU'd conv output, NHWC [N,HW,C]). */
+ * dy[n,hw,c] = y[n,hw,c] > 0 ? dpool[n,c] / HW : 0   (y = the ReLU'd conv output, NHWC [N,HW,C]; a correctly
+ * rounded division).  N*HW*C == 0 returns 0 and writes nothing. */
 int seam_avgpool_relu_bwd_f32(const float* dpool, const float* y, float* dy, int N, int HW, int C,
                               seam_stream_t stream);
 
 /* nn.BatchNorm1d(256) in training mode (models/match_head.py:62): batch statistics over the M rows (M >= 2),
  * running_mean/var updated in place with `momentum` (unbiased variance), or left alone when NULL;
- * save_mean / save_invstd [F] feed seam_bn1d_bwd_f32 (dx, dgamma, dbeta). */
+ * save_mean / save_invstd [F] feed seam_bn1d_bwd_f32 (dx, dgamma, dbeta).  The statistics are shifted, corrected
+ * two-pass sums (their error scales with a column's spread, not its offset).
+ * Refused (nothing written): the forward when M < 2 or F <= 0 (torch: "Expected more than 1 value per channel when
+ * training"), the backward when M <= 0 or F <= 0. */
 int seam_bn1d_train_fwd_f32(const float* x, const float* gamma, const float* beta, float* y,
                             float* save_mean, float* save_invstd, float* running_mean,
                             float* running_var, int M, int F, float momentum, float eps,
@@ -615,11 +622,14 @@ int seam_bn1d_bwd_f32(const float* dy, const float* x, const float* save_mean, c
                       int frozen /* 1: eval-mode statistics, dx = gamma*invstd*dy */, seam_stream_t stream);
 
 /* nn.CrossEntropyLoss(weight=[w0,w1]) over [n,2] logits with int64 targets, mean reduction -- the criterion of
- * every loss of models/match_head.py (:213,257,367,386): loss [1] and dloss/dlogits [n,2] in one launch. */
+ * every loss of models/match_head.py (:213,257,367,386): loss [1] and dloss/dlogits [n,2] in one launch.
+ * n <= 0 is refused (nothing written).  If the weights of the targets' classes sum to 0, loss and dlogits are NaN (0/0),
+ * as in torch. */
 int seam_ce2_fwd_bwd_f32(const float* logits, const int64_t* target, const float* weight, float* loss,
                          float* dlogits, int64_t n, seam_stream_t stream);
 
-/* Gradients of seam_pair_logits_f32: g [Q,G,2] -> da [Q,256], db [G,256], dw [2,256], dbias [2]. */
+/* Gradients of seam_pair_logits_f32: g [Q,G,2] -> da [Q,256], db [G,256], dw [2,256], dbias [2].
+ * Refused (nothing written): D != 256, Q <= 0, G <= 0. */
 int seam_pair_logits_bwd_f32(const float* a, const float* b, const float* w, const float* g, float* da,
                              float* db, float* dw, float* dbias, int Q, int G, int D,
                              seam_stream_t stream);
@@ -628,7 +638,8 @@ int seam_pair_logits_bwd_f32(const float* a, const float* b, const float* w, con
  * as seq; only rows t < len[s] are written) and the parameter gradients, grads[11] = device pointers in the
  * reference's layouts: theta.weight [128,256], theta.bias [128], phi.weight, phi.bias, g.weight, g.bias,
  * concat_project.0.weight [256], W.weight [256,128], W.bias [256], attention_scorer.weight [256], .bias [1].
- * ws: >= seam_nlb_bwd_workspace_floats(S,Tmax) floats. */
+ * ws: >= seam_nlb_bwd_workspace_floats(S,Tmax) floats.  len[s] > Tmax is read as Tmax, len[s] <= 0 as an empty sequence
+ * (no row written).  Refused (nothing written): Tmax > 64 (a sequence is kept in LDS) or Tmax <= 0; S <= 0 returns 0. */
 int64_t seam_nlb_bwd_workspace_floats(int S, int Tmax);
 int seam_nlb_attnpool_bwd_f32(const float* seq, int64_t t_stride, int64_t s_stride, const int* len, int S,
                               int Tmax, const float* w_proj_t, const float* b_proj, const float* w_cat,
@@ -639,7 +650,7 @@ int seam_nlb_attnpool_bwd_f32(const float* seq, int64_t t_stride, int64_t s_stri
 /* Gradients of the non-local block ALONE -- the z output of seam_nlb_attnpool_f32, i.e. NONLocalBlock1D.forward called
  * directly and grad-enabled (ref models/nlb.py:66-101): dz rows at dz + s*dz_s_stride + t*dz_t_stride (256 floats each)
  * -> dseq (as above) and grads[9] = the first nine pointers of the list above (no attention scorer behind a direct call).
- * Same workspace as seam_nlb_attnpool_bwd_f32. */
+ * Same workspace, length rules and refusals as seam_nlb_attnpool_bwd_f32, and dz == NULL is refused. */
 int seam_nlb_block_bwd_f32(const float* seq, int64_t t_stride, int64_t s_stride, const int* len, int S, int Tmax,
                            const float* w_proj_t, const float* b_proj, const float* w_cat,
                            const float* w_out_t, const float* b_out, const float* dz, int64_t dz_t_stride,

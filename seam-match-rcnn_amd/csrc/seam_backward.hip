@@ -180,13 +180,14 @@ __global__ void colsum_final_kernel(const float* __restrict__ partial, float* __
 // ------------------------------------------------------------------------------------------------ pool / BN
 // AvgPool2d over the whole HW map followed by ReLU, and the ReLU in front of it (ref models/match_head.py:57-60):
 // dy[n][hw][c] = y[n][hw][c] > 0 ? dpool[n][c] / HW : 0     (pool > 0 whenever any y > 0, so its ReLU mask is implied)
+// A true division, correctly rounded like torch's mean backward: dpool * (1/HW) rounds twice and is up to 1.3 ulp off.
 __global__ void avgpool_relu_bwd_kernel(const float* __restrict__ dpool, const float* __restrict__ y, float* __restrict__ dy,
                                         int HW, int C, size_t total) {
-    const float inv = 1.f / (float)HW;
+    const float hw = (float)HW;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         const size_t n = i / ((size_t)HW * C);
-        dy[i] = y[i] > 0.f ? dpool[n * C + c] * inv : 0.f;
+        dy[i] = y[i] > 0.f ? dpool[n * C + c] / hw : 0.f;
     }
 }
 
@@ -198,14 +199,22 @@ __global__ void bn1d_train_fwd_kernel(const float* __restrict__ x, const float* 
                                       float eps) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    float mean = 0.f;
-    for (int m = 0; m < M; ++m) mean += x[(size_t)m * F + f];
-    mean /= (float)M;
-    float var = 0.f;
+    // Shifted, corrected two-pass statistics: the first pass sums x - x[0] (its error scales with the column's spread,
+    // not its offset); the second adds back sum(x - mean0) / M, which is exactly mean - mean0, and takes the variance as
+    // sum d^2 - (sum d)^2 / M.  A plain sum of x is off by ~ M * u * |mean|, and the backward turns that error of the saved
+    // mean into gradient error (e.g. a non-zero bias gradient in front of the BatchNorm) growing with the batch.
+    const float x0 = x[f];
+    float s = 0.f;
+    for (int m = 0; m < M; ++m) s += x[(size_t)m * F + f] - x0;
+    const float mean0 = x0 + s / (float)M;
+    float sd = 0.f, var = 0.f;
     for (int m = 0; m < M; ++m) {
-        const float d = x[(size_t)m * F + f] - mean;
+        const float d = x[(size_t)m * F + f] - mean0;
+        sd += d;
         var = fmaf(d, d, var);
     }
+    const float mean = mean0 + sd / (float)M;
+    var = fmaxf(var - sd * (sd / (float)M), 0.f);
     const float vb = var / (float)M;
     const float inv = 1.f / sqrtf(vb + eps);
     const float g = gamma[f], bta = beta[f];

@@ -287,3 +287,72 @@ def test_input_gradient_and_frozen_bn():
     close(xd.grad, xc.grad, rtol=1e-3, atol_frac=2e-4, msg="conv_seq: d roi_features", l2=L2_KEYS)
     for k, prm in mp.named_parameters():
         close(prm.grad, p[k].grad, rtol=1e-3, atol_frac=2e-4, msg=k, l2=L2_KEYS)
+
+
+def test_engine_step_at_reference_batch_size():
+    """The reference's training batch (train_movingfashion.py: 16 shops of one shop image + 10 frames, n_frames = 3): 16 x 10
+    frames of 1-2 ROIs, ~250 ROIs -- conv_wgrad splits its pixel axis differently from the small fixtures, and BatchNorm and
+    the pair logits reduce over ~10x more rows.  vs the oracle's autograd, with the tolerances of the ragged test above."""
+    import random
+    rng = random.Random(2024)
+    types, prod, img = [], [], []
+    i = 0
+    for p in range(16):
+        types.append(1); prod.append(p); img.append(i); i += 1
+        for _ in range(10):
+            nb = rng.choice((1, 2))
+            types += [0] * nb; prod += [p] * nb; img += [i] * nb
+            i += 1
+    assert 230 <= len(types) <= 340
+    types_t = torch.IntTensor(types)
+    x = torch.from_numpy(synth.roi_features(47, len(types)))
+    mp, ta = make_heads(3)
+    logits, l1, l2 = engine_step(mp, ta, x.to(DEV), types_t, prod, img)
+    # the oracle in float64 (its own fp32 rounding kept out of the comparison; the losses build float tensors by default)
+    f64 = lambda sd: {k: (v.double() if v.dtype.is_floating_point else v) for k, v in sd.items()}  # noqa: E731
+    mps, tas = f64(to_torch(synth.match_predictor_state(11))), f64(to_torch(synth.temporal_aggregator_state(12)))
+    torch.set_default_dtype(torch.float64)
+    try:
+        ref = OL.train_step(x.double(), types_t, prod, img, mps, tas, n_frames=3)
+    finally:
+        torch.set_default_dtype(torch.float32)
+    close(logits, ref["logits"], msg="logits")
+    np.testing.assert_allclose(float(l1), float(ref["match_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(l2), float(ref["aggregation_loss"]), rtol=1e-4)
+    for k, p in mp.named_parameters():
+        close(p.grad, ref["grads_mp"][k], rtol=1e-3, atol_frac=2e-4, msg="mp." + k, zero=ZERO_BN_TRAIN + ("mp.linear.1.bias",), l2=L2_KEYS)
+    for k, p in ta.named_parameters():
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        close(g, ref["grads_ta"][k], rtol=1e-3, atol_frac=2e-4, msg="ta." + k, zero=ZERO_BN_TRAIN + ZERO_ALWAYS, l2=L2_KEYS)
+    close(mp.linear[1].running_mean, mps["linear.1.running_mean"], msg="bn running_mean follows the oracle")
+    close(mp.linear[1].running_var, mps["linear.1.running_var"], msg="bn running_var follows the oracle")
+
+
+@pytest.mark.parametrize("rows", [64, 65])
+def test_aggregator_backward_row_limit(rows):
+    """The NLB backward keeps a sequence in LDS up to 64 rows: a grad-enabled Mode-A pass whose longest sequence has 65 rows
+    must raise from backward() (not hand back a gradient); 64 rows must match the oracle's autograd."""
+    from seam_match_rcnn_amd._native import SeamNativeError
+    _, ta = make_heads(-1)
+    ta.train()
+    types = torch.IntTensor([1] + [0] * rows + [0, 0])
+    ids = torch.tensor([0] + [1] * rows + [2, 2])
+    x = torch.from_numpy(synth.roi_features(48, len(types)))
+    out = ta(x.to(DEV), types, ids)
+    g0, g2 = rnd(49, *out[0].shape), rnd(50, *out[2].shape)
+    loss = (out[0] * g0.to(DEV)).sum() + (out[2] * g2.to(DEV)).sum()
+    if rows > 64:
+        with pytest.raises(SeamNativeError):
+            loss.backward()
+        return
+    loss.backward()
+    sd = to_torch(synth.temporal_aggregator_state(12))
+    buf = ("running_mean", "running_var", "num_batches_tracked")
+    p = {k: (v if k.endswith(buf) else v.clone().requires_grad_(True)) for k, v in sd.items()}
+    oout = OH.temporal_aggregation_forward(x, types, ids, p, bn_train=True)
+    ((oout[0] * g0).sum() + (oout[2] * g2).sum()).backward()
+    close(out[0], oout[0], msg="x3_1b"); close(out[2], oout[2], msg="x5")
+    for k, prm in ta.named_parameters():
+        want = p[k].grad if p[k].grad is not None else torch.zeros_like(p[k])
+        got = prm.grad if prm.grad is not None else torch.zeros_like(prm)
+        close(got, want, rtol=1e-3, atol_frac=2e-4, msg="ta." + k, zero=ZERO_BN_TRAIN + ZERO_ALWAYS, l2=L2_KEYS)
