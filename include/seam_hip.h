@@ -672,6 +672,40 @@ int64_t seam_resize_workspace_bytes(int H, int W, int OH, int OW);
 int seam_resize_bicubic_u8(const uint8_t* in, uint8_t* out, int H, int W, int OH, int OW, void* ws,
                            seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training branch of the RoI heads (ref models/matchrcnn.py:333-472, torchvision roi_heads [TV]), csrc/seam_roi_train.hip.
+ * Every kernel reduces in a fixed order: a launch is bit-identical to the next.
+ *
+ * seam_roi_sample_f32: select_training_samples per image, one workgroup each.  cand [N,P,4] xyxy (the image's proposals
+ *   followed by its GT boxes; n_cand[i] <= P rows are real), keys [N,P] (one uniform draw per candidate), gt_boxes [N,G,4],
+ *   gt_labels int64 [N,G] (n_gt[i] rows real).  Matcher(0.5, 0.5) on box_iou in fp32 (first GT on ties; background label
+ *   0, matched index 0); BalancedPositiveNegativeSampler(batch, pos_max / batch): the min(#pos, pos_max) positives
+ *   (label >= 1) and min(#neg, batch - that) negatives (label 0) with the smallest (key, index); the sampled rows in
+ *   ascending candidate order -> idx, labels, matched (int64 [N,batch]), boxes and BoxCoder((wx,wy,ww,wh)).encode targets
+ *   ([N,batch,4]); rows past the count: idx/labels/matched -1, boxes/targets 0.  count int32 [N,2] = (rows, positives),
+ *   (-1,-1) for an image with no GT box.  Refused: P outside 1..16384, G outside 1..32767, batch outside 1..16384,
+ *   pos_max outside 0..batch, a NULL pointer.
+ * seam_fastrcnn_loss_fwd_bwd_f32: fastrcnn_loss [TV] on R rows: loss[0] = mean cross entropy of class_logits [R,ncls]
+ *   against labels int64 [R]; loss[1] = smooth-L1 (beta 1/9) of box_regression [R,4*ncls] at the label's 4 deltas
+ *   against targets [R,4], summed over the rows with label > 0, / R; dclass, dbox = their gradients (for a unit upstream
+ *   gradient; zeros outside the label's deltas).  A label outside 0..ncls-1 makes both losses NaN.  One workgroup.
+ * seam_mask_loss_fwd_bwd_f32: maskrcnn_loss [TV] on P positive ROIs: logits [P,14,14,4,ncls] (the sub-pixel layout of
+ *   MaskRCNNPredictor), labels int64 [P], rois [P,4] xyxy in the masks' frame; ROI k's GT mask is the uint8 [H,W] map at
+ *   masks + mask_off[k] with (H,W) = mask_hw[2k..2k+1].  Target = roi_align(mask, roi, 28, 1.0, sampling_ratio=-1,
+ *   aligned=False), recomputed per bin and never stored; loss = mean BCE-with-logits on the label channel;
+ *   dlogits (layout of logits) = its gradient, zeros in the other channels.  ws: P floats.  Refused: P outside
+ *   1..21399 (P*784 < 2^24), ncls outside 1..65536, a NULL pointer. */
+int seam_roi_sample_f32(const float* cand, const int* n_cand, const float* keys, const float* gt_boxes, const int64_t* gt_labels,
+                        const int* n_gt, int N, int P, int G, int batch, int pos_max, float wx, float wy, float ww, float wh,
+                        int64_t* idx, int64_t* labels, int64_t* matched, float* boxes, float* targets, int* count,
+                        seam_stream_t stream);
+int seam_fastrcnn_loss_fwd_bwd_f32(const float* class_logits, const float* box_regression, const int64_t* labels,
+                                   const float* targets, int R, int ncls, float* loss, float* dclass, float* dbox,
+                                   seam_stream_t stream);
+int seam_mask_loss_fwd_bwd_f32(const float* logits, const int64_t* labels, const float* rois, const uint8_t* masks,
+                               const int64_t* mask_off, const int* mask_hw, int P, int ncls, float* loss, float* dlogits,
+                               float* ws, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,3 +151,149 @@ class WeightedCE2Function(torch.autograd.Function):
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
         return dlogits * g, None, None
+
+
+# ---------------------------------------------------------------------------------------------------- RoI heads training
+# (ref models/matchrcnn.py:333-472).  Gradients stop at the RoIAlign outputs: the feature maps are constants here.
+
+def _pad_rows(w: torch.Tensor, rows: int) -> torch.Tensor:
+    """[K,...] -> [rows,...] with zero rows appended (pack_conv_dgrad needs Cout % 32 == 0)."""
+    if w.shape[0] == rows:
+        return w.contiguous()
+    out = w.new_zeros((rows,) + tuple(w.shape[1:]))
+    out[:w.shape[0]] = w
+    return out
+
+
+def _pad_cols(x: torch.Tensor, cols: int) -> torch.Tensor:
+    """[M,K] -> [M,cols], zero columns appended."""
+    if x.shape[1] == cols:
+        return x.contiguous()
+    out = x.new_zeros((x.shape[0], cols))
+    out[:, :x.shape[1]] = x
+    return out
+
+
+def _up32(k: int) -> int:
+    return (k + 31) // 32 * 32
+
+
+class BoxHeadFunction(torch.autograd.Function):
+    """TwoMLPHead + FastRCNNPredictor (ref torchvision roi_heads box branch): x NHWC [R,7,7,256] ->
+    (class_logits [R,ncls], box_regression [R,4*ncls]).  fc6 is the 7x7 valid conv over the tile; fc7 and the fused
+    ncls + 4*ncls predictor rows are 1x1 convs.  No input gradient (RoIAlign has no backward here)."""
+
+    @staticmethod
+    def forward(ctx, x, w6, b6, w7, b7, wc, bc, wb, bb):
+        x = x.detach().contiguous()
+        r = x.shape[0]
+        w6c = w6.detach().view(w6.shape[0], x.shape[-1], 7, 7)
+        h6 = ops.conv2d(x, ops.pack_conv(w6c, b6, wino=False), relu=True)                       # [R,1,1,1024]
+        h7 = ops.linear(h6.view(r, -1), ops.pack_conv(w7, b7), relu=True)                       # [R,1024]
+        wp = torch.cat([wc.detach(), wb.detach()], 0)
+        o = ops.linear(h7, ops.pack_conv(wp, torch.cat([bc.detach(), bb.detach()], 0)), out_f32=True)
+        ncls = wc.shape[0]
+        ctx.save_for_backward(x, h6, h7, w6c, w7, wp)
+        ctx.ncls = ncls
+        return o[:, :ncls].contiguous(), o[:, ncls:].contiguous()
+
+    @staticmethod
+    def backward(ctx, dcls, dbox):
+        x, h6, h7, w6c, w7, wp = ctx.saved_tensors
+        r, ncls = x.shape[0], ctx.ncls
+        kp = _up32(wp.shape[0])
+        do = torch.zeros((r, kp), dtype=F32, device=x.device)
+        if dcls is not None:
+            do[:, :ncls] = dcls
+        if dbox is not None:
+            do[:, ncls:wp.shape[0]] = dbox
+        dwp = ops.conv_wgrad(h7.view(r, 1, 1, -1), do.view(r, 1, 1, kp), 1, 1).view(kp, -1)[:wp.shape[0]]
+        dbp = ops.colsum(do)[:wp.shape[0]]
+        dh7 = ops.conv2d(do.view(r, 1, 1, kp), ops.pack_conv_dgrad(_pad_rows(wp, kp), wino=False), relu=2,
+                         residual=h7.view(r, 1, 1, -1))                                          # [R,1,1,1024]
+        dw7 = ops.conv_wgrad(h6, dh7, 1, 1).view(w7.shape)
+        db7 = ops.colsum(dh7)
+        dh6 = ops.conv2d(dh7, ops.pack_conv_dgrad(w7, wino=False), relu=2, residual=h6)
+        dw6 = ops.conv_wgrad(x, dh6, 7, 7).view(w6c.shape[0], -1)
+        db6 = ops.colsum(dh6)
+        return None, dw6, db6, dw7, db7, dwp[:ncls], dbp[:ncls], dwp[ncls:], dbp[ncls:]
+
+
+class MaskHeadFunction(torch.autograd.Function):
+    """MaskRCNNHeads (4 x conv3x3 pad 1 + ReLU) + MaskRCNNPredictor: x NHWC [P,14,14,256] -> logits in the sub-pixel
+    layout [P,14,14,4*ncls] (detection.MaskRCNNPredictor.forward).  conv5_mask (ConvTranspose2d 2x2/s2) is the 1x1 conv
+    to the 4 sub-pixel groups (a,b) (channel (a*2+b)*256+co), so its backward is a 1x1 dgrad + wgrad with no shuffle.
+    No input gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, w4, b4, wt, bt, wl, bl):
+        x = x.detach().contiguous()
+        p = x.shape[0]
+        ws3 = (w1, w2, w3, w4)
+        acts = [x]
+        for w, b in zip(ws3, (b1, b2, b3, b4)):
+            acts.append(ops.conv2d(acts[-1], ops.pack_conv(w, b, pad=1, wino=False), relu=True))
+        u = ops.conv2d(acts[-1], ops.pack_conv(wt, bt, transposed2x2=True), relu=True)          # [P,14,14,4*256]
+        ncls = wl.shape[0]
+        logits = ops.linear(u.view(p * 784, -1), ops.pack_conv(wl, bl)).view(p, 14, 14, 4 * ncls)
+        ctx.save_for_backward(*acts, u, *(w.detach() for w in ws3), wt.detach(), wl.detach())
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        a0, a1, a2, a3, a4, u, w1, w2, w3, w4, wt, wl = ctx.saved_tensors
+        p = a0.shape[0]
+        ncls, cr = wl.shape[0], wl.shape[1]
+        kp = _up32(ncls)
+        # mask_fcn_logits: one 1x1 conv over the P*196*4 rows (the sub-pixel group is the fastest row index)
+        dl = _pad_cols(dlogits.contiguous().view(p * 784, ncls).to(F32), kp).view(p * 784, 1, 1, kp)
+        dwl = ops.conv_wgrad(u.view(p * 784, 1, 1, cr), dl, 1, 1)[:ncls]
+        dbl = ops.colsum(dl)[:ncls]
+        du = ops.conv2d(dl, ops.pack_conv_dgrad(_pad_rows(wl, kp), wino=False), relu=2,
+                        residual=u.view(p * 784, 1, 1, cr)).view(p, 14, 14, 4 * cr)
+        # conv5_mask as the 1x1 conv with rows (a*2+b)*Cout+co over Cin
+        cin, cout = wt.shape[0], wt.shape[1]
+        wt1 = wt.permute(2, 3, 1, 0).reshape(4 * cout, cin)
+        dwt1 = ops.conv_wgrad(a4, du, 1, 1).view(2, 2, cout, cin)
+        dwt = dwt1.permute(3, 2, 0, 1).contiguous()
+        dbt = ops.colsum(du).view(4, cout).sum(0)
+        dy = ops.conv2d(du, ops.pack_conv_dgrad(wt1, wino=False), relu=2, residual=a4)
+        acts, weights = (a0, a1, a2, a3), (w1, w2, w3, w4)
+        dws, dbs = [None] * 4, [None] * 4
+        for l in (3, 2, 1, 0):
+            dws[l] = ops.conv_wgrad(acts[l], dy, 3, 3, pad=1)
+            dbs[l] = ops.colsum(dy)
+            if l > 0:
+                dy = ops.conv2d(dy, ops.pack_conv_dgrad(weights[l], pad_fwd=1, wino=False), relu=2, residual=acts[l])
+        return (None, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dws[3], dbs[3], dwt, dbt, dwl, dbl)
+
+
+class FastRCNNLossFunction(torch.autograd.Function):
+    """fastrcnn_loss [TV] -> (loss_classifier, loss_box_reg), 0-d each; the forward launch computes both gradients."""
+
+    @staticmethod
+    def forward(ctx, class_logits, box_regression, labels, targets):
+        loss, dcls, dbox = ops.fastrcnn_loss_fwd_bwd(class_logits.detach().contiguous(), box_regression.detach().contiguous(),
+                                                     labels, targets.detach())
+        ctx.save_for_backward(dcls, dbox)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box):
+        dcls, dbox = ctx.saved_tensors
+        return dcls * g_cls, dbox * g_box, None, None
+
+
+class MaskLossFunction(torch.autograd.Function):
+    """maskrcnn_loss [TV] on the sub-pixel logits; the forward launch computes the gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rois, masks, mask_off, mask_hw):
+        loss, dl = ops.mask_loss_fwd_bwd(logits.detach().contiguous(), labels, rois.detach(), masks, mask_off, mask_hw)
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None, None, None

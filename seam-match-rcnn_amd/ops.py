@@ -1256,3 +1256,73 @@ def resize_bicubic_u8(img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor
     ws = torch.empty((int(lib.seam_resize_workspace_bytes(h, w, out_h, out_w)),), dtype=torch.uint8, device=img.device)
     _native.check(lib.seam_resize_bicubic_u8(_ptr(img), _ptr(out), h, w, out_h, out_w, _ptr(ws), _stream()), "seam_resize_bicubic_u8")
     return out
+
+
+# ------------------------------------------------------------------------------ RoI heads training branch (csrc/seam_roi_train.hip)
+SAMPLE_MAX_CANDIDATES = 16384      # per image: rpn_post_nms_top_n_train (8000) + the GT boxes fit
+
+
+def roi_sample(cand: torch.Tensor, n_cand: torch.Tensor, keys: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor,
+               n_gt: torch.Tensor, batch: int = 512, pos_max: int = 128, weights=(10.0, 10.0, 5.0, 5.0)):
+    """select_training_samples [TV] on padded per-image arrays: cand [N,P,4] (proposals then GT boxes), n_cand int32 [N],
+    keys [N,P], gt_boxes [N,G,4], gt_labels int64 [N,G], n_gt int32 [N] -> (idx, labels, matched int64 [N,batch],
+    boxes, targets [N,batch,4], count int32 [N,2] = (sampled rows, positives)); rows past the count hold -1 / 0."""
+    cand, keys, gt_boxes = _req(cand, name="cand"), _req(keys, name="keys"), _req(gt_boxes, name="gt_boxes")
+    n_cand, n_gt = _req(n_cand, torch.int32, "n_cand"), _req(n_gt, torch.int32, "n_gt")
+    gt_labels = _req(gt_labels, torch.int64, "gt_labels")
+    n, p = cand.shape[0], cand.shape[1]
+    g = gt_boxes.shape[1]
+    if p > SAMPLE_MAX_CANDIDATES:
+        raise ValueError(f"roi_sample: {p} candidates per image exceed the kernel's capacity of {SAMPLE_MAX_CANDIDATES}")
+    if tuple(keys.shape) != (n, p) or tuple(gt_labels.shape) != (n, g) or n_cand.numel() != n or n_gt.numel() != n:
+        raise ValueError("roi_sample: inconsistent shapes")
+    dev = cand.device
+    idx = torch.empty((n, batch), dtype=torch.int64, device=dev)
+    labels = torch.empty_like(idx)
+    matched = torch.empty_like(idx)
+    boxes = torch.empty((n, batch, 4), dtype=F32, device=dev)
+    targets = torch.empty_like(boxes)
+    count = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    wx, wy, ww, wh = (float(w) for w in weights)
+    _native.check(_native.lib().seam_roi_sample_f32(_ptr(cand), _ptr(n_cand), _ptr(keys), _ptr(gt_boxes), _ptr(gt_labels), _ptr(n_gt),
+                                                    n, p, g, int(batch), int(pos_max), wx, wy, ww, wh, _ptr(idx), _ptr(labels),
+                                                    _ptr(matched), _ptr(boxes), _ptr(targets), _ptr(count), _stream()),
+                  "seam_roi_sample_f32")
+    return idx, labels, matched, boxes, targets, count
+
+
+def fastrcnn_loss_fwd_bwd(class_logits: torch.Tensor, box_regression: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor):
+    """fastrcnn_loss [TV] -> (loss [2] = (classifier, box_reg), dclass_logits, dbox_regression) for a unit upstream gradient."""
+    class_logits, box_regression = _req(class_logits, name="class_logits"), _req(box_regression, name="box_regression")
+    labels, targets = _req(labels, torch.int64, "labels"), _req(targets, name="targets")
+    r, ncls = class_logits.shape
+    if tuple(box_regression.shape) != (r, 4 * ncls) or labels.numel() != r or tuple(targets.shape) != (r, 4):
+        raise ValueError("fastrcnn_loss_fwd_bwd: inconsistent shapes")
+    loss = torch.empty((2,), dtype=F32, device=class_logits.device)
+    dcls, dbox = torch.empty_like(class_logits), torch.empty_like(box_regression)
+    _native.check(_native.lib().seam_fastrcnn_loss_fwd_bwd_f32(_ptr(class_logits), _ptr(box_regression), _ptr(labels), _ptr(targets),
+                                                               r, ncls, _ptr(loss), _ptr(dcls), _ptr(dbox), _stream()),
+                  "seam_fastrcnn_loss_fwd_bwd_f32")
+    return loss, dcls, dbox
+
+
+def mask_loss_fwd_bwd(logits: torch.Tensor, labels: torch.Tensor, rois: torch.Tensor, masks: torch.Tensor, mask_off: torch.Tensor,
+                      mask_hw: torch.Tensor):
+    """maskrcnn_loss [TV] on the sub-pixel logits [P,14,14,4*ncls]: labels int64 [P], rois [P,4] in the masks' frame, masks a flat
+    uint8 buffer holding each ROI's GT mask at byte mask_off[k] (int64 [P]) with size mask_hw[k] (int32 [P,2])
+    -> (loss [], dlogits like logits) for a unit upstream gradient."""
+    logits, rois = _req(logits, name="logits"), _req(rois, name="rois")
+    labels, masks = _req(labels, torch.int64, "labels"), _req(masks, torch.uint8, "masks")
+    mask_off, mask_hw = _req(mask_off, torch.int64, "mask_off"), _req(mask_hw, torch.int32, "mask_hw")
+    p = logits.shape[0]
+    ncls = logits.shape[-1] // 4
+    if tuple(logits.shape) != (p, 14, 14, 4 * ncls) or labels.numel() != p or tuple(rois.shape) != (p, 4) or mask_off.numel() != p \
+            or tuple(mask_hw.shape) != (p, 2):
+        raise ValueError("mask_loss_fwd_bwd: inconsistent shapes")
+    loss = torch.empty((), dtype=F32, device=logits.device)
+    dl = torch.empty_like(logits)
+    ws = torch.empty((max(p, 1),), dtype=F32, device=logits.device)
+    _native.check(_native.lib().seam_mask_loss_fwd_bwd_f32(_ptr(logits), _ptr(labels), _ptr(rois), _ptr(masks), _ptr(mask_off),
+                                                           _ptr(mask_hw), p, ncls, _ptr(loss), _ptr(dl), _ptr(ws), _stream()),
+                  "seam_mask_loss_fwd_bwd_f32")
+    return loss, dl
