@@ -706,6 +706,52 @@ int seam_mask_loss_fwd_bwd_f32(const float* logits, const int64_t* labels, const
                                const int64_t* mask_off, const int* mask_hw, int P, int ncls, float* loss, float* dlogits,
                                float* ws, seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training branch of the RPN (torchvision RegionProposalNetwork.assign_targets_to_anchors / compute_loss [TV]),
+ * csrc/seam_rpn_train.hip.  Sized for 2^20 anchors per image: many workgroups per image, state in the caller's workspace.
+ * Float reductions run in a fixed order and the only atomics are integer ones: a launch is bit-identical to the next.
+ * Caps (a call outside them is refused and writes nothing): N 1..4096 images, A 1..2^20 anchors, G 1..seam_rpn_max_gt() = 128
+ * GT boxes per image, batch 1..1024.
+ *
+ * seam_rpn_match_f32: Matcher(fg_thresh, bg_thresh, allow_low_quality_matches=True) of anchors [A,4] (shared by the batch)
+ *   against gt_boxes [N,G,4] (n_gt[i] rows real; boxes must be finite), box_iou in fp32 in torchvision's expression order.
+ *   Per anchor the maximum over the GT boxes (first GT on ties): < bg_thresh -> label 0, < fg_thresh -> label -1 (ignored),
+ *   else label 1.  Low-quality rule: every anchor whose IoU with some GT box EQUALS that box's largest IoU over the image's
+ *   anchors becomes foreground, matched to its own argmax GT (a GT box that overlaps no anchor has maximum 0, which every
+ *   anchor equals: the whole image turns foreground, as in torchvision).  n_gt[i] == 0: all background.
+ *   labels int8 [N,A]; matched int32 [N,A] = the argmax GT of a foreground anchor, 0 otherwise.
+ *   ws: seam_rpn_match_workspace_floats(N, A, G) floats (0 = outside the caps).  Also refused: bg_thresh > fg_thresh, NULL.
+ * seam_rpn_sample_f32: BalancedPositiveNegativeSampler(batch, pos_max / batch) on those labels with one uniform key per
+ *   anchor (keys [N,A]): the min(#foreground, pos_max) foreground and min(#background, batch - that) background anchors
+ *   with the smallest (key, index), by a radix select over ord(key) << 20 | index in global memory.  idx int64 [N,batch]:
+ *   the sampled anchors in ascending order, -1 past the count; slabels (1 / 0; -1 past the count) and smatched int64
+ *   [N,batch]; targets [N,batch,4] = BoxCoder((1,1,1,1)).encode(matched GT, anchor) on the foreground rows, 0 elsewhere;
+ *   count int32 [N,2] = (rows, foreground rows).  ws: seam_rpn_sample_workspace_bytes(N, batch) bytes.
+ *   Also refused: pos_max outside 0..batch, NULL.
+ * seam_rpn_gather_patches_f32: the 3x3 input window of the RPN conv at M sampled pixels.  maps: HOST array of L device
+ *   pointers to NHWC fp32 maps [N,H_l,W_l,C]; hw: HOST array of 2L ints (H_l, W_l); rows: device int32 [M,4] =
+ *   (image, level, y, x) -> out [M,3,3,C], zeros outside the map (the conv's padding) and for a row whose image, level or
+ *   pixel is out of range.  Refused: M outside 1..2^20, L outside 1..8, C outside 4..4096 or not a multiple of 4, NULL.
+ * seam_rpn_loss_fwd_bwd_f32: compute_loss on the M sampled rows.  head [M,head_cols]: the head's outputs at each row's
+ *   pixel (A objectness logits, then 4A deltas); slot int32 [M]: the row's anchor slot a; labels int64 [M] (1 / 0);
+ *   targets [M,4].  loss[0] = mean BCE-with-logits(head[r,a], label); loss[1] = smooth-L1 (beta 1/9) of
+ *   head[r, A+4a..A+4a+3] against targets on the label-1 rows, summed, / M.  grad [M,grad_cols] = both gradients for a
+ *   unit upstream gradient, zeros elsewhere (grad_cols >= 5A: the padding the input-gradient conv wants).  A slot outside
+ *   0..A-1 or a label outside {0,1} makes both losses NaN.  One workgroup.  Refused: M outside 1..2^20, A outside 1..64,
+ *   head_cols or grad_cols outside 5A..1024, NULL. */
+int seam_rpn_max_gt(void);
+int64_t seam_rpn_match_workspace_floats(int N, int A, int G);
+int seam_rpn_match_f32(const float* anchors, const float* gt_boxes, const int* n_gt, int N, int A, int G, float fg_thresh,
+                       float bg_thresh, int8_t* labels, int* matched, float* ws, seam_stream_t stream);
+int64_t seam_rpn_sample_workspace_bytes(int N, int batch);
+int seam_rpn_sample_f32(const int8_t* labels, const int* matched, const float* keys, const float* anchors, const float* gt_boxes,
+                        int N, int A, int G, int batch, int pos_max, int64_t* idx, int64_t* slabels, int64_t* smatched,
+                        float* targets, int* count, void* ws, seam_stream_t stream);
+int seam_rpn_gather_patches_f32(const void* const* maps, const int* hw, const int* rows, int M, int N, int L, int C, float* out,
+                                seam_stream_t stream);
+int seam_rpn_loss_fwd_bwd_f32(const float* head, const int* slot, const int64_t* labels, const float* targets, int M, int A,
+                              int head_cols, int grad_cols, float* loss, float* grad, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

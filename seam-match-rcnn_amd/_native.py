@@ -158,6 +158,13 @@ SIGNATURES = {
     "seam_roi_sample_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
     "seam_fastrcnn_loss_fwd_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "seam_mask_loss_fwd_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "seam_rpn_max_gt": (_i, []),
+    "seam_rpn_match_workspace_floats": (_i64, [_i, _i, _i]),
+    "seam_rpn_match_f32": (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
+    "seam_rpn_sample_workspace_bytes": (_i64, [_i, _i]),
+    "seam_rpn_sample_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "seam_rpn_gather_patches_f32": (_i, [C.POINTER(_p), C.POINTER(_i), _p, _i, _i, _i, _i, _p, _p]),
+    "seam_rpn_loss_fwd_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -297,3 +297,56 @@ class MaskLossFunction(torch.autograd.Function):
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
         return dl * g, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------- RPN training
+# d loss / d head output is zero outside the sampled (pixel, anchor) slots and the feature maps are constants, so the
+# gradient of the 3x3 conv and of the two 1x1 predictors is exactly a sum over the sampled rows: no dense backward conv.
+
+class RPNHeadRowsFunction(torch.autograd.Function):
+    """RPNHead at M sampled pixels: patches NHWC [M,3,3,256] (the conv's 3x3 input windows, zero padding included; slots
+    that share a pixel are separate rows) -> [M, A + 4A] (objectness logits | deltas).  No input gradient."""
+
+    @staticmethod
+    def forward(ctx, patches, w, b, wc, bc, wb, bb):
+        x = patches.detach().contiguous()
+        m = x.shape[0]
+        t = ops.conv2d(x, ops.pack_conv(w, b, pad=0, wino=False), relu=True)                    # [M,1,1,256]
+        wp = torch.cat([wc.detach().reshape(wc.shape[0], -1), wb.detach().reshape(wb.shape[0], -1)], 0)
+        o = ops.linear(t.view(m, -1), ops.pack_conv(wp, torch.cat([bc.detach(), bb.detach()], 0)), out_f32=True)
+        ctx.save_for_backward(x, t, wp)
+        ctx.shapes = (wc.shape, wb.shape)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        x, t, wp = ctx.saved_tensors
+        m, k = x.shape[0], wp.shape[0]
+        kp = _up32(k)
+        do = _pad_cols(do.to(F32), kp).view(m, 1, 1, kp)
+        dwp = ops.conv_wgrad(t, do, 1, 1).view(kp, -1)[:k]
+        dbp = ops.colsum(do)[:k]
+        dt = ops.conv2d(do, ops.pack_conv_dgrad(_pad_rows(wp, kp), wino=False), relu=2, residual=t)    # [M,1,1,256]
+        dw = ops.conv_wgrad(x, dt, 3, 3)
+        db = ops.colsum(dt)
+        a = ctx.shapes[0][0]
+        return (None, dw, db, dwp[:a].reshape(ctx.shapes[0]), dbp[:a], dwp[a:].reshape(ctx.shapes[1]), dbp[a:])
+
+
+class RPNLossFunction(torch.autograd.Function):
+    """RegionProposalNetwork.compute_loss [TV] on the sampled rows -> (loss_objectness, loss_rpn_box_reg), 0-d each; the
+    forward launch computes the gradient."""
+
+    @staticmethod
+    def forward(ctx, head, slot, labels, targets, num_anchors):
+        loss, grad = ops.rpn_loss_fwd_bwd(head.detach().contiguous(), slot, labels, targets.detach(), num_anchors,
+                                          _up32(head.shape[1]))
+        ctx.save_for_backward(grad)
+        ctx.a, ctx.k = num_anchors, head.shape[1]
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_obj, g_box):
+        (grad,) = ctx.saved_tensors
+        scale = torch.cat([g_obj.expand(ctx.a), g_box.expand(grad.shape[1] - ctx.a)])
+        return (grad * scale)[:, :ctx.k], None, None, None, None

@@ -9,29 +9,16 @@
 #include <stdint.h>
 
 #include "seam_hip.h"
+#include "seam_train_common.h"
 
 namespace {
+
+using namespace seam_train;       // wave_sum, block_sum256, ord_key, iou_gt_prop, box_area
 
 constexpr int SAMPLE_THREADS = 1024;
 constexpr int SAMPLE_MAX_CAND = 16384;     // == NMS_MAX_BOXES: rpn_post_nms_top_n_train (8000) + the GT boxes fit
 constexpr int SAMPLE_IDX_BITS = 14;        // 2^14 == SAMPLE_MAX_CAND: a candidate index fits below the key
 constexpr int MASK_M = 28;                 // mask target resolution (MaskRCNNPredictor output)
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order sum over a 256-thread block (4 waves)
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
 
 // exclusive prefix sum of v over a 1024-thread block (thread order); *total = the sum of all v
 __device__ __forceinline__ int block_scan1024(int v, int* s_wave, int* total) {
@@ -52,26 +39,6 @@ __device__ __forceinline__ int block_scan1024(int v, int* s_wave, int* total) {
     }
     *total = tot;
     return base + x - v;
-}
-
-// float -> unsigned with the same order (negative keys below positive ones)
-__device__ __forceinline__ unsigned ord_key(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// torchvision box_iou(gt, proposals) element, in its expression order and without FMA contraction
-__device__ __forceinline__ float iou_gt_prop(float4 g, float area_g, float4 p, float area_p) {
-#pragma clang fp contract(off)
-    const float iw = fmaxf(fminf(g.z, p.z) - fmaxf(g.x, p.x), 0.f);
-    const float ih = fmaxf(fminf(g.w, p.w) - fmaxf(g.y, p.y), 0.f);
-    const float inter = iw * ih;
-    return inter / ((area_g + area_p) - inter);
-}
-
-__device__ __forceinline__ float box_area(float4 b) {
-#pragma clang fp contract(off)
-    return (b.z - b.x) * (b.w - b.y);
 }
 
 struct SampleArgs {

@@ -518,6 +518,12 @@ class RegionProposalNetwork(nn.Module):
                              f"candidates per image seam_nms_sorted_f32 handles (max {NMS_MAX_BOXES // 5})")
         self.pre_nms_top_n, self.post_nms_top_n = pre_nms_top_n_test, post_nms_top_n_test
         self.nms_thresh, self.min_size = nms_thresh, min_size
+        # training branch (torchvision's defaults): proposal counts, anchor matcher and sampler
+        self.pre_nms_top_n_train, self.post_nms_top_n_train = int(pre_nms_top_n_train), int(post_nms_top_n_train)
+        self.batch_size_per_image, self.positive_fraction = 256, 0.5
+        self.fg_iou_thresh, self.bg_iou_thresh = 0.7, 0.3
+        # torch.Generator (on the features' device) that draws the sampler's keys; None: torch's default generator
+        self.sample_generator = None
         self._anchor_cache = {}
 
     def anchors(self, padded_hw, feat_hws, device):
@@ -526,7 +532,23 @@ class RegionProposalNetwork(nn.Module):
             self._anchor_cache[key] = [torch.from_numpy(a).to(device) for a in grid_anchors(padded_hw, feat_hws)]
         return self._anchor_cache[key]
 
-    def forward(self, feats: "OrderedDict[str, torch.Tensor]", image_sizes, padded_hw, padded_out: bool = False):
+    def forward(self, feats: "OrderedDict[str, torch.Tensor]", image_sizes, padded_hw, padded_out: bool = False, targets=None):
+        """Proposals of the batch (``filter_proposals``).  In training mode WITH ``targets`` (one dict with "boxes" in the
+        resized frame per image) it returns ``(proposals, {"loss_objectness", "loss_rpn_box_reg"})``: the proposals come from
+        ``pre_nms_top_n_train`` / ``post_nms_top_n_train`` and carry no tape, the losses are ``training_losses``.  Every other
+        call -- training mode without targets included -- returns the test-mode proposals."""
+        if self.training and targets is not None:
+            if cdt(self) != torch.float32 or cdt(self.head) != torch.float32 or feats["0"].dtype != torch.float32:
+                raise NotImplementedError("the training branch of the RPN is fp32 only: call set_compute_dtype(torch.float32)")
+            if 5 * self.pre_nms_top_n_train > NMS_MAX_BOXES or self.pre_nms_top_n_train < 1 or self.post_nms_top_n_train < 1:
+                raise ValueError(f"rpn_pre_nms_top_n_train = {self.pre_nms_top_n_train}: 5 levels x top-n must be within 1..{NMS_MAX_BOXES}")
+            with torch.no_grad():
+                proposals = self._proposals(feats, image_sizes, padded_hw, padded_out, self.pre_nms_top_n_train,
+                                            self.post_nms_top_n_train)
+            return proposals, self.training_losses(feats, padded_hw, targets)
+        return self._proposals(feats, image_sizes, padded_hw, padded_out, self.pre_nms_top_n, self.post_nms_top_n)
+
+    def _proposals(self, feats, image_sizes, padded_hw, padded_out, pre_nms_top_n, post_nms_top_n):
         """RegionProposalNetwork.filter_proposals for the whole batch: per-level top-k + decode + clip + sigmoid in ONE
         launch per level (``seam_rpn_topk_decode_f32``: a radix select over the logits in place, no device sort), small-box
         filter, per-level NMS, first post_nms_top_n -- one host synchronisation (the variable-length split of the
@@ -540,7 +562,7 @@ class RegionProposalNetwork(nn.Module):
         dev = fl[0].device
         anchors = self.anchors(padded_hw, [f.shape[1:3] for f in fl], dev)
         a = self.head.num_anchors
-        ks = [min(self.pre_nms_top_n, f.shape[1] * f.shape[2] * a) for f in fl]
+        ks = [min(pre_nms_top_n, f.shape[1] * f.shape[2] * a) for f in fl]
         if max(ks) <= ops.rpn_topk_max():
             heads = self.head.fused(fl)
             ktot = sum(ks)
@@ -555,12 +577,65 @@ class RegionProposalNetwork(nn.Module):
         else:
             bx, sc, lv = self._topk_by_sort(self.head(fl), anchors, image_sizes, ks, n, dev)
         valid = ((bx[..., 2] - bx[..., 0]) >= self.min_size) & ((bx[..., 3] - bx[..., 1]) >= self.min_size)
-        order, sel, _ = batched_nms_images(bx, sc, lv, valid, self.nms_thresh, self.post_nms_top_n)
+        order, sel, _ = batched_nms_images(bx, sc, lv, valid, self.nms_thresh, post_nms_top_n)
         kept = torch.gather(bx, 1, order[..., None].expand(-1, -1, 4))
         if padded_out:
-            return compact_rows(sel, [kept], self.post_nms_top_n)[0].contiguous(), sel.sum(1)
+            return compact_rows(sel, [kept], post_nms_top_n)[0].contiguous(), sel.sum(1)
         counts = sel.sum(1).tolist()                                                    # the one sync
         return list(kept[sel].split(counts, 0))
+
+    def training_losses(self, feats, padded_hw, targets):
+        """assign_targets_to_anchors + compute_loss [TV] -> {"loss_objectness", "loss_rpn_box_reg"} (0-d fp32, with a tape into
+        ``head``'s six parameters; the feature maps are constants).
+
+        Matcher(fg_iou_thresh, bg_iou_thresh, allow_low_quality_matches=True) on all anchors of an image in the order of
+        ``grid_anchors`` (level, y, x, anchor), then BalancedPositiveNegativeSampler with the key rule of
+        ``NewRoIHeads.training_losses``: one uniform key per anchor from ``sample_generator``, the positives / negatives with the
+        smallest (key, index) are kept -- torchvision's distribution, not its ``randperm`` draw.  The head is re-evaluated on the
+        3x3 windows of the sampled pixels only (``autograd.RPNHeadRowsFunction``) and the losses are computed on those rows, so
+        the loss value is exactly the function that is differentiated.  One device->host copy (the sampled anchors)."""
+        from ..autograd import RPNHeadRowsFunction, RPNLossFunction
+        fl = list(feats.values())
+        n, dev = fl[0].shape[0], fl[0].device
+        if len(targets) != n:
+            raise ValueError("one target dict per image is needed")
+        na = self.head.num_anchors
+        hws = [tuple(int(v) for v in f.shape[1:3]) for f in fl]
+        key = ("cat", tuple(padded_hw), tuple(hws), str(dev))
+        if key not in self._anchor_cache:
+            self._anchor_cache[key] = torch.cat(self.anchors(padded_hw, hws, dev)).contiguous()
+        anchors = self._anchor_cache[key]
+        gts = [t["boxes"].to(dev, torch.float32).reshape(-1, 4) for t in targets]
+        n_gt = [int(g.shape[0]) for g in gts]
+        gtp = torch.zeros((n, max(max(n_gt), 1), 4), dtype=torch.float32, device=dev)
+        for i, g in enumerate(gts):
+            gtp[i, :n_gt[i]] = g
+        labels, matched = ops.rpn_match(anchors, gtp, torch.tensor(n_gt, dtype=torch.int32).to(dev), self.fg_iou_thresh,
+                                        self.bg_iou_thresh)
+        keys = torch.rand(labels.shape, generator=self.sample_generator, device=dev)
+        bs = int(self.batch_size_per_image)
+        idx, slab, _, stargets, count = ops.rpn_sample(labels, matched, keys, anchors, gtp, bs, int(bs * self.positive_fraction))
+        host = torch.cat([count.to(torch.int64), idx], 1).cpu().numpy()                          # the one device->host copy
+        rows = [int(c) for c in host[:, 0]]
+        if sum(rows) == 0:
+            raise ValueError("the RPN sampler kept no anchor: every anchor of the batch is in the ignored IoU band")
+        flat = np.concatenate([host[i, 2:2 + c] for i, c in enumerate(rows)])                    # anchor index (level, y, x, a)
+        img = np.repeat(np.arange(n), rows)
+        starts = np.cumsum([0] + [h * w * na for h, w in hws])
+        lvl = np.searchsorted(starts, flat, side="right") - 1
+        rem = flat - starts[lvl]
+        pix, slot = rem // na, rem % na
+        wl = np.asarray([w for _, w in hws], np.int64)[lvl]
+        meta = np.stack([img, lvl, pix // wl, pix % wl, slot], 1).astype(np.int32)
+        meta = torch.from_numpy(meta).to(dev)
+        patches = ops.rpn_gather_patches(fl, meta[:, :4].contiguous())
+        h = self.head
+        o = RPNHeadRowsFunction.apply(patches, h.conv.weight, h.conv.bias, h.cls_logits.weight, h.cls_logits.bias,
+                                      h.bbox_pred.weight, h.bbox_pred.bias)
+        lab = torch.cat([slab[i, :c] for i, c in enumerate(rows)])
+        tgt = torch.cat([stargets[i, :c] for i, c in enumerate(rows)])
+        loss_objectness, loss_rpn_box_reg = RPNLossFunction.apply(o, meta[:, 4].contiguous(), lab, tgt, na)
+        return dict(loss_objectness=loss_objectness, loss_rpn_box_reg=loss_rpn_box_reg)
 
     def _clip_hw(self, image_sizes, dev):
         key = ("clip", tuple(map(tuple, image_sizes)), str(dev))

@@ -12,6 +12,9 @@ identical, so the 14x14 ROI features are computed once here.
 Training branch of the heads (``NewRoIHeads.forward`` with ``self.training``)    ref :333-472
 -> ``([], {loss_classifier, loss_box_reg, loss_mask, loss_match})``; backward fills the gradients
 of the box, mask and match heads (the features are constants: no RoIAlign backward).
+
+``MatchRCNN.forward(images, targets)`` in training mode adds the RPN's two losses (``detection.RegionProposalNetwork``)
+and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43), backbone frozen.
 """
 from __future__ import annotations
 
@@ -219,6 +222,53 @@ class MatchRCNN(VideoMatchRCNN):
 
     def load_saved_matchrcnn(self, sd):
         self.load_state_dict(sd, strict=False)
+
+    def forward(self, images, targets=None):
+        """Eval: the detections (``VideoMatchRCNN.forward``).  Training mode with ``targets``: the reference's loss dict
+        (ref stuffs/engine.py:40-43) -- loss_classifier, loss_box_reg, loss_mask, loss_match from the RoI heads and
+        loss_objectness, loss_rpn_box_reg from the RPN.  ``backward()`` reaches ``rpn.head`` and the RoI heads; the feature
+        maps are computed without a tape, so every backbone parameter must be frozen (``requires_grad_(False)``)."""
+        if not self.training or targets is None:
+            return super().forward(images, targets)
+        if any(p.requires_grad for p in self.backbone.parameters()):
+            raise NotImplementedError(
+                "MatchRCNN training: the FPN / ResNet backward is not built, so the backbone cannot learn; freeze it with "
+                "`for p in model.backbone.parameters(): p.requires_grad_(False)` (a silent partial gradient would be worse)")
+        if any(det.cdt(m) != torch.float32 for m in (self, self.backbone, self.rpn, self.roi_heads)):
+            raise NotImplementedError("MatchRCNN training is fp32 only: call set_compute_dtype(torch.float32)")
+        images = list(images)
+        if len(images) != len(targets):
+            raise ValueError("one target dict per image is needed")
+        with torch.no_grad():
+            feats, sizes, orig, padded = self.extract_features([i.detach() for i in images])
+        dev = feats["0"].device
+        tg = []
+        for t, s, o in zip(targets, sizes, orig):         # GeneralizedRCNNTransform.resize of the targets [TV]
+            t = dict(t, boxes=det.GeneralizedRCNNTransform.rescale_boxes(t["boxes"].to(dev).to(torch.float32), o, s))
+            if "masks" in t:
+                t["masks"] = resize_masks_nearest(t["masks"].to(dev), s)
+            tg.append(t)
+        proposals, rpn_losses = self.rpn(feats, sizes, padded, targets=tg)
+        _, losses = self.roi_heads(feats, proposals, sizes, tg)
+        losses = dict(losses)
+        losses.update(rpn_losses)
+        return losses
+
+
+def resize_masks_nearest(masks: torch.Tensor, hw) -> torch.Tensor:
+    """``F.interpolate(masks[:, None].float(), size=hw)[:, 0].byte()`` (mode "nearest": source index = floor(dst * in / out) in
+    fp32, clamped) as two index selections, which keep the masks uint8 [n,H,W] -> [n,h,w]."""
+    h, w = int(hw[0]), int(hw[1])
+    if masks.dim() != 3:
+        raise ValueError("targets['masks'] must be [n_gt,H,W]")
+    if tuple(masks.shape[1:]) == (h, w):
+        return masks
+
+    def src(n_in, n_out):
+        scale = np.float32(n_in) / np.float32(n_out)
+        i = np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64)
+        return torch.from_numpy(np.minimum(i, n_in - 1)).to(masks.device)
+    return masks.index_select(1, src(masks.shape[1], h)).index_select(2, src(masks.shape[2], w)).contiguous()
 
 
 def matchrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True, **kwargs):

@@ -251,10 +251,12 @@ class VideoMatchRCNN(nn.Module):
         super().__init__()
         self.transform = det.GeneralizedRCNNTransform(min_size, max_size)
         self.backbone = backbone
-        self.rpn = det.RegionProposalNetwork(rpn_pre_nms_top_n_test, rpn_post_nms_top_n_test, rpn_nms_thresh)
+        self.rpn = det.RegionProposalNetwork(rpn_pre_nms_top_n_test, rpn_post_nms_top_n_test, rpn_nms_thresh,
+                                             pre_nms_top_n_train=kwargs.pop("rpn_pre_nms_top_n_train", 2000),
+                                             post_nms_top_n_train=kwargs.pop("rpn_post_nms_top_n_train", 2000))
         self.roi_heads = self.roi_heads_cls(num_classes, n_frames, box_score_thresh, box_nms_thresh,
                                             box_detections_per_img)
-        self._ignored_kwargs = kwargs       # training-only knobs of torchvision's MaskRCNN ctor
+        self._ignored_kwargs = kwargs       # the other training-only knobs of torchvision's MaskRCNN ctor
 
     def set_compute_dtype(self, dtype: torch.dtype):
         """torch.float32 (default: exact fp32 MFMA) or torch.float16 (fp16 MFMA with fp32 accumulation for

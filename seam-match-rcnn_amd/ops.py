@@ -1326,3 +1326,93 @@ def mask_loss_fwd_bwd(logits: torch.Tensor, labels: torch.Tensor, rois: torch.Te
                                                            _ptr(mask_hw), p, ncls, _ptr(loss), _ptr(dl), _ptr(ws), _stream()),
                   "seam_mask_loss_fwd_bwd_f32")
     return loss, dl
+
+
+# ------------------------------------------------------------------------------ RPN training branch (csrc/seam_rpn_train.hip)
+RPN_MAX_ANCHORS = 1 << 20          # per image
+
+
+def rpn_max_gt() -> int:
+    return int(_native.lib().seam_rpn_max_gt())
+
+
+def rpn_match(anchors: torch.Tensor, gt_boxes: torch.Tensor, n_gt: torch.Tensor, fg_thresh: float = 0.7, bg_thresh: float = 0.3):
+    """Matcher(fg, bg, allow_low_quality_matches=True) [TV]: anchors [A,4] (shared by the batch), gt_boxes [N,G,4], n_gt int32 [N]
+    -> (labels int8 [N,A]: -1 ignored / 0 background / 1 foreground, matched int32 [N,A]: the argmax GT of a foreground anchor)."""
+    anchors, gt_boxes = _req(anchors, name="anchors"), _req(gt_boxes, name="gt_boxes")
+    n_gt = _req(n_gt, torch.int32, "n_gt")
+    if anchors.dim() != 2 or anchors.shape[1] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4 or n_gt.numel() != gt_boxes.shape[0]:
+        raise ValueError("rpn_match: inconsistent shapes")
+    a, (n, g) = anchors.shape[0], gt_boxes.shape[:2]
+    lib = _native.lib()
+    nws = int(lib.seam_rpn_match_workspace_floats(n, a, g))
+    if nws <= 0:
+        raise ValueError(f"rpn_match: N = {n}, A = {a}, G = {g} outside the kernel's caps (A <= {RPN_MAX_ANCHORS}, G <= {rpn_max_gt()})")
+    dev = anchors.device
+    labels = torch.empty((n, a), dtype=torch.int8, device=dev)
+    matched = torch.empty((n, a), dtype=torch.int32, device=dev)
+    ws = torch.empty((nws,), dtype=F32, device=dev)
+    _native.check(lib.seam_rpn_match_f32(_ptr(anchors), _ptr(gt_boxes), _ptr(n_gt), n, a, g, float(fg_thresh), float(bg_thresh),
+                                         _ptr(labels), _ptr(matched), _ptr(ws), _stream()), "seam_rpn_match_f32")
+    return labels, matched
+
+
+def rpn_sample(labels: torch.Tensor, matched: torch.Tensor, keys: torch.Tensor, anchors: torch.Tensor, gt_boxes: torch.Tensor,
+               batch: int = 256, pos_max: int = 128):
+    """BalancedPositiveNegativeSampler [TV] with the key rule of ``roi_sample`` on ``rpn_match``'s outputs: keys [N,A]
+    -> (idx, labels, matched int64 [N,batch] in ascending anchor order, -1 past the count; targets [N,batch,4] =
+    BoxCoder((1,1,1,1)).encode on the foreground rows; count int32 [N,2] = (rows, foreground rows))."""
+    labels, matched = _req(labels, torch.int8, "labels"), _req(matched, torch.int32, "matched")
+    keys, anchors, gt_boxes = _req(keys, name="keys"), _req(anchors, name="anchors"), _req(gt_boxes, name="gt_boxes")
+    n, a = labels.shape
+    g = gt_boxes.shape[1]
+    if tuple(matched.shape) != (n, a) or tuple(keys.shape) != (n, a) or tuple(anchors.shape) != (a, 4) or gt_boxes.shape[0] != n:
+        raise ValueError("rpn_sample: inconsistent shapes")
+    lib = _native.lib()
+    nws = int(lib.seam_rpn_sample_workspace_bytes(n, int(batch)))
+    if nws <= 0 or a > RPN_MAX_ANCHORS:
+        raise ValueError(f"rpn_sample: N = {n}, A = {a}, batch = {batch} outside the kernel's caps")
+    dev = labels.device
+    idx = torch.empty((n, batch), dtype=torch.int64, device=dev)
+    slab, smat = torch.empty_like(idx), torch.empty_like(idx)
+    targets = torch.empty((n, batch, 4), dtype=F32, device=dev)
+    count = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
+    _native.check(lib.seam_rpn_sample_f32(_ptr(labels), _ptr(matched), _ptr(keys), _ptr(anchors), _ptr(gt_boxes), n, a, g, int(batch),
+                                          int(pos_max), _ptr(idx), _ptr(slab), _ptr(smat), _ptr(targets), _ptr(count), _ptr(ws),
+                                          _stream()), "seam_rpn_sample_f32")
+    return idx, slab, smat, targets, count
+
+
+def rpn_gather_patches(feats: Sequence[torch.Tensor], rows: torch.Tensor) -> torch.Tensor:
+    """feats: the NHWC fp32 pyramid maps [N,H_l,W_l,C]; rows int32 [M,4] = (image, level, y, x) -> [M,3,3,C], the 3x3 window of
+    each row's pixel with the conv's zero padding."""
+    feats = [_req(f, name="feats") for f in feats]
+    rows = _req(rows, torch.int32, "rows")
+    n, c = feats[0].shape[0], feats[0].shape[3]
+    if rows.dim() != 2 or rows.shape[1] != 4 or any(f.dim() != 4 or f.shape[0] != n or f.shape[3] != c for f in feats):
+        raise ValueError("rpn_gather_patches: inconsistent shapes")
+    m, l = rows.shape[0], len(feats)
+    out = torch.empty((m, 3, 3, c), dtype=F32, device=rows.device)
+    maps = (C.c_void_p * l)(*[f.data_ptr() for f in feats])
+    hw = (C.c_int * (2 * l))(*[int(v) for f in feats for v in f.shape[1:3]])
+    _native.check(_native.lib().seam_rpn_gather_patches_f32(maps, hw, _ptr(rows), m, n, l, c, _ptr(out), _stream()),
+                  "seam_rpn_gather_patches_f32")
+    return out
+
+
+def rpn_loss_fwd_bwd(head: torch.Tensor, slot: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, num_anchors: int,
+                     grad_cols: int = 32):
+    """RegionProposalNetwork.compute_loss [TV] on the sampled rows: head [M,>=5A], slot int32 [M], labels int64 [M], targets [M,4]
+    -> (loss [2] = (objectness, rpn_box_reg), grad [M,grad_cols]) for a unit upstream gradient."""
+    head, targets = _req(head, name="head"), _req(targets, name="targets")
+    slot, labels = _req(slot, torch.int32, "slot"), _req(labels, torch.int64, "labels")
+    m = head.shape[0]
+    if head.dim() != 2 or slot.numel() != m or labels.numel() != m or tuple(targets.shape) != (m, 4):
+        raise ValueError("rpn_loss_fwd_bwd: inconsistent shapes")
+    loss = torch.empty((2,), dtype=F32, device=head.device)
+    grad = torch.empty((m, int(grad_cols)), dtype=F32, device=head.device)
+    _native.check(_native.lib().seam_rpn_loss_fwd_bwd_f32(_ptr(head), _ptr(slot), _ptr(labels), _ptr(targets), m, int(num_anchors),
+                                                          head.shape[1], int(grad_cols), _ptr(loss), _ptr(grad), _stream()),
+                  "seam_rpn_loss_fwd_bwd_f32")
+    return loss, grad
