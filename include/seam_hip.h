@@ -752,6 +752,45 @@ int seam_rpn_gather_patches_f32(const void* const* maps, const int* hw, const in
 int seam_rpn_loss_fwd_bwd_f32(const float* head, const int* slot, const int64_t* labels, const float* targets, int M, int A,
                               int head_cols, int grad_cols, float* loss, float* grad, seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training the FPN (torchvision FeaturePyramidNetwork under the heads' six losses), csrc/seam_fpn_train.hip: the adjoints of
+ * RoIAlign, of the RPN's 3x3-window gather and of the nearest top-down merge.  The dense convolutions of the FPN backward
+ * run on seam_conv2d_f32 over rotated weights, seam_conv_wgrad_f32 and seam_colsum_f32.  fp32, NHWC.
+ * No float atomics: every output element is summed by one thread in a fixed order, so a launch is bit-identical to the
+ * next, and every entry point writes its outputs completely (zeros where nothing arrives).
+ *
+ * seam_roi_align_bwd_f32: adjoint of seam_roi_align_f32 -- same rois [K,5], levels (or NULL: the forward's LevelMapper, one
+ *   shared device function, so a ROI on a level boundary sends its gradient to the level the forward read), hw, C, scales,
+ *   k_min, P, sampling_ratio; dout NHWC [K,P,P,C] -> the four gradient maps dfeat_l [N,H_l,W_l,C], written completely
+ *   (whole images that own no ROI are zeros; K == 0 writes zeros and needs no rois / dout).  torchvision
+ *   roi_align(aligned=False) backward: samples with a coordinate < -1 or > size contribute nothing, coordinates clamped at
+ *   0, last row / column collapse, ROI extent >= 1, bin average / sr^2.  The sample positions are torchvision's fp32
+ *   operation sequence with no fused multiply-add (the forward kernel fuses one, which can move a position by an ulp).
+ *   A ROI whose image index is outside [0,N) or not finite, or whose given level is outside 0..3, contributes nothing; no
+ *   ROI can cause an access outside the maps (gather form: a workgroup writes only its own 8x8-pixel tile).
+ *   ws: seam_roi_align_bwd_workspace_bytes(N, K) bytes (0 = outside the caps).
+ *   Refused, nothing launched or written: C % 4, C outside 4..4096, P outside 1..32, sampling_ratio outside 1..64, N outside
+ *   1..4096, K outside 0..2^20, a NULL pointer, a map extent <= 0, a map of 2^31 bytes or more.
+ * seam_rpn_scatter_patches_f32: adjoint of seam_rpn_gather_patches_f32 -- dpatch [M,3,3,C], rows int32 [M,4] = (image, level,
+ *   y, x), dmaps / hw HOST arrays as in the gather: dmap_l[n, y+r-1, x+s-1, :] += dpatch[m,r,s,:] for the taps inside the
+ *   map, in row order; the maps are written completely (zeros elsewhere); a row whose image, level or pixel is out of range
+ *   contributes nothing.  Caps and refusals of the gather (M 1..2^20, L 1..8, C 4..4096 % 4, NULL), and N 1..4096.
+ * seam_upsample_add_bwd_f32: adjoint of seam_upsample_add_f32 / seam_conv2d_upres_f32 (one shared index function):
+ *   dtop[n,ht,wt,:] = base[n,ht,wt,:] + sum of dlat[n,h,w,:] over the fine pixels the forward maps to (ht,wt), rows then
+ *   columns ascending; base may be NULL, and may be dtop itself.  dlat [N,H,W,C], dtop / base [N,Ht,Wt,C]; any size ratio.
+ * seam_subsample_add_bwd_f32: adjoint of LastLevelMaxPool (max_pool2d k=1, s=2): d[n,2i,2j,:] += dpool[n,i,j,:] in place;
+ *   d [N,H,W,C], dpool [N,Hp,Wp,C] with Hp = (H-1)/2+1, Wp = (W-1)/2+1 (anything else is refused).
+ * The last two refuse a non-positive extent, C % 4 and a NULL pointer. */
+int64_t seam_roi_align_bwd_workspace_bytes(int N, int K);
+int seam_roi_align_bwd_f32(const float* dout, const float* rois, const int* levels, const int* hw, int C, float scale0,
+                           float scale1, float scale2, float scale3, int k_min, int N, int K, int P, int sampling_ratio,
+                           float* dfeat0, float* dfeat1, float* dfeat2, float* dfeat3, void* ws, seam_stream_t stream);
+int seam_rpn_scatter_patches_f32(const float* dpatch, const int* rows, int M, int N, int L, int C, void* const* dmaps,
+                                 const int* hw, seam_stream_t stream);
+int seam_upsample_add_bwd_f32(const float* dlat, const float* base, float* dtop, int N, int H, int W, int Ht, int Wt, int C,
+                              seam_stream_t stream);
+int seam_subsample_add_bwd_f32(float* d, const float* dpool, int N, int H, int W, int Hp, int Wp, int C, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

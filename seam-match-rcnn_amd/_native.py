@@ -165,6 +165,11 @@ SIGNATURES = {
     "seam_rpn_sample_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "seam_rpn_gather_patches_f32": (_i, [C.POINTER(_p), C.POINTER(_i), _p, _i, _i, _i, _i, _p, _p]),
     "seam_rpn_loss_fwd_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "seam_roi_align_bwd_workspace_bytes": (_i64, [_i, _i]),
+    "seam_roi_align_bwd_f32": (_i, [_p, _p, _p, C.POINTER(_i), _i, _f, _f, _f, _f, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "seam_rpn_scatter_patches_f32": (_i, [_p, _p, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), _p]),
+    "seam_upsample_add_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_subsample_add_bwd_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -154,7 +154,7 @@ class WeightedCE2Function(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------- RoI heads training
-# (ref models/matchrcnn.py:333-472).  Gradients stop at the RoIAlign outputs: the feature maps are constants here.
+# (ref models/matchrcnn.py:333-472).  Each head returns an input gradient only when its input carries a tape (a trainable FPN).
 
 def _pad_rows(w: torch.Tensor, rows: int) -> torch.Tensor:
     """[K,...] -> [rows,...] with zero rows appended (pack_conv_dgrad needs Cout % 32 == 0)."""
@@ -178,10 +178,20 @@ def _up32(k: int) -> int:
     return (k + 31) // 32 * 32
 
 
+def _full_dgrad_1x1(dy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Input gradient of a VALID RxS conv whose output is 1x1 (fc6 over its 7x7 tile, the RPN conv over a 3x3 window):
+    dy [M,K], w OIHW [K,C,R,S] -> dx NHWC [M,R,S,C] = dy @ W with W[k, (r,s,c)] -- the full transposed conv has one tap per
+    output pixel, so it is one GEMM and the result lands in NHWC order."""
+    k, c, r, s = w.shape
+    wt = w.detach().permute(2, 3, 1, 0).reshape(r * s * c, k).contiguous()
+    return ops.linear(dy.contiguous(), ops.pack_conv(wt, None)).view(dy.shape[0], r, s, c)
+
+
 class BoxHeadFunction(torch.autograd.Function):
     """TwoMLPHead + FastRCNNPredictor (ref torchvision roi_heads box branch): x NHWC [R,7,7,256] ->
     (class_logits [R,ncls], box_regression [R,4*ncls]).  fc6 is the 7x7 valid conv over the tile; fc7 and the fused
-    ncls + 4*ncls predictor rows are 1x1 convs.  No input gradient (RoIAlign has no backward here)."""
+    ncls + 4*ncls predictor rows are 1x1 convs.  The input gradient (asked for when the RoIAlign output carries a tape) is the
+    full 7x7 transposed conv of the 1x1 gradient, i.e. one GEMM [R,1024] x [1024, 7*7*256] straight into the NHWC tile."""
 
     @staticmethod
     def forward(ctx, x, w6, b6, w7, b7, wc, bc, wb, bb):
@@ -216,14 +226,17 @@ class BoxHeadFunction(torch.autograd.Function):
         dh6 = ops.conv2d(dh7, ops.pack_conv_dgrad(w7, wino=False), relu=2, residual=h6)
         dw6 = ops.conv_wgrad(x, dh6, 7, 7).view(w6c.shape[0], -1)
         db6 = ops.colsum(dh6)
-        return None, dw6, db6, dw7, db7, dwp[:ncls], dbp[:ncls], dwp[ncls:], dbp[ncls:]
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _full_dgrad_1x1(dh6.view(r, -1), w6c)
+        return dx, dw6, db6, dw7, db7, dwp[:ncls], dbp[:ncls], dwp[ncls:], dbp[ncls:]
 
 
 class MaskHeadFunction(torch.autograd.Function):
     """MaskRCNNHeads (4 x conv3x3 pad 1 + ReLU) + MaskRCNNPredictor: x NHWC [P,14,14,256] -> logits in the sub-pixel
     layout [P,14,14,4*ncls] (detection.MaskRCNNPredictor.forward).  conv5_mask (ConvTranspose2d 2x2/s2) is the 1x1 conv
     to the 4 sub-pixel groups (a,b) (channel (a*2+b)*256+co), so its backward is a 1x1 dgrad + wgrad with no shuffle.
-    No input gradient."""
+    The input gradient (asked for when the RoIAlign output carries a tape) is one more 3x3 dgrad."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w3, b3, w4, b4, wt, bt, wl, bl):
@@ -265,7 +278,10 @@ class MaskHeadFunction(torch.autograd.Function):
             dbs[l] = ops.colsum(dy)
             if l > 0:
                 dy = ops.conv2d(dy, ops.pack_conv_dgrad(weights[l], pad_fwd=1, wino=False), relu=2, residual=acts[l])
-        return (None, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dws[3], dbs[3], dwt, dbt, dwl, dbl)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.conv2d(dy, ops.pack_conv_dgrad(weights[0], pad_fwd=1, wino=False))
+        return (dx, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dws[3], dbs[3], dwt, dbt, dwl, dbl)
 
 
 class FastRCNNLossFunction(torch.autograd.Function):
@@ -300,12 +316,13 @@ class MaskLossFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------- RPN training
-# d loss / d head output is zero outside the sampled (pixel, anchor) slots and the feature maps are constants, so the
-# gradient of the 3x3 conv and of the two 1x1 predictors is exactly a sum over the sampled rows: no dense backward conv.
+# d loss / d head output is zero outside the sampled (pixel, anchor) slots, so the gradient of the 3x3 conv and of the two
+# 1x1 predictors is exactly a sum over the sampled rows: no dense backward conv.
 
 class RPNHeadRowsFunction(torch.autograd.Function):
     """RPNHead at M sampled pixels: patches NHWC [M,3,3,256] (the conv's 3x3 input windows, zero padding included; slots
-    that share a pixel are separate rows) -> [M, A + 4A] (objectness logits | deltas).  No input gradient."""
+    that share a pixel are separate rows) -> [M, A + 4A] (objectness logits | deltas).  The input gradient (asked for when the
+    windows carry a tape, ``RPNPatchesFunction``) is the full 3x3 transposed conv of the [M,1,1,256] gradient: one GEMM."""
 
     @staticmethod
     def forward(ctx, patches, w, b, wc, bc, wb, bb):
@@ -314,13 +331,13 @@ class RPNHeadRowsFunction(torch.autograd.Function):
         t = ops.conv2d(x, ops.pack_conv(w, b, pad=0, wino=False), relu=True)                    # [M,1,1,256]
         wp = torch.cat([wc.detach().reshape(wc.shape[0], -1), wb.detach().reshape(wb.shape[0], -1)], 0)
         o = ops.linear(t.view(m, -1), ops.pack_conv(wp, torch.cat([bc.detach(), bb.detach()], 0)), out_f32=True)
-        ctx.save_for_backward(x, t, wp)
+        ctx.save_for_backward(x, t, wp, w.detach())
         ctx.shapes = (wc.shape, wb.shape)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        x, t, wp = ctx.saved_tensors
+        x, t, wp, w = ctx.saved_tensors
         m, k = x.shape[0], wp.shape[0]
         kp = _up32(k)
         do = _pad_cols(do.to(F32), kp).view(m, 1, 1, kp)
@@ -330,7 +347,8 @@ class RPNHeadRowsFunction(torch.autograd.Function):
         dw = ops.conv_wgrad(x, dt, 3, 3)
         db = ops.colsum(dt)
         a = ctx.shapes[0][0]
-        return (None, dw, db, dwp[:a].reshape(ctx.shapes[0]), dbp[:a], dwp[a:].reshape(ctx.shapes[1]), dbp[a:])
+        dx = _full_dgrad_1x1(dt.view(m, -1), w) if ctx.needs_input_grad[0] else None
+        return (dx, dw, db, dwp[:a].reshape(ctx.shapes[0]), dbp[:a], dwp[a:].reshape(ctx.shapes[1]), dbp[a:])
 
 
 class RPNLossFunction(torch.autograd.Function):
@@ -350,3 +368,120 @@ class RPNLossFunction(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         scale = torch.cat([g_obj.expand(ctx.a), g_box.expand(grad.shape[1] - ctx.a)])
         return (grad * scale)[:, :ctx.k], None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------- FPN training
+# The adjoints of csrc/seam_fpn_train.hip behind torch's tape: RoIAlign, the RPN's window gather, and the pyramid itself.
+# Every gradient is summed in a fixed order (no float atomics), so two identical steps give the same bits.
+
+class RoIAlignFunction(torch.autograd.Function):
+    """MultiScaleRoIAlign on four NHWC maps [N,H_l,W_l,C] -> [K,P,P,C]; backward = ``ops.roi_align_bwd`` (the maps'
+    gradients are written completely; the ROIs are constants)."""
+
+    @staticmethod
+    def forward(ctx, rois, scales, pooled, sampling_ratio, k_min, f0, f1, f2, f3):
+        feats = [f.detach() for f in (f0, f1, f2, f3)]
+        rois = rois.detach().contiguous()
+        ctx.save_for_backward(rois)
+        ctx.geom = ([tuple(f.shape[1:3]) for f in feats], feats[0].shape[0], tuple(scales), sampling_ratio, k_min)
+        return ops.roi_align(feats, rois, scales, pooled, sampling_ratio, k_min)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (rois,) = ctx.saved_tensors
+        hws, n, scales, sr, k_min = ctx.geom
+        d = ops.roi_align_bwd(dout.contiguous().to(F32), rois, hws, n, scales, sr, k_min)
+        return (None, None, None, None, None, *d)
+
+
+class RPNPatchesFunction(torch.autograd.Function):
+    """``ops.rpn_gather_patches`` over the pyramid maps; backward = ``ops.rpn_scatter_patches`` (rows in row order)."""
+
+    @staticmethod
+    def forward(ctx, rows, *maps):
+        maps = [m.detach() for m in maps]
+        ctx.save_for_backward(rows)
+        ctx.geom = ([tuple(m.shape[1:3]) for m in maps], maps[0].shape[0])
+        return ops.rpn_gather_patches(maps, rows)
+
+    @staticmethod
+    def backward(ctx, dpatch):
+        (rows,) = ctx.saved_tensors
+        hws, n = ctx.geom
+        return (None, *ops.rpn_scatter_patches(dpatch.contiguous().to(F32), rows, hws, n))
+
+
+class GatherRowsFunction(torch.autograd.Function):
+    """``x[idx]`` for a HOST index array that may hold duplicates (``filter_proposals`` can keep a ROI once per GT box).  The
+    backward adds the j-th occurrence of every index in round j -- inside a round the indices are unique -- so the sum has a
+    fixed order whatever the device's index_put does with duplicates."""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        import numpy as np
+        idx = np.asarray(idx, np.int64)
+        order = np.argsort(idx, kind="stable")
+        srt = idx[order]
+        first = np.r_[True, srt[1:] != srt[:-1]] if len(srt) else np.zeros(0, bool)
+        start = np.maximum.accumulate(np.where(first, np.arange(len(srt)), 0)) if len(srt) else np.zeros(0, np.int64)
+        occ = np.arange(len(srt)) - start                        # 0 for the first occurrence of an index, 1 for the second ...
+        dev = x.device
+        ctx.rounds = [(torch.from_numpy(srt[occ == j]).to(dev), torch.from_numpy(order[occ == j]).to(dev))
+                      for j in range(int(occ.max()) + 1 if len(occ) else 0)]
+        ctx.shape = x.shape
+        return x.detach()[torch.from_numpy(idx).to(dev)]
+
+    @staticmethod
+    def backward(ctx, g):
+        dx = torch.zeros(ctx.shape, dtype=g.dtype, device=g.device)
+        for rows, pos in ctx.rounds:
+            dx[rows] += g[pos]
+        return dx, None
+
+
+class FPNFunction(torch.autograd.Function):
+    """FeaturePyramidNetwork + LastLevelMaxPool on NHWC maps: (C2..C5, the sixteen parameters) -> (P2..P5, pool).
+
+    forward: the launches of ``FeaturePyramidNetwork.forward`` in its single-stream form on the module's packed weights (the
+    same bits), keeping the four merged inner maps.  backward, finest level first (an inner map's gradient needs the finer
+    level's): the pool adjoint into P5's gradient, then per level colsum + conv_wgrad of the 3x3 output conv, its dgrad
+    (exact fp32), ``upsample_add_bwd`` of the finer inner gradient with that dgrad as its base, conv_wgrad + colsum of the
+    lateral 1x1, and -- only when a C map asks for it -- the 1x1 dgrad."""
+
+    @staticmethod
+    def forward(ctx, packed, c2, c3, c4, c5, *params):
+        inner, layer = packed
+        feats = [f.detach() for f in (c2, c3, c4, c5)]
+        last = ops.conv2d(feats[3], inner[3])
+        inners = [None, None, None, last]
+        outs = [None, None, None, ops.conv2d(last, layer[3])]
+        for i in (2, 1, 0):
+            last = ops.conv2d_topdown(feats[i], inner[i], last)
+            inners[i] = last
+            outs[i] = ops.conv2d(last, layer[i])
+        pool = ops.maxpool2d(outs[3], 1, 2, 0)
+        ctx.save_for_backward(*feats, *inners, *(params[2 * i].detach() for i in range(8)))
+        return (*outs, pool)
+
+    @staticmethod
+    def backward(ctx, g0, g1, g2, g3, gpool):
+        saved = ctx.saved_tensors
+        feats, inners, iw, lw = saved[0:4], saved[4:8], saved[8:12], saved[12:16]
+        gs = [g0, g1, g2, g3]
+        for i in range(4):
+            gs[i] = (torch.zeros_like(inners[i]) if gs[i] is None else gs[i].contiguous().to(F32))
+        if gpool is not None:
+            gs[3] = ops.subsample_add_bwd_(gs[3].clone(), gpool.contiguous().to(F32))
+        d_in = [None] * 4            # gradients of the merged inner maps
+        diw, dib, dlw, dlb, dfeat = [None] * 4, [None] * 4, [None] * 4, [None] * 4, [None] * 4
+        for i in range(4):
+            dlw[i] = ops.conv_wgrad_chunked(inners[i], gs[i], 3, 3, 1, 1)
+            dlb[i] = ops.colsum(gs[i])
+            own = ops.conv2d(gs[i], ops.pack_conv_dgrad(lw[i], pad_fwd=1))
+            d_in[i] = own if i == 0 else ops.upsample_add_bwd(d_in[i - 1], own.shape[1:3], base=own)
+            diw[i] = ops.conv_wgrad_chunked(feats[i], d_in[i], 1, 1)
+            dib[i] = ops.colsum(d_in[i])
+            if ctx.needs_input_grad[1 + i]:
+                dfeat[i] = ops.conv2d(d_in[i], ops.pack_conv_dgrad(iw[i]))
+        grads = [t for i in range(4) for t in (diw[i], dib[i])] + [t for i in range(4) for t in (dlw[i], dlb[i])]
+        return (None, *dfeat, *grads)

@@ -31,6 +31,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "seam_fastdiv.h"
+#include "seam_fpn_common.h"
 #include "seam_opts.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -443,8 +444,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm(const Con
                         const int m = cm0 + wm0 + i * 32 + k * RPI + er;
                         int nl, ho, wo;
                         split_row(p, HoWo, m - up_first * HoWo, nl, ho, wo);
-                        const int ht = min((int)floorf((float)ho * shs), p.rH - 1);
-                        const int wt = min((int)floorf((float)wo * sws), p.rW - 1);
+                        const int ht = seam_fpn::nearest_src(ho, shs, p.rH);
+                        const int wt = seam_fpn::nearest_src(wo, sws, p.rW);
                         const unsigned uo = (nok && m < p.M) ? (unsigned)(((nl * p.rH + ht) * p.rW + wt) * p.K + n) * 4u : kOob;
                         rv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, uo, 0, 0));
                     }

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "seam_fastdiv.h"
+#include "seam_fpn_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -276,10 +277,8 @@ __global__ void upsample_add_kernel(T* __restrict__ lat, const T* __restrict__ t
         r /= W;
         const int h = (int)(r % H);
         const int n = (int)(r / H);
-        int ht = (int)floorf((float)h * sh);
-        int wt = (int)floorf((float)w * sw);
-        if (ht > Ht - 1) ht = Ht - 1;
-        if (wt > Wt - 1) wt = Wt - 1;
+        const int ht = seam_fpn::nearest_src(h, sh, Ht);       // one index rule for the merge and its adjoint
+        const int wt = seam_fpn::nearest_src(w, sw, Wt);
         V a = *reinterpret_cast<V*>(lat + i * E);
         const V b = *reinterpret_cast<const V*>(top + (((size_t)n * Ht + ht) * Wt + wt) * C + c * E);
 #pragma unroll

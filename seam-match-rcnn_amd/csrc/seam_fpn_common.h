@@ -1,0 +1,23 @@
+// Device helpers shared by a forward kernel and its adjoint (seam_roialign.hip, seam_elementwise.hip, seam_conv.hip, seam_pw.hip,
+// seam_pwh.hip, seam_fpn_train.hip): a gradient must go to the level / pixel the forward read, so both sides call ONE function.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace seam_fpn {
+
+// LevelMapper: floor(4 + log2(sqrt(area)/224) + 1e-6), clamped to [k_min, k_min+3], every step an fp32 operation rounded
+// correctly (the host's torch.log2 and the oracle): log2 in fp64, rounded once -- the fast log2f is an ulp off at some
+// sizes within a few ulps of 112 / 224 / 448 * 2^-1e-6 and moved those boxes one level down
+__device__ __forceinline__ int map_level(float x1, float y1, float x2, float y2, int k_min) {
+    const float s = sqrtf((x2 - x1) * (y2 - y1));
+    float l = floorf(4.f + (float)log2((double)(s / 224.f)) + 1e-6f);
+    l = fminf(fmaxf(l, (float)k_min), (float)(k_min + 3));
+    return (int)l - k_min;
+}
+
+// ATen upsample_nearest: source index of destination index `dst`, scale = (float)in / (float)out
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
+    return min((int)floorf((float)dst * scale), in_size - 1);
+}
+
+}  // namespace seam_fpn

@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_fastdiv.h"
+#include "seam_fpn_common.h"
 #include "seam_opts.h"
 #include <type_traits>
 
@@ -226,8 +227,8 @@ __global__ __launch_bounds__(64 * PW_WAVES, 1) void pw_sw_kernel(const PwArgs p)
                     const int rm = rl - nl * HoWo;
                     const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);     // rm < Ho*Wo, Wo >= 2: exact by seam_conv1x1_sw_f32's check
                     const int wo = rm - ho * p.Wo;
-                    const int ht = min((int)floorf((float)ho * fh), p.rH - 1);
-                    const int wt = min((int)floorf((float)wo * fw), p.rW - 1);
+                    const int ht = seam_fpn::nearest_src(ho, fh, p.rH);
+                    const int wt = seam_fpn::nearest_src(wo, fw, p.rW);
                     uo[ih][q] = (unsigned)((((img0 + nl) * p.rH + ht) * p.rW + wt) * p.K + n0 + (lane & 7) * 4) * 4u;
                 }
         }

@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "seam_fastdiv.h"
+#include "seam_fpn_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -218,8 +219,8 @@ __global__ __launch_bounds__(64 * PWH_WAVES, 1) void pw_swh_kernel(const PwhArgs
                 const int rm = rl - nl * HoWo;
                 const int ho = (int)__umulhi((unsigned)rm, p.m_Wo);         // rm < Ho*Wo, Wo >= 2: exact by seam_conv1x1_swh_f16's check
                 const int wo = rm - ho * p.Wo;
-                const int ht = min((int)floorf((float)ho * fh), p.rH - 1);
-                const int wt = min((int)floorf((float)wo * fw), p.rW - 1);
+                const int ht = seam_fpn::nearest_src(ho, fh, p.rH);
+                const int wt = seam_fpn::nearest_src(wo, fw, p.rW);
                 uo[ih] = (unsigned)((((img0 + nl) * p.rH + ht) * p.rW + wt) * p.K + n0 + (lane & 3) * 8) * 2u;
             }
         }

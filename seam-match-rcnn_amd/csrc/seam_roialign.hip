@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_opts.h"
+#include "seam_fpn_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -37,15 +38,7 @@ struct RoiArgs {
     int K, P, sr;
 };
 
-__device__ __forceinline__ int map_level(float x1, float y1, float x2, float y2, int k_min) {
-    // LevelMapper: floor(4 + log2(sqrt(area)/224) + 1e-6), clamped to [k_min, k_min+3], every step an fp32 operation rounded
-    // correctly (the host's torch.log2 and the oracle): log2 in fp64, rounded once -- the fast log2f is an ulp off at some
-    // sizes within a few ulps of 112 / 224 / 448 * 2^-1e-6 and moved those boxes one level down
-    const float s = sqrtf((x2 - x1) * (y2 - y1));
-    float l = floorf(4.f + (float)log2((double)(s / 224.f)) + 1e-6f);
-    l = fminf(fmaxf(l, (float)k_min), (float)(k_min + 3));
-    return (int)l - k_min;
-}
+using seam_fpn::map_level;      // shared with the adjoint (seam_fpn_train.hip): one LevelMapper for both
 
 // one bilinear sample, fixed operation order (both kernels): acc + (((w1 v1) + w2 v2) + w3 v3) + w4 v4, each "+ w v" one fma
 __device__ __forceinline__ f32x4 sample_acc(f32x4 acc, float w1, f32x4 v1, float w2, f32x4 v2, float w3, f32x4 v3, float w4, f32x4 v4) {

@@ -342,6 +342,16 @@ class FeaturePyramidNetwork(nn.Module):
         od["pool"] = pool
         return od
 
+    def forward_taped(self, feats: List[torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
+        """The same five maps (the same bits) with a tape into the sixteen parameters and into ``feats``
+        (``autograd.FPNFunction``): what ``MatchRCNN.forward`` runs in training mode when an FPN parameter can learn.  fp32."""
+        from ..autograd import FPNFunction
+        if cdt(self) != torch.float32 or any(f.dtype != torch.float32 for f in feats):
+            raise NotImplementedError("the training branch of the FPN is fp32 only: call set_compute_dtype(torch.float32)")
+        params = [t for blocks in (self.inner_blocks, self.layer_blocks) for m in blocks for t in (m.weight, m.bias)]
+        outs = FPNFunction.apply(self.packed(), *feats, *params)
+        return OrderedDict(zip(("0", "1", "2", "3", "pool"), outs))
+
 
 class BackboneWithFPN(nn.Module):
     def __init__(self):
@@ -586,7 +596,7 @@ class RegionProposalNetwork(nn.Module):
 
     def training_losses(self, feats, padded_hw, targets):
         """assign_targets_to_anchors + compute_loss [TV] -> {"loss_objectness", "loss_rpn_box_reg"} (0-d fp32, with a tape into
-        ``head``'s six parameters; the feature maps are constants).
+        ``head``'s six parameters, and into the feature maps when one of them requires a gradient).
 
         Matcher(fg_iou_thresh, bg_iou_thresh, allow_low_quality_matches=True) on all anchors of an image in the order of
         ``grid_anchors`` (level, y, x, anchor), then BalancedPositiveNegativeSampler with the key rule of
@@ -594,7 +604,7 @@ class RegionProposalNetwork(nn.Module):
         smallest (key, index) are kept -- torchvision's distribution, not its ``randperm`` draw.  The head is re-evaluated on the
         3x3 windows of the sampled pixels only (``autograd.RPNHeadRowsFunction``) and the losses are computed on those rows, so
         the loss value is exactly the function that is differentiated.  One device->host copy (the sampled anchors)."""
-        from ..autograd import RPNHeadRowsFunction, RPNLossFunction
+        from ..autograd import RPNHeadRowsFunction, RPNLossFunction, RPNPatchesFunction
         fl = list(feats.values())
         n, dev = fl[0].shape[0], fl[0].device
         if len(targets) != n:
@@ -628,7 +638,10 @@ class RegionProposalNetwork(nn.Module):
         wl = np.asarray([w for _, w in hws], np.int64)[lvl]
         meta = np.stack([img, lvl, pix // wl, pix % wl, slot], 1).astype(np.int32)
         meta = torch.from_numpy(meta).to(dev)
-        patches = ops.rpn_gather_patches(fl, meta[:, :4].contiguous())
+        if torch.is_grad_enabled() and any(f.requires_grad for f in fl):       # a trainable FPN: the windows carry the tape
+            patches = RPNPatchesFunction.apply(meta[:, :4].contiguous(), *fl)
+        else:
+            patches = ops.rpn_gather_patches(fl, meta[:, :4].contiguous())
         h = self.head
         o = RPNHeadRowsFunction.apply(patches, h.conv.weight, h.conv.bias, h.cls_logits.weight, h.cls_logits.bias,
                                       h.bbox_pred.weight, h.bbox_pred.bias)
@@ -700,6 +713,9 @@ class MultiScaleRoIAlign(nn.Module):
         rois = torch.cat([self._idx, allb.view(-1, 4)], 1).contiguous()
         scales = self.infer_scales([f.shape[1:3] for f in fl], image_sizes)
         k_min = int(round(-math.log2(scales[0])))
+        if torch.is_grad_enabled() and any(f.requires_grad for f in fl):       # a trainable FPN: the maps receive a gradient
+            from ..autograd import RoIAlignFunction
+            return RoIAlignFunction.apply(rois, tuple(scales), self.output_size, self.sampling_ratio, k_min, *fl)
         return ops.roi_align(fl, rois, scales, self.output_size, self.sampling_ratio, k_min)
 
 

@@ -11,10 +11,11 @@ identical, so the 14x14 ROI features are computed once here.
 
 Training branch of the heads (``NewRoIHeads.forward`` with ``self.training``)    ref :333-472
 -> ``([], {loss_classifier, loss_box_reg, loss_mask, loss_match})``; backward fills the gradients
-of the box, mask and match heads (the features are constants: no RoIAlign backward).
+of the box, mask and match heads, and of the feature maps when they carry a tape (``autograd.RoIAlignFunction``).
 
 ``MatchRCNN.forward(images, targets)`` in training mode adds the RPN's two losses (``detection.RegionProposalNetwork``)
-and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43), backbone frozen.
+and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43).  ``backbone.body`` is
+frozen; ``backbone.fpn`` learns from all six losses when its parameters require a gradient (``autograd.FPNFunction``).
 """
 from __future__ import annotations
 
@@ -23,7 +24,8 @@ import torch
 from torch.nn.utils.rnn import pad_sequence
 
 from .. import ops
-from ..autograd import BoxHeadFunction, FastRCNNLossFunction, MaskHeadFunction, MaskLossFunction, WeightedCE2Function
+from ..autograd import (BoxHeadFunction, FastRCNNLossFunction, GatherRowsFunction, MaskHeadFunction, MaskLossFunction,
+                        WeightedCE2Function)
 from . import detection as det
 from .match_head import MatchPredictor
 from .video_matchrcnn import TemporalRoIHeads, VideoMatchRCNN, model_urls  # noqa: F401
@@ -202,7 +204,10 @@ class NewRoIHeads(TemporalRoIHeads):
             pairs.append(_host(targets[i]["pair_ids"]).reshape(-1)[mi])
             styles.append(_host(targets[i]["styles"]).reshape(-1)[mi])
         keep, types = np.concatenate(keep), np.concatenate(types)
-        feats = mask_roi[torch.from_numpy(keep).to(dev)]
+        if mask_roi.requires_grad:          # `keep` can hold duplicates: their gradients are added in a fixed order
+            feats = GatherRowsFunction.apply(mask_roi, keep)
+        else:
+            feats = mask_roi[torch.from_numpy(keep).to(dev)]
         _, match_logits = self.match_predictor(feats.permute(0, 3, 1, 2), torch.from_numpy(types).to(torch.int32))
         gts = match_targets(np.concatenate(pairs), np.concatenate(styles), types)
         if gts.size == 0:           # no street or no shop ROI: mean over zero pairs, NaN as in the reference
@@ -226,21 +231,31 @@ class MatchRCNN(VideoMatchRCNN):
     def forward(self, images, targets=None):
         """Eval: the detections (``VideoMatchRCNN.forward``).  Training mode with ``targets``: the reference's loss dict
         (ref stuffs/engine.py:40-43) -- loss_classifier, loss_box_reg, loss_mask, loss_match from the RoI heads and
-        loss_objectness, loss_rpn_box_reg from the RPN.  ``backward()`` reaches ``rpn.head`` and the RoI heads; the feature
-        maps are computed without a tape, so every backbone parameter must be frozen (``requires_grad_(False)``)."""
+        loss_objectness, loss_rpn_box_reg from the RPN.  ``backward()`` reaches ``rpn.head``, the RoI heads and -- when one of
+        its parameters requires a gradient -- the sixteen parameters of ``backbone.fpn`` (through RoIAlign, the RPN's windows
+        and the top-down merges).  The ResNet body is computed without a tape, so every parameter of ``backbone.body`` must be
+        frozen (``requires_grad_(False)``).  With the whole backbone frozen nothing is taped and the launches are unchanged."""
         if not self.training or targets is None:
             return super().forward(images, targets)
-        if any(p.requires_grad for p in self.backbone.parameters()):
+        if any(p.requires_grad for p in self.backbone.body.parameters()):
             raise NotImplementedError(
-                "MatchRCNN training: the FPN / ResNet backward is not built, so the backbone cannot learn; freeze it with "
-                "`for p in model.backbone.parameters(): p.requires_grad_(False)` (a silent partial gradient would be worse)")
+                "MatchRCNN training: the ResNet body backward of the backbone is not built, so backbone.body cannot learn; "
+                "freeze it with `for p in model.backbone.body.parameters(): p.requires_grad_(False)` (backbone.fpn may stay "
+                "trainable; a silent partial gradient would be worse)")
+        fpn_learns = any(p.requires_grad for p in self.backbone.fpn.parameters())
         if any(det.cdt(m) != torch.float32 for m in (self, self.backbone, self.rpn, self.roi_heads)):
             raise NotImplementedError("MatchRCNN training is fp32 only: call set_compute_dtype(torch.float32)")
         images = list(images)
         if len(images) != len(targets):
             raise ValueError("one target dict per image is needed")
-        with torch.no_grad():
-            feats, sizes, orig, padded = self.extract_features([i.detach() for i in images])
+        if fpn_learns:                      # body without a tape, the pyramid through FPNFunction
+            with torch.no_grad():
+                x, sizes, orig, padded = self.transform([i.detach() for i in images])
+                c = self.backbone.body(x)            # fp32: never the padded space-to-depth frame of the fp16 path
+            feats = self.backbone.fpn.forward_taped(c)
+        else:
+            with torch.no_grad():
+                feats, sizes, orig, padded = self.extract_features([i.detach() for i in images])
         dev = feats["0"].device
         tg = []
         for t, s, o in zip(targets, sizes, orig):         # GeneralizedRCNNTransform.resize of the targets [TV]

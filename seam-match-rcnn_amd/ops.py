@@ -312,6 +312,32 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 
     return dw
 
 
+# seam_conv_wgrad_f32 indexes an operand with 32 bits: one of 2^31 bytes or more is split over images (FPN level 0 at
+# 800x1333 passes that at 32 images).  A module constant so that a test can lower it.
+WGRAD_MAX_OPERAND_BYTES = (1 << 31) - 1
+
+
+def conv_wgrad_chunked(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0) -> torch.Tensor:
+    """``conv_wgrad`` for operands of any size: the images are split into equal consecutive chunks (the last may be shorter) whose
+    operands stay within ``WGRAD_MAX_OPERAND_BYTES``, and the partial dW are added in chunk order -- a fixed order, so two calls
+    give the same bits.  One chunk is exactly ``conv_wgrad``."""
+    x, dy = _req(x, name="x"), _req(dy, name="dy")
+    n = x.shape[0]
+    if dy.shape[0] != n or n == 0:
+        raise ValueError("conv_wgrad_chunked: x and dy need the same, non-zero number of images")
+    per = max(x[0].numel(), dy[0].numel()) * 4
+    if per > WGRAD_MAX_OPERAND_BYTES:
+        raise ValueError(f"conv_wgrad_chunked: one image's operand ({per} bytes) exceeds the limit of {WGRAD_MAX_OPERAND_BYTES}")
+    step = max(1, min(n, WGRAD_MAX_OPERAND_BYTES // per))
+    if step >= n:
+        return conv_wgrad(x, dy, R, S, stride, pad)
+    dw = None
+    for i in range(0, n, step):
+        part = conv_wgrad(x[i:i + step], dy[i:i + step], R, S, stride, pad)
+        dw = part if dw is None else dw.add_(part)
+    return dw
+
+
 def colsum(x: torch.Tensor) -> torch.Tensor:
     """[..., K] -> [K] sum over all leading dims (bias gradients)."""
     x = _req(x)
@@ -1416,3 +1442,85 @@ def rpn_loss_fwd_bwd(head: torch.Tensor, slot: torch.Tensor, labels: torch.Tenso
                                                           head.shape[1], int(grad_cols), _ptr(loss), _ptr(grad), _stream()),
                   "seam_rpn_loss_fwd_bwd_f32")
     return loss, grad
+
+
+# ------------------------------------------------------------------------------ FPN training: the adjoints (csrc/seam_fpn_train.hip)
+def roi_align_bwd(dout: torch.Tensor, rois: torch.Tensor, feat_hws: Sequence[Sequence[int]], n_images: int, scales: Sequence[float],
+                  sampling_ratio: int = 2, k_min: int = 2, levels: Optional[torch.Tensor] = None) -> list:
+    """Adjoint of ``roi_align``: dout NHWC fp32 [K,P,P,C], rois fp32 [K,5], feat_hws the four (H_l, W_l) -> the four gradient
+    maps [N,H_l,W_l,C], written completely (zeros where no ROI reaches).  Fixed summation order: two calls give the same bits."""
+    dout, rois = _req(dout, name="dout"), _req(rois, name="rois")
+    if dout.dim() != 4 or dout.shape[1] != dout.shape[2] or rois.dim() != 2 or rois.shape[1] != 5 or rois.shape[0] != dout.shape[0]:
+        raise ValueError("roi_align_bwd: dout must be [K,P,P,C] and rois [K,5]")
+    if len(feat_hws) != 4 or len(scales) != 4:
+        raise ValueError("roi_align_bwd: four levels are needed")
+    k, p, c = dout.shape[0], dout.shape[1], dout.shape[3]
+    n = int(n_images)
+    if levels is not None:
+        levels = _req(levels, torch.int32, "levels")
+        if levels.numel() != k:
+            raise ValueError("roi_align_bwd: one level per ROI is needed")
+    lib = _native.lib()
+    hws = [(int(h), int(w)) for h, w in feat_hws]
+    nws = int(lib.seam_roi_align_bwd_workspace_bytes(n, k))
+    if nws <= 0:
+        raise ValueError(f"roi_align_bwd: {n} images / {k} ROIs are outside the kernel's caps")
+    outs = [torch.empty((n, h, w, c), dtype=F32, device=dout.device) for h, w in hws]
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dout.device)
+    hw = (C.c_int * 8)(*[d for s in hws for d in s])
+    _native.check(lib.seam_roi_align_bwd_f32(_ptr(dout) if k else None, _ptr(rois) if k else None, _ptr(levels), hw, c,
+                                             scales[0], scales[1], scales[2], scales[3], k_min, n, k, p, int(sampling_ratio),
+                                             _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(ws), _stream()),
+                  "seam_roi_align_bwd_f32")
+    return outs
+
+
+def rpn_scatter_patches(dpatch: torch.Tensor, rows: torch.Tensor, feat_hws: Sequence[Sequence[int]], n_images: int) -> list:
+    """Adjoint of ``rpn_gather_patches``: dpatch fp32 [M,3,3,C], rows int32 [M,4] = (image, level, y, x), feat_hws the (H_l, W_l)
+    of the levels -> the gradient maps [N,H_l,W_l,C] (zeros where no window reaches).  Rows are added in row order."""
+    dpatch = _req(dpatch, name="dpatch")
+    rows = _req(rows, torch.int32, "rows")
+    if dpatch.dim() != 4 or tuple(dpatch.shape[1:3]) != (3, 3) or rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] != dpatch.shape[0]:
+        raise ValueError("rpn_scatter_patches: inconsistent shapes")
+    m, c, n, l = dpatch.shape[0], dpatch.shape[3], int(n_images), len(feat_hws)
+    hws = [(int(h), int(w)) for h, w in feat_hws]
+    if m == 0:
+        return [torch.zeros((n, h, w, c), dtype=F32, device=dpatch.device) for h, w in hws]
+    outs = [torch.empty((n, h, w, c), dtype=F32, device=dpatch.device) for h, w in hws]
+    maps = (C.c_void_p * l)(*[o.data_ptr() for o in outs])
+    hw = (C.c_int * (2 * l))(*[d for s in hws for d in s])
+    _native.check(_native.lib().seam_rpn_scatter_patches_f32(_ptr(dpatch), _ptr(rows), m, n, l, c, maps, hw, _stream()),
+                  "seam_rpn_scatter_patches_f32")
+    return outs
+
+
+def upsample_add_bwd(dlat: torch.Tensor, top_hw: Sequence[int], base: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of the nearest top-down merge (``upsample_add_`` / ``conv2d_topdown``): dlat [N,H,W,C] -> [N,Ht,Wt,C], each
+    coarse pixel the sum of the fine pixels the forward mapped to it, plus ``base`` [N,Ht,Wt,C] when given."""
+    dlat = _req(dlat, name="dlat")
+    n, h, w, c = dlat.shape
+    ht, wt = int(top_hw[0]), int(top_hw[1])
+    if base is not None:
+        base = _req(base, name="base")
+        if tuple(base.shape) != (n, ht, wt, c):
+            raise ValueError("upsample_add_bwd: base must be [N,Ht,Wt,C]")
+    out = torch.empty((n, ht, wt, c), dtype=F32, device=dlat.device)
+    _native.check(_native.lib().seam_upsample_add_bwd_f32(_ptr(dlat), _ptr(base), _ptr(out), n, h, w, ht, wt, c, _stream()),
+                  "seam_upsample_add_bwd_f32")
+    return out
+
+
+def subsample_add_bwd_(d: torch.Tensor, dpool: torch.Tensor) -> torch.Tensor:
+    """Adjoint of LastLevelMaxPool (k=1, s=2), in place: d[n,2i,2j,:] += dpool[n,i,j,:]; returns d."""
+    if not d.is_contiguous():
+        raise ValueError("subsample_add_bwd_: d is updated in place and must be contiguous")
+    d, dpool = _req(d, name="d"), _req(dpool, name="dpool")
+    n, h, w, c = d.shape
+    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise ValueError("subsample_add_bwd_: dpool must be [N,(H-1)//2+1,(W-1)//2+1,C]")
+    _native.check(_native.lib().seam_subsample_add_bwd_f32(_ptr(d), _ptr(dpool), n, h, w, dpool.shape[1], dpool.shape[2], c, _stream()),
+                  "seam_subsample_add_bwd_f32")
+    return d
+
+
+subsample_add_bwd = subsample_add_bwd_
