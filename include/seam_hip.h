@@ -791,6 +791,32 @@ int seam_upsample_add_bwd_f32(const float* dlat, const float* base, float* dtop,
                               seam_stream_t stream);
 int seam_subsample_add_bwd_f32(float* d, const float* dpool, int N, int H, int W, int Hp, int Wp, int C, seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training the ResNet body (torchvision Bottleneck v1.5 with FrozenBatchNorm2d), csrc/seam_body_train.hip.  The stride-1
+ * convolutions of the bottleneck backward run on seam_conv2d_f32 / the Winograd kernels over rotated weights and on
+ * seam_conv_wgrad_f32; the 1x1 / stride-2 shortcut adjoint is seam_subsample_add_bwd_f32.  What is added here: the input
+ * gradient of the three 3x3 / stride-2 / pad-1 convs (layer{2,3,4}.0.conv2) and the ReLU at a block's output.  fp32, NHWC,
+ * no float atomics, a fixed summation order (two launches give the same bits), every output element written exactly once.
+ *
+ * seam_conv3x3s2_dgrad_f32: dy NHWC [N,Ho,Wo,K] with Ho = (H-1)/2+1, Wo = (W-1)/2+1; the forward conv's OIHW weight
+ *   w [K,C,3,3] and the FrozenBN scale [K] (or NULL) of its epilogue packed by seam_pack_conv3x3s2_dgrad_f32 into
+ *   w_packed [9][C][K] (9*C*K floats, w_packed[r*3+s][c][k] = scale[k] * w[k,c,r,s]: dy*scale is never materialised);
+ *   mask NHWC [N,H,W,C] or NULL; dx NHWC [N,H,W,C]:
+ *     dx[n,h,w,c] = sum over (r,s,ho,wo) with 2*ho+r-1 == h, 2*wo+s-1 == w, 0<=ho<Ho, 0<=wo<Wo of
+ *                   scale[k] * dy[n,ho,wo,k] * w[k,c,r,s], summed over k;   dx = 0 where mask <= 0.
+ *   A gather: an even row has the tap r = 1 (ho = h/2), an odd row r = 0 (ho = (h+1)/2) and r = 2 (ho = (h-1)/2), columns
+ *   alike, so the four (row parity, column parity) classes of input pixels are GEMMs over 1, 2, 2 and 4 taps -- 9/4 taps
+ *   per pixel, one launch, v_mfma_f32_32x32x2_f32.  Taps with ho == Ho or wo == Wo (last odd row / column of an even-sized
+ *   map) do not exist and contribute nothing.
+ *   Refused, nothing launched or written: N, H, W <= 0, C % 32, K % 32, a NULL dy / w_packed / dx, dy or dx of 2^31 bytes or more
+ *   (split the batch over images).  The pack refuses K % 32, C % 32 and a NULL w / w_packed.
+ * seam_relu_mask_add_f32: out[m,c] = y[m,c] > 0 ? a[m,c] + b[m,c] : 0 over [M,C], b NULL or a second gradient; 16 bytes per
+ *   lane.  Refused: M <= 0, C <= 0, C % 4, a NULL y / a / out. */
+int seam_pack_conv3x3s2_dgrad_f32(const float* w, const float* scale, float* w_packed, int K, int C, seam_stream_t stream);
+int seam_conv3x3s2_dgrad_f32(const float* dy, const float* w_packed, const float* mask, float* dx, int N, int H, int W, int C, int K,
+                             seam_stream_t stream);
+int seam_relu_mask_add_f32(const float* y, const float* a, const float* b, float* out, int64_t M, int C, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ SIGNATURES = {
     "seam_rpn_scatter_patches_f32": (_i, [_p, _p, _i, _i, _i, _i, C.POINTER(_p), C.POINTER(_i), _p]),
     "seam_upsample_add_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "seam_subsample_add_bwd_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_pack_conv3x3s2_dgrad_f32": (_i, [_p, _p, _p, _i, _i, _p]),
+    "seam_conv3x3s2_dgrad_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "seam_relu_mask_add_f32": (_i, [_p, _p, _p, _p, _i64, _i, _p]),
 }
 
 _lib = None

@@ -485,3 +485,101 @@ class FPNFunction(torch.autograd.Function):
                 dfeat[i] = ops.conv2d(d_in[i], ops.pack_conv_dgrad(iw[i]))
         grads = [t for i in range(4) for t in (diw[i], dib[i])] + [t for i in range(4) for t in (dlw[i], dlb[i])]
         return (None, *dfeat, *grads)
+
+
+# ---------------------------------------------------------------------------------------------------- ResNet body training
+# Bottleneck v1.5 with FrozenBatchNorm2d: y = relu(bn3(conv3(o2)) + shortcut(x)), o2 = relu(bn2(conv2(o1))), o1 = relu(bn1(conv1(x))).
+# A FrozenBN is y = scale[k] * conv + shift[k], so a conv's output gradient carries scale[k]: the dgrad weights are packed from
+# scale[k] * W (once per backward) and the wgrad result is scaled by row.
+
+def _scaled(w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    return w.detach() * scale.view(-1, 1, 1, 1)
+
+
+class BodyFunction(torch.autograd.Function):
+    """A run of consecutive bottlenecks of ``ResNet50Body``, from the first one that holds a trainable weight to the last of
+    layer4: (input of the first block, the conv weights of every block in ``detection.block_weights`` order) -> the outputs of
+    the layers that end inside the run (C2..C5 or the upper ones of them).
+
+    forward: ``detection.body_block`` per block -- the launches of ``ResNet50Body._run``, the fused ``conv2d_dual`` shortcut
+    blocks included -- keeping per block its input, the two post-ReLU inner activations and its output.  backward, last block
+    first: g = relu_mask_add(y, gradient from the block above, gradient of the FPN into this layer's map); conv3: wgrad + 1x1
+    dgrad masked by o2; conv2: wgrad + dgrad masked by o1 (stride 1: the rotated-weight conv, stride 2: ``conv3x3s2_dgrad``);
+    conv1: wgrad + 1x1 dgrad whose epilogue adds the shortcut gradient -- g itself, or for a projection block the 1x1 dgrad of
+    the downsample conv on the coarse grid, scattered to the even pixels when the stride is 2.  A weight gradient is computed
+    only for a weight that requires one, an input gradient only where a block below still needs it (never for the first)."""
+
+    @staticmethod
+    def forward(ctx, meta, x, *weights):
+        from .models.detection import body_block
+        x = x.detach()
+        xs, o1s, o2s, outs = [x], [], [], []
+        for e, stride, _, last in meta:
+            x, o1, o2 = body_block(x, e, stride)
+            xs.append(x)
+            o1s.append(o1)
+            o2s.append(o2)
+            if last:
+                outs.append(x)
+        ctx.save_for_backward(*xs, *o1s, *o2s, *(w.detach() for w in weights))
+        ctx.meta = [(dict(s1=e["c1"].scale, s2=e["c2"].scale, s3=e["c3"].scale, sd=e["ds"].scale if "ds" in e else None),
+                     stride, proj, last) for e, stride, proj, last in meta]
+        ctx.n_blocks = len(meta)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        nb = ctx.n_blocks
+        saved = ctx.saved_tensors
+        xs, o1s, o2s, ws = saved[:nb + 1], saved[nb + 1:2 * nb + 1], saved[2 * nb + 1:3 * nb + 1], saved[3 * nb + 1:]
+        need = ctx.needs_input_grad[2:]
+        wpos, k = [], 0
+        for _, _, proj, _ in ctx.meta:
+            wpos.append(k)
+            k += 4 if proj else 3
+        dws = [None] * len(ws)
+        gouts = list(gouts)
+        g_up = None                                   # gradient of the block above into this block's output
+        for b in range(nb - 1, -1, -1):
+            sc, stride, proj, last = ctx.meta[b]
+            x, o1, o2, y = xs[b], o1s[b], o2s[b], xs[b + 1]
+            g_fpn = gouts.pop() if last else None
+            if g_fpn is not None:
+                g_fpn = g_fpn.contiguous().to(F32)
+            first, second = (g_up, g_fpn) if g_up is not None else (g_fpn, None)
+            if first is None:
+                first = torch.zeros_like(y)
+            g = ops.relu_mask_add(y, first, second)
+            p = wpos[b]
+            w1, w2, w3 = ws[p], ws[p + 1], ws[p + 2]
+            need_dx = b > 0
+            need1 = need[p] or need_dx                # the gradient of o1 is wanted
+            need2 = need[p + 1] or need1              # ... of o2
+            if need[p + 2]:
+                dws[p + 2] = ops.conv_wgrad_chunked(o2, g, 1, 1) * sc["s3"].view(-1, 1, 1, 1)
+            if proj and need[p + 3]:
+                dws[p + 3] = ops.conv_wgrad_chunked(x, g, 1, 1, stride, 0) * sc["sd"].view(-1, 1, 1, 1)
+            g_up = None
+            if not need2:
+                continue
+            d2 = ops.conv2d(g, ops.pack_conv_dgrad(_scaled(w3, sc["s3"])), relu=2, residual=o2)
+            if need[p + 1]:
+                dws[p + 1] = ops.conv_wgrad_chunked(o1, d2, 3, 3, stride, 1) * sc["s2"].view(-1, 1, 1, 1)
+            if not need1:
+                continue
+            if stride == 2:
+                d1 = ops.conv3x3s2_dgrad(d2, ops.pack_conv3x3s2_dgrad(w2, sc["s2"]), o1.shape[1:3], mask=o1)
+            else:
+                d1 = ops.conv2d(d2, ops.pack_conv_dgrad(_scaled(w2, sc["s2"]), pad_fwd=1), relu=2, residual=o1)
+            if need[p]:
+                dws[p] = ops.conv_wgrad_chunked(x, d1, 1, 1) * sc["s1"].view(-1, 1, 1, 1)
+            if not need_dx:
+                continue
+            if proj:
+                short = ops.conv2d(g, ops.pack_conv_dgrad(_scaled(ws[p + 3], sc["sd"])))
+                if stride == 2:
+                    short = ops.subsample_add_bwd_(torch.zeros_like(x), short)
+            else:
+                short = g
+            g_up = ops.conv2d(d1, ops.pack_conv_dgrad(_scaled(w1, sc["s1"])), relu=False, residual=short)
+        return (None, None, *dws)

@@ -26,6 +26,8 @@ enum Id {
     WINO_MT,           // 0 (default): F(2x2) launcher picks its m-tile form; 1 | 2 force it
     WINO_NSPLIT,       // 0 (default): the F(2x2) launcher splits the n-tiles over XCD groups by its weight-footprint rule; > 0 forces it
     ROIALIGN_LDS,      // 2 (default): LDS-staged ROI quadrant tiles; 1: row-staged tiles; 0: gather kernel (profiles/r03_roialign_ab.txt)
+    S2_DGRAD,          // 1 (default): the input gradient of a 3x3 / stride-2 conv runs on conv3x3s2_dgrad (csrc/seam_body_train.hip); 0: the
+                       //   composition -- dy zero-stuffed, then the stride-1 dgrad (read by ops.conv3x3s2_dgrad; A/B: tools/body_train_timing.py)
     COUNT
 };
 
@@ -33,7 +35,7 @@ struct Entry { const char* name; int dflt; };
 constexpr Entry kTable[COUNT] = {
     {"SEAM_W24_PC", 1}, {"SEAM_W24_NT", 0}, {"SEAM_W24_PERSIST", 1}, {"SEAM_W24_NSPLIT", 0}, {"SEAM_W24_DYNLDS", 0}, {"SEAM_F16PC_TILE16", 1},
     {"SEAM_CONV_TILE", 0}, {"SEAM_F16_VEC_EPILOGUE", 1}, {"SEAM_EPI_PRIO", 1}, {"SEAM_CONV_SLOTS", 512}, {"SEAM_CONV_DYNLDS", 0},
-    {"SEAM_PW_BLOCKS", 256}, {"SEAM_WINO_MT", 0}, {"SEAM_WINO_NSPLIT", 0}, {"SEAM_ROIALIGN_LDS", 2},
+    {"SEAM_PW_BLOCKS", 256}, {"SEAM_WINO_MT", 0}, {"SEAM_WINO_NSPLIT", 0}, {"SEAM_ROIALIGN_LDS", 2}, {"SEAM_S2_DGRAD", 1},
 };
 
 extern std::atomic<int> g_value[COUNT];      // seam_abi.hip

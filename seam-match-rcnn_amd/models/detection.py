@@ -195,9 +195,11 @@ class ResNet50Body(nn.Module):
             self._pk, self._pk_key = pk, key
         return self._pk
 
-    def forward(self, x: torch.Tensor, s2d_padded: bool = False) -> List[torch.Tensor]:
+    def forward(self, x: torch.Tensor, s2d_padded: bool = False, taped: bool = False) -> List[torch.Tensor]:
         """x NHWC4 [N,H,W,4] (or the space-to-depth frame [N,H/2,W/2,12|16]; ``s2d_padded``: the fp16 frame with its 2 + 1 zero
-        cells around it, [N,H/2+3,W/2+3,16]) -> [C2, C3, C4, C5] NHWC."""
+        cells around it, [N,H/2+3,W/2+3,16]) -> [C2, C3, C4, C5] NHWC.  ``taped``: ``forward_taped`` (the training form)."""
+        if taped:
+            return self.forward_taped(x, s2d_padded)
         pk = self.packed()
         n = x.shape[0]
         if BODY_STREAMS >= 2 and n >= 2 * BODY_STREAMS and x.is_cuda:
@@ -228,7 +230,8 @@ class ResNet50Body(nn.Module):
             return outs
         return self._run(x, pk, None, s2d_padded)
 
-    def _run(self, x, pk, outs, s2d_padded=False):
+    def _stem(self, x, pk, s2d_padded=False):
+        """Stem conv (either input form) + FrozenBN + ReLU + the 3x3 / stride-2 max-pool."""
         if x.shape[-1] in (12, 16):    # space-to-depth input [N,H/2,W/2,12] (fp16: 16): the stem as a 4x4 / stride-1 conv, output grid = input grid
             streaming = ("stem_rows" in pk and x.dtype == torch.float16 and x.shape[-1] == 16
                          and (x.shape[1] - (3 if s2d_padded else 0)) * (x.shape[2] - (3 if s2d_padded else 0)) >= 128)
@@ -240,7 +243,10 @@ class ResNet50Body(nn.Module):
                 x = ops.conv2d(x, pk["stem_s2d"], relu=True, out_hw=(x.shape[1], x.shape[2]))
         else:
             x = ops.conv2d(x, pk["stem"], relu=True)           # 7x7/s2 + FrozenBN + ReLU
-        x = ops.maxpool2d(x, 3, 2, 1)
+        return ops.maxpool2d(x, 3, 2, 1)
+
+    def _run(self, x, pk, outs, s2d_padded=False):
+        x = self._stem(x, pk, s2d_padded)
         feats = []
         for li in range(1, 5):
             nblk = len(getattr(self, f"layer{li}"))
@@ -256,6 +262,60 @@ class ResNet50Body(nn.Module):
                                out=outs[li - 1] if (outs is not None and bi == nblk - 1) else None)
             feats.append(x)
         return feats
+
+    def blocks(self):
+        """[(layer, index, Bottleneck)] in forward order."""
+        return [(li, bi, b) for li in range(1, 5) for bi, b in enumerate(getattr(self, f"layer{li}"))]
+
+    def forward_taped(self, x: torch.Tensor, s2d_padded: bool = False) -> List[torch.Tensor]:
+        """The same four maps (the same bits: the launches of ``_run`` on the packed weights, on one stream) with a tape into the
+        conv weights of ``layer1..layer4`` that require a gradient (``autograd.BodyFunction``): what ``MatchRCNN.forward`` runs
+        in training mode when the body can learn.  The tape starts at the first block that holds a trainable parameter: the stem
+        and the blocks below it run as in ``forward``, nothing of them is kept and no gradient is computed for them.  fp32; the
+        stem (``conv1``) has no backward and must be frozen."""
+        from ..autograd import BodyFunction
+        if cdt(self) != torch.float32 or x.dtype != torch.float32:
+            raise NotImplementedError("the training branch of the ResNet body is fp32 only: call set_compute_dtype(torch.float32)")
+        if self.conv1.weight.requires_grad:
+            raise NotImplementedError(
+                "ResNet body training: the stem of the backbone (backbone.body.conv1 and its max-pool) has no backward; freeze "
+                "it with `model.backbone.body.conv1.weight.requires_grad_(False)` or build the model with "
+                "trainable_backbone_layers <= 4 (layer1..layer4 may learn)")
+        pk = self.packed()
+        blocks = self.blocks()
+        start = next((i for i, (_, _, b) in enumerate(blocks) if any(p.requires_grad for p in b.parameters())), len(blocks))
+        with torch.no_grad():
+            x = self._stem(x.detach(), pk, s2d_padded)
+            feats = []
+            for li, bi, b in blocks[:start]:
+                x = body_block(x, pk[(li, bi)], b.stride)[0]
+                if bi == len(getattr(self, f"layer{li}")) - 1:
+                    feats.append(x)
+        if start == len(blocks):
+            return feats
+        rest = blocks[start:]
+        weights = [w for _, _, b in rest for w in block_weights(b)]
+        meta = [(pk[(li, bi)], b.stride, b.downsample is not None, bi == len(getattr(self, f"layer{li}")) - 1) for li, bi, b in rest]
+        return feats + list(BodyFunction.apply(meta, x, *weights))
+
+
+def block_weights(b: Bottleneck):
+    """The conv weights of a bottleneck in the order ``BodyFunction`` takes them: conv1, conv2, conv3[, downsample.0]."""
+    ws = [b.conv1.weight, b.conv2.weight, b.conv3.weight]
+    if b.downsample is not None:
+        ws.append(b.downsample[0].weight)
+    return ws
+
+
+def body_block(x, e, stride):
+    """One bottleneck on its packed weights ``e`` -- the launches of ``ResNet50Body._run`` -> (output, the two post-ReLU inner
+    activations)."""
+    o1 = ops.conv2d(x, e["c1"], relu=True)
+    o2 = ops.conv2d(o1, e["c2"], relu=True)
+    if "c3ds" in e:
+        return ops.conv2d_dual(o2, x, e["c3ds"], stride, relu=True), o1, o2
+    idt = ops.conv2d(x, e["ds"]) if "ds" in e else x
+    return ops.conv2d(o2, e["c3"], relu=True, residual=idt), o1, o2
 
 
 # The small pyramid levels (100^2 and below) cannot fill 256 CUs on their own; their FPN output convs and RPN-head launches run on
@@ -364,14 +424,29 @@ class BackboneWithFPN(nn.Module):
         return self.fpn(self.body(x, s2d_padded))
 
 
-def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, **_):
+BODY_LAYER_ORDER = ['layer4', 'layer3', 'layer2', 'layer1', 'conv1']
+
+
+def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_layers=None, **_):
+    """``trainable_layers`` is torchvision's keyword: an integer 0..5 freezes every parameter of the body whose name does not start
+    with one of the first ``n`` entries of ['layer4', 'layer3', 'layer2', 'layer1', 'conv1'] (3: the reference's configuration;
+    5 unfreezes the stem, which the training forward refuses).  None (the default) leaves every ``requires_grad`` as built."""
+    if trainable_layers is not None and (isinstance(trainable_layers, bool) or not isinstance(trainable_layers, int)
+                                         or not 0 <= trainable_layers <= 5):
+        raise ValueError(f"trainable_layers must be None or an integer in 0..5, got {trainable_layers!r}")
     if backbone_name != "resnet50":
         raise NotImplementedError("only resnet50 is on the SEAM path (ref models/video_matchrcnn.py:337)")
     if pretrained:
         import warnings
         warnings.warn("pretrained_backbone=True ignored: no network in this environment; load weights with "
                       "load_state_dict() (keys are torchvision-compatible)")
-    return BackboneWithFPN()
+    backbone = BackboneWithFPN()
+    if trainable_layers is not None:
+        keep = BODY_LAYER_ORDER[:trainable_layers]
+        for name, p in backbone.body.named_parameters():
+            if not any(name.startswith(l) for l in keep):
+                p.requires_grad_(False)
+    return backbone
 
 
 # ------------------------------------------------------------------------------ RPN (a5)

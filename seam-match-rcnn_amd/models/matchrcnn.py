@@ -14,8 +14,10 @@ Training branch of the heads (``NewRoIHeads.forward`` with ``self.training``)   
 of the box, mask and match heads, and of the feature maps when they carry a tape (``autograd.RoIAlignFunction``).
 
 ``MatchRCNN.forward(images, targets)`` in training mode adds the RPN's two losses (``detection.RegionProposalNetwork``)
-and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43).  ``backbone.body`` is
-frozen; ``backbone.fpn`` learns from all six losses when its parameters require a gradient (``autograd.FPNFunction``).
+and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43).  ``backbone.fpn`` learns from
+all six losses when its parameters require a gradient (``autograd.FPNFunction``), and so do the bottlenecks of
+``backbone.body.layer1..layer4`` (``autograd.BodyFunction``); the stem stays frozen.  ``trainable_backbone_layers=3`` is the
+reference's configuration (torchvision's default of ``resnet_fpn_backbone``: layer2..layer4 learn).
 """
 from __future__ import annotations
 
@@ -233,25 +235,34 @@ class MatchRCNN(VideoMatchRCNN):
         (ref stuffs/engine.py:40-43) -- loss_classifier, loss_box_reg, loss_mask, loss_match from the RoI heads and
         loss_objectness, loss_rpn_box_reg from the RPN.  ``backward()`` reaches ``rpn.head``, the RoI heads and -- when one of
         its parameters requires a gradient -- the sixteen parameters of ``backbone.fpn`` (through RoIAlign, the RPN's windows
-        and the top-down merges).  The ResNet body is computed without a tape, so every parameter of ``backbone.body`` must be
-        frozen (``requires_grad_(False)``).  With the whole backbone frozen nothing is taped and the launches are unchanged."""
+        and the top-down merges) and the conv weights of ``backbone.body.layer1..layer4`` that require one
+        (``autograd.BodyFunction``; the tape starts at the first block that holds such a weight).  The stem has no backward:
+        ``backbone.body.conv1.weight`` must be frozen.  With the whole backbone frozen nothing is taped and the launches are
+        unchanged; with only the body frozen the step is the FPN-training one."""
         if not self.training or targets is None:
             return super().forward(images, targets)
-        if any(p.requires_grad for p in self.backbone.body.parameters()):
+        body = self.backbone.body
+        if body.conv1.weight.requires_grad:
             raise NotImplementedError(
-                "MatchRCNN training: the ResNet body backward of the backbone is not built, so backbone.body cannot learn; "
-                "freeze it with `for p in model.backbone.body.parameters(): p.requires_grad_(False)` (backbone.fpn may stay "
-                "trainable; a silent partial gradient would be worse)")
+                "MatchRCNN training: the stem of the backbone (backbone.body.conv1 and its max-pool) has no backward, so it cannot "
+                "learn; freeze it with `model.backbone.body.conv1.weight.requires_grad_(False)` or build the model with "
+                "trainable_backbone_layers <= 4 (layer1..layer4 and backbone.fpn may stay trainable; a silent partial gradient "
+                "would be worse)")
+        body_learns = any(p.requires_grad for p in body.parameters())
         fpn_learns = any(p.requires_grad for p in self.backbone.fpn.parameters())
         if any(det.cdt(m) != torch.float32 for m in (self, self.backbone, self.rpn, self.roi_heads)):
             raise NotImplementedError("MatchRCNN training is fp32 only: call set_compute_dtype(torch.float32)")
         images = list(images)
         if len(images) != len(targets):
             raise ValueError("one target dict per image is needed")
-        if fpn_learns:                      # body without a tape, the pyramid through FPNFunction
+        if body_learns or fpn_learns:
             with torch.no_grad():
                 x, sizes, orig, padded = self.transform([i.detach() for i in images])
-                c = self.backbone.body(x)            # fp32: never the padded space-to-depth frame of the fp16 path
+            if body_learns:                 # the body through BodyFunction; a frozen FPN still passes its gradient to C2..C5
+                c = body(x, taped=True)
+            else:                           # body without a tape, the pyramid through FPNFunction
+                with torch.no_grad():
+                    c = body(x)             # fp32: never the padded space-to-depth frame of the fp16 path
             feats = self.backbone.fpn.forward_taped(c)
         else:
             with torch.no_grad():
@@ -286,10 +297,13 @@ def resize_masks_nearest(masks: torch.Tensor, hw) -> torch.Tensor:
     return masks.index_select(1, src(masks.shape[1], h)).index_select(2, src(masks.shape[2], w)).contiguous()
 
 
-def matchrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True, **kwargs):
+def matchrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True,
+                           trainable_backbone_layers=None, **kwargs):
+    """``trainable_backbone_layers``: torchvision's keyword, passed to ``det.resnet_fpn_backbone`` (None: nothing is frozen here;
+    3: the reference's layer2..layer4)."""
     if pretrained:
         pretrained_backbone = False
-    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone)
+    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone, trainable_layers=trainable_backbone_layers)
     model = MatchRCNN(backbone, num_classes, **kwargs)
     if pretrained:
         raise RuntimeError("pretrained=True needs a download (" + model_urls['maskrcnn_resnet50_fpn_coco'] +

@@ -320,10 +320,12 @@ class VideoMatchRCNN(nn.Module):
 
 
 def videomatchrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True,
-                                n_frames=3, **kwargs):
+                                n_frames=3, trainable_backbone_layers=None, **kwargs):
+    """``trainable_backbone_layers``: torchvision's keyword, passed to ``det.resnet_fpn_backbone`` (it sets ``requires_grad`` only:
+    ``VideoMatchRCNN`` itself stays inference-only)."""
     if pretrained:
         pretrained_backbone = False
-    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone)
+    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone, trainable_layers=trainable_backbone_layers)
     model = VideoMatchRCNN(backbone, num_classes, n_frames, **kwargs)
     if pretrained:
         raise RuntimeError("pretrained=True needs a download (" + model_urls['maskrcnn_resnet50_fpn_coco'] +

@@ -1524,3 +1524,96 @@ def subsample_add_bwd_(d: torch.Tensor, dpool: torch.Tensor) -> torch.Tensor:
 
 
 subsample_add_bwd = subsample_add_bwd_
+
+
+# ---------------------------------------------------------------------------------------------------- ResNet body training
+def relu_mask_add(y: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = y > 0 ? a + b : 0 over [..., C] (``seam_relu_mask_add_f32``): the ReLU at a bottleneck's output, whose gradient
+    feeds both the residual branch and the shortcut; ``b`` (or None) is a second gradient arriving at the same map."""
+    y, a = _req(y, name="y"), _req(a, name="a")
+    if a.shape != y.shape or (b is not None and b.shape != y.shape):
+        raise ValueError("relu_mask_add: y, a and b need one shape")
+    if b is not None:
+        b = _req(b, name="b")
+    c = y.shape[-1]
+    out = torch.empty_like(y)
+    _native.check(_native.lib().seam_relu_mask_add_f32(_ptr(y), _ptr(a), _ptr(b), _ptr(out), y.numel() // c, c, _stream()),
+                  "seam_relu_mask_add_f32")
+    return out
+
+
+@dataclass
+class PackedS2Dgrad:
+    """Weights of ``conv3x3s2_dgrad``: both forms are packed from the same scaled weight, so either selector value can run."""
+    K: int
+    C: int
+    w: torch.Tensor                       # OIHW, scale folded (the composition packs its rotated form from it on first use)
+    wp: torch.Tensor                      # [9][C][K] rows of seam_conv3x3s2_dgrad_f32
+    pc: Optional[PackedConv] = None       # stride-1 dgrad weights of the composition (SEAM_S2_DGRAD=0)
+
+
+def pack_conv3x3s2_dgrad(weight: torch.Tensor, scale: Optional[torch.Tensor] = None) -> PackedS2Dgrad:
+    """OIHW weight [K,C,3,3] of a 3x3 / stride-2 / pad-1 conv, and the [K] scale of its FrozenBN epilogue (or None), for
+    ``conv3x3s2_dgrad``: ``dy * scale`` is never materialised, the scale rides in the packed weights."""
+    weight = _req(weight.detach(), name="weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("pack_conv3x3s2_dgrad: weight must be [K,C,3,3]")
+    k, c = int(weight.shape[0]), int(weight.shape[1])
+    if scale is not None:
+        scale = _req(scale.detach(), name="scale")
+        if tuple(scale.shape) != (k,):
+            raise ValueError("pack_conv3x3s2_dgrad: scale must be [K]")
+    wp = torch.empty((9, c, k), dtype=F32, device=weight.device)
+    _native.check(_native.lib().seam_pack_conv3x3s2_dgrad_f32(_ptr(weight), _ptr(scale), _ptr(wp), k, c, _stream()),
+                  "seam_pack_conv3x3s2_dgrad_f32")
+    ws = weight if scale is None else (weight * scale[:, None, None, None]).contiguous()
+    return PackedS2Dgrad(k, c, ws, wp)
+
+
+def _conv3x3s2_dgrad_one(dy, pk, hw, mask, out=None):
+    n, ho, wo, k = dy.shape
+    h, w = hw
+    if _native.get_option("SEAM_S2_DGRAD") != 0:
+        dx = out if out is not None else torch.empty((n, h, w, pk.C), dtype=F32, device=dy.device)
+        _native.check(_native.lib().seam_conv3x3s2_dgrad_f32(_ptr(dy), _ptr(pk.wp), _ptr(mask), _ptr(dx), n, h, w, pk.C, k, _stream()),
+                      "seam_conv3x3s2_dgrad_f32")
+        return dx
+    # the composition: dy zero-stuffed onto the even pixels of an [H, W] grid (2Ho-1 stuffed rows + the H - (2Ho-1) zero rows the
+    # forward's last tap never reached), then the stride-1 dgrad with one pixel of padding
+    if pk.pc is None:
+        pk.pc = pack_conv_dgrad(pk.w, pad_fwd=1)
+    z = torch.zeros((n, h, w, k), dtype=F32, device=dy.device)
+    z[:, 0:2 * ho - 1:2, 0:2 * wo - 1:2] = dy
+    return conv2d(z, pk.pc, relu=2 if mask is not None else False, residual=mask, out=out)
+
+
+def conv3x3s2_dgrad(dy: torch.Tensor, pk: PackedS2Dgrad, hw: Sequence[int], mask: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of a 3x3 / stride-2 / pad-1 conv: dy NHWC [N,Ho,Wo,K] -> dx NHWC [N,H,W,C] for the forward input size
+    ``hw`` (Ho = (H-1)//2+1), zeroed where ``mask`` [N,H,W,C] <= 0 (the ReLU of the producer, ``relu=2`` of ``conv2d``).
+    SEAM_S2_DGRAD selects the gather kernel (``seam_conv3x3s2_dgrad_f32``) or the zero-stuffed composition.  A batch whose dy or
+    dx reaches ``WGRAD_MAX_OPERAND_BYTES`` is split over images, as ``conv_wgrad_chunked`` does.  ``out``: a contiguous fp32
+    [N,H,W,C] tensor to write into (every element is written exactly once)."""
+    dy = _req(dy, name="dy")
+    n, ho, wo, k = dy.shape
+    h, w = int(hw[0]), int(hw[1])
+    if n == 0 or k != pk.K or ho != (h - 1) // 2 + 1 or wo != (w - 1) // 2 + 1:
+        raise ValueError(f"conv3x3s2_dgrad: dy {tuple(dy.shape)} does not belong to an input of {h} x {w} and {pk.K} output channels")
+    if mask is not None:
+        mask = _req(mask, name="mask")
+        if tuple(mask.shape) != (n, h, w, pk.C):
+            raise ValueError("conv3x3s2_dgrad: mask must be [N,H,W,C]")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dy.device or out.dtype != F32
+                            or tuple(out.shape) != (n, h, w, pk.C) or not out.is_contiguous()):
+        raise ValueError(f"conv3x3s2_dgrad: out must be a contiguous float32 tensor of shape {(n, h, w, pk.C)} on {dy.device}")
+    per = max(h * w * pk.C, ho * wo * k) * 4
+    if per > WGRAD_MAX_OPERAND_BYTES:
+        raise ValueError(f"conv3x3s2_dgrad: one image's operand ({per} bytes) exceeds the limit of {WGRAD_MAX_OPERAND_BYTES}")
+    step = max(1, min(n, WGRAD_MAX_OPERAND_BYTES // per))
+    if step >= n:
+        return _conv3x3s2_dgrad_one(dy, pk, (h, w), mask, out)
+    if out is None:
+        out = torch.empty((n, h, w, pk.C), dtype=F32, device=dy.device)
+    for i in range(0, n, step):
+        _conv3x3s2_dgrad_one(dy[i:i + step], pk, (h, w), None if mask is None else mask[i:i + step], out[i:i + step])
+    return out
