@@ -491,6 +491,20 @@ int seam_conv2d_bx3(const float* x, const void* w_packed, const float* scale, co
                     int stride, int pad, int relu, seam_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Three-plane split ("sx") convolution: the fp32 product on the bf16 matrix pipe.  Each fp32 operand is cut by
+ * truncation into three bf16 pieces that sum back to it exactly (a = a0 + a1 + a2); every piece product is exact in
+ * the fp32 accumulator.  terms = 6 keeps the products with i + j <= 2 (what is dropped is < 2^-22 of the product, one
+ * fp32 rounding); terms = 9 keeps all nine (the exact fp32 product, summed in another order than the fma chain).
+ * Same contraction, epilogue (scale / shift, residual, ReLU) and argument meaning as seam_conv2d_f32.  Inf / NaN
+ * inputs give NaN outputs; inputs below 2^-110 lose bits under 2^-133.  Weights: seam_pack_conv_weight_sx
+ * (rows_padded * kred * 6 bytes, three bf16 planes per chunk; tmp = rows_padded*kred floats of scratch). */
+int seam_pack_conv_weight_sx(const float* w, void* w_packed, float* tmp, int K, int Cin, int R, int S,
+                             int Cstore, int mode, seam_stream_t stream);
+int seam_conv2d_sx(const float* x, const void* w_packed, const float* scale, const float* shift,
+                   const float* residual, float* y, int N, int H, int W, int C, int K, int R, int S,
+                   int stride, int pad, int relu, int terms, seam_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Winograd F(2x2,3x3) convolution, fp32 MFMA: the stride-1 3x3 layers of the same call sites as seam_conv2d_f32
  * (ResNet-50 bottleneck 3x3s, FPN output convs, RPNHead conv [TV]; MaskRCNNHeads [TV]; MatchPredictor.conv_seq,
  * models/match_head.py:50-60) with 2.25x fewer matrix-core issues.  Same contract as seam_conv2d_f32 with R = S = 3,

@@ -69,6 +69,8 @@ SIGNATURES = {
     "seam_conv2d_upres_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_pack_conv_weight_bx3": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv2d_bx3": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_pack_conv_weight_sx": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_conv2d_sx": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_wino_supported": (_i, [_i, _i, _i, _i, _i]),
     "seam_wino_weight_floats": (C.c_longlong, [_i, _i]),
     "seam_wino_slot_fill_pct": (_i, [_i, _i, _i, _i, _i, _i]),

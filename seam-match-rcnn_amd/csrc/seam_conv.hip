@@ -869,6 +869,376 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm_bx3(const
     }
 }
 
+// =====================================================================================================================
+// Three-plane split ("sx"): the fp32 product itself on the bf16 matrix pipe.
+//   a = a0 + a1 + a2, three bf16 pieces cut by TRUNCATION: a0 = the top 16 bits of a, a1 = the top 16 bits of a - a0,
+//   a2 = a - a0 - a1.  Both subtractions are exact in fp32 (the remainders have <= 16 and <= 8 significand bits), so the
+//   pieces sum back to a exactly; truncation never rounds up, so a finite a near FLT_MAX has finite pieces.  Every piece
+//   product ai*bj has a 16-bit significand: exact in the fp32 accumulator.
+//   TERMS = 6 keeps i + j <= 2: what is dropped (a1b2 + a2b1 + a2b2) is < 2^-22 |ab|, one fp32 rounding of the product.
+//   TERMS = 9 keeps all: the exact fp32 product; only the order of the fp32 additions differs from the fma chain.
+//   Within a k-step the terms are issued smallest first (i + j descending), so the low-order terms meet before a0b0.
+//   Denormals / tiny inputs: the pieces of |a| < 2^-110 reach below the bf16 denormal step 2^-133 and lose those bits
+//   (absolute error < 2^-133 |b|, and the matrix unit may flush denormal pieces): invisible at fp32 scale.  Inf / NaN
+//   inputs: a - a0 = NaN, the outputs that read them are NaN (the fp32 kernel gives Inf for Inf inputs).
+// Everything else is conv_igemm_bx3's: the fp32 gather, the chunk walk, the register ring, the XOR-swizzled 64-byte LDS
+// rows (three planes per operand: 96 KiB at 128 x 128, one block per CU), plus the fp32 kernel's 16-byte epilogue.
+// Weights (seam_pack_conv_weight_sx): [n_slab][chunk][plane 0..2][slab_bn rows][32 bf16] -- 192 B per row-chunk.
+// top 16 bits of x as a float.  The opaque asm keeps each value its own register: without it hipcc (7.x) folds the four
+// masked words of a vector into ONE operand of its v_pk_add_f32 (op_sel_hi:[1,0]) and every element loses the top piece of
+// element 0 instead of its own -- found by the identity test, visible in the ISA.
+__device__ __forceinline__ float top16(float x) {
+    unsigned t = __builtin_bit_cast(unsigned, x) & 0xffff0000u;
+    asm volatile("" : "+v"(t));
+    return __builtin_bit_cast(float, t);
+}
+
+__device__ __forceinline__ void split3_bf16(const f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const float a0 = top16(v[2 * p]), b0 = top16(v[2 * p + 1]);
+        const float ra = v[2 * p] - a0, rb = v[2 * p + 1] - b0;          // exact: <= 16 significand bits left
+        const float a1 = top16(ra), b1 = top16(rb);
+        const float sa = ra - a1, sb = rb - b1;                          // exact: <= 8 bits left, a bf16 as it stands
+        p0[p] = (__builtin_bit_cast(unsigned, a0) >> 16) | __builtin_bit_cast(unsigned, b0);
+        p1[p] = (__builtin_bit_cast(unsigned, a1) >> 16) | __builtin_bit_cast(unsigned, b1);
+        p2[p] = (__builtin_bit_cast(unsigned, sa) >> 16) | (__builtin_bit_cast(unsigned, sb) & 0xffff0000u);
+    }
+}
+
+template <int BM, int BN, int TERMS>
+__global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 1 : 2) void conv_igemm_sx(const ConvArgs p) {
+    static_assert(TERMS == 6 || TERMS == 9, "six or nine piece products");
+    constexpr int NW = 4, ES = 4, EPV = 4, BKE = 32;
+    constexpr int WM = BM / 2, WN = BN / 2;
+    constexpr int MT = WM / 32, NT = WN / 32;
+    constexpr int RP = 8 * NW;
+    constexpr int AI = BM / RP;
+    constexpr int VPP = BN * 4;                  // 16-byte vectors of one weight plane of the tile
+    constexpr int BI = 3 * VPP / 256;            // weight vectors per thread per chunk
+    constexpr int Q = TERMS * MT * NT;           // MFMAs per k-step (16 k-values)
+    constexpr int PA = BM * 64 + 64;             // bytes of one A plane
+    constexpr int PB = BN * 64 + 64;
+
+    __shared__ __attribute__((aligned(16))) char As[2][3 * PA];     // [buffer][plane 0 | 1 | 2]
+    __shared__ __attribute__((aligned(16))) char Bs[2][3 * PB];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int wm0 = (wid >> 1) * WM;
+    const int wn0 = (wid & 1) * WN;
+
+    const int nblk = gridDim.x;
+    const int b = blockIdx.x;
+    const int xcd = b & 7;
+    const int q8 = nblk >> 3, rem = nblk & 7;
+    const int tile = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + (b >> 3);
+    const int tm = tile / p.tiles_n;
+    const int tn = tile - tm * p.tiles_n;
+    const int m0 = tm * BM;
+    const int n0 = tn * BN;
+
+    const int nk = p.kred / BKE;
+    const int lcol = tid & 7;
+    const int lrow = tid >> 3;
+    const int HoWo = p.Ho * p.Wo;
+    const int n_first = m0 / HoWo;
+    const size_t img_elems = (size_t)p.H * p.W * p.C;
+    const size_t rem_bytes = ((size_t)(p.N - n_first) * img_elems) * ES;
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)p.x + (size_t)n_first * img_elems * ES), 0,
+        (int)(rem_bytes > kOob ? kOob : (unsigned)rem_bytes), 0x00020000);
+    const int slab_stride = p.slab_bn * 192;                 // one chunk of a slab: three planes of slab_bn 64-byte rows
+    const int n_in_slab = n0 % p.slab_bn;
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * 6), 0,
+        (int)((unsigned)nk * (unsigned)slab_stride), 0x00020000);
+
+    int arow[AI], ahi[AI], awi[AI];
+#pragma unroll
+    for (int i = 0; i < AI; ++i) {
+        const int m = m0 + lrow + RP * i;
+        if (m < p.M) {
+            const int n = m / HoWo;
+            const int rm = m - n * HoWo;
+            const int ho = rm / p.Wo;
+            const int wo = rm - ho * p.Wo;
+            ahi[i] = ho * p.stride - p.pad;
+            awi[i] = wo * p.stride - p.pad;
+            arow[i] = ((((n - n_first) * p.H + ahi[i]) * p.W + awi[i]) * p.C) * ES;
+        } else {
+            ahi[i] = -(1 << 28);
+            awi[i] = 0;
+            arow[i] = 0;
+        }
+    }
+    // weight vector v = tid + 256 i of the tile's [plane][BN rows][4 slots]: the plane is a compile-time function of i
+    int brow[BI];
+#pragma unroll
+    for (int i = 0; i < BI; ++i) {
+        const int pl = (256 * i) / VPP, within = tid + (256 * i) % VPP;
+        brow[i] = pl * p.slab_bn * 64 + (n_in_slab + (within >> 2)) * 64 + (within & 3) * 16;
+    }
+
+    int kc, kr, ks, tapoff;
+    {
+        const int kk = lcol * EPV;
+        const int pos = kk / p.C;
+        kc = kk - pos * p.C;
+        kr = pos / p.S;
+        ks = pos - kr * p.S;
+        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
+    }
+    int uq = 0;
+
+    constexpr int D = 2;
+    f32x4 areg[D][AI], breg[D][BI];
+    auto load_a = [&](f32x4 (&ar)[AI], int i) {
+        const bool ok = (unsigned)(ahi[i] + kr) < (unsigned)p.H && (unsigned)(awi[i] + ks) < (unsigned)p.W && kr < p.R;
+        const unsigned off = ok ? (unsigned)(arow[i] + tapoff) : kOob;
+        if (!(SEAM_BX3_ABL & 1)) ar[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0));
+    };
+    auto load_b = [&](f32x4 (&br)[BI], int i) {
+        const int so = uq < nk ? uq * slab_stride : (int)kOob;
+        if (!(SEAM_BX3_ABL & 1)) br[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, brow[i], so, 0));
+    };
+    auto advance_k = [&]() {
+        ++uq;
+        if (p.C >= BKE) {
+            if (++ks == p.S) {
+                ks = 0;
+                kc += BKE;
+                if (kc >= p.C) { kc -= p.C; ++kr; }
+            }
+        } else {
+            kc += BKE;
+            while (kc >= p.C) {
+                kc -= p.C;
+                if (++ks == p.S) { ks = 0; ++kr; }
+            }
+        }
+        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
+    };
+    auto load_chunk = [&](f32x4 (&ar)[AI], f32x4 (&br)[BI]) {
+#pragma unroll
+        for (int i = 0; i < AI; ++i) load_a(ar, i);
+#pragma unroll
+        for (int i = 0; i < BI; ++i) load_b(br, i);
+        advance_k();
+    };
+    // A: 4 floats -> 8 B in each of the three planes at bf16 index 4*lcol of the row; B: 16 B of one plane's row
+    auto store_row = [&](const f32x4 (&ar)[AI], const f32x4 (&br)[BI], int buf, int r) {
+        if (SEAM_BX3_ABL & 2) return;
+        if (r < AI) {
+            const int row = lrow + RP * r;
+            const int off = row * 64 + ((((lcol >> 1) ^ (row >> 2)) & 3) << 4) + (lcol & 1) * 8;
+            u32x2 q0, q1, q2;
+            if (SEAM_BX3_ABL & 4) { q0[0] = __builtin_bit_cast(unsigned, ar[r][0]); q0[1] = __builtin_bit_cast(unsigned, ar[r][1]);
+                                    q1[0] = __builtin_bit_cast(unsigned, ar[r][2]); q1[1] = __builtin_bit_cast(unsigned, ar[r][3]); q2 = q0; }
+            else split3_bf16(ar[r], q0, q1, q2);
+            *reinterpret_cast<u32x2*>(&As[buf][off]) = q0;
+            *reinterpret_cast<u32x2*>(&As[buf][PA + off]) = q1;
+            *reinterpret_cast<u32x2*>(&As[buf][2 * PA + off]) = q2;
+        } else {
+            const int i = r - AI;
+            const int pl = (256 * i) / VPP, within = tid + (256 * i) % VPP;
+            const int row = within >> 2;
+            *reinterpret_cast<f32x4*>(&Bs[buf][pl * PB + row * 64 + ((((within & 3) ^ (row >> 2)) & 3) << 4)]) = br[i];
+        }
+    };
+
+    f32x16 acc[MT][NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // fragment addresses: lane reads 16 B (8 bf16 of k) of row (l & 31) at slot 2*step + (l >> 5), swizzled
+    const int arow0 = wm0 + (lane & 31), brow0 = wn0 + (lane & 31);
+    struct Frag { f32x4 a[3][MT], b[3][NT]; };
+    Frag f0, f1;
+    auto read_frags = [&](Frag& f, int buf, int step) {
+        if (SEAM_BX3_ABL & 16) return;
+        const int slot = 2 * step + (lane >> 5);
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int row = arow0 + i * 32;
+            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) f.a[pl][i] = *reinterpret_cast<const f32x4*>(&As[buf][pl * PA + off]);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int row = brow0 + j * 32;
+            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) f.b[pl][j] = *reinterpret_cast<const f32x4*>(&Bs[buf][pl * PB + off]);
+        }
+    };
+    auto mf = [&](const Frag& f, int idx) {       // idx in [0, Q): term-major, the smallest terms of a tile first
+        // (piece of a) * 4 + (piece of b), by descending i + j; the six-term form starts at i + j = 2
+        constexpr int T9[9] = {2 * 4 + 2, 2 * 4 + 1, 1 * 4 + 2, 2 * 4 + 0, 1 * 4 + 1, 0 * 4 + 2, 1 * 4 + 0, 0 * 4 + 1, 0};
+        const int term = T9[idx / (MT * NT) + (9 - TERMS)], i = (idx / NT) % MT, j = idx % NT;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.a[term >> 2][i]),
+                                                            __builtin_bit_cast(bf16x8, f.b[term & 3][j]), acc[i][j], 0, 0, 0);
+    };
+
+    auto chunk = [&](int buf, f32x4 (&lda)[AI], f32x4 (&ldb)[BI], const f32x4 (&sta)[AI], const f32x4 (&stb)[BI]) {
+        // k-step 0 (+ the gathers and weight rows of chunk t+D)
+        read_frags(f1, buf, 1);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            mf(f0, q);
+#pragma unroll
+            for (int i = 0; i < AI + BI; ++i)
+                if ((i * Q) / (AI + BI) == q) {
+                    if (i < AI) load_a(lda, i);
+                    else load_b(ldb, i - AI);
+                }
+            if (q == Q - 1) advance_k();
+        }
+        // k-step 1: chunk t+1 goes to the other LDS buffer behind the first two thirds of the MFMAs, then the barrier
+        // and the first fragments of the next chunk; the last third covers their latency
+        constexpr int QS = (2 * Q) / 3;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            mf(f1, q);
+#pragma unroll
+            for (int r = 0; r < AI + BI; ++r)
+                if ((r * QS) / (AI + BI) == q) store_row(sta, stb, buf ^ 1, r);
+            if (q == QS - 1) {
+                if (!(SEAM_BX3_ABL & 8)) __syncthreads();
+                read_frags(f0, buf ^ 1, 0);
+            }
+        }
+    };
+
+    load_chunk(areg[0], breg[0]);
+#pragma unroll
+    for (int r = 0; r < AI + BI; ++r) store_row(areg[0], breg[0], 0, r);
+    load_chunk(areg[1], breg[1]);
+    __syncthreads();
+    read_frags(f0, 0, 0);
+
+    for (int t = 0; t < nk; t += 2) {
+        chunk(0, areg[0], breg[0], areg[1], breg[1]);
+        if (t + 1 < nk) chunk(1, areg[1], breg[1], areg[0], breg[0]);
+    }
+    __syncthreads();                 // every wave is done with the LDS buffers: the epilogue's transpose reuses them
+
+    // ---- epilogue (the fp32 kernel's: 16-byte form through a wave-private LDS transpose when K % 4 == 0) ----------
+    const size_t tile_off = (size_t)m0 * p.K;
+    const unsigned rows_here = (unsigned)min(BM, p.M - m0);
+    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((char*)p.y + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)(p.res ? p.res : p.y) + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
+    if ((p.K & 3) == 0) {
+        constexpr int EW = WN + 4;                 // padded row, floats
+        constexpr int LPR = WN / 4;                // lanes per row
+        constexpr int RPI = 64 / LPR;              // rows per 16-byte pass of the wave
+        constexpr int NP = 32 / RPI;               // passes per 32-row MFMA tile
+        static_assert(4 * 32 * EW * 4 <= 2 * 3 * (BM >= BN ? PA : PB), "the transpose fits the operand's LDS");
+        float* eb = reinterpret_cast<float*>(BM >= BN ? &As[0][0] : &Bs[0][0]) + wid * 32 * EW;
+        const int er = lane / LPR, ec = (lane % LPR) * 4;
+        const int n = n0 + wn0 + ec;
+        const bool nok = n < p.K;
+        f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+        if (p.scale && nok) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
+        if (p.shift && nok) sh = *reinterpret_cast<const f32x4*>(p.shift + n);
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            unsigned eo[NP];
+            f32x4 rv[NP];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int row = wm0 + i * 32 + k * RPI + er;
+                eo[k] = nok ? (unsigned)(row * p.K + n) * 4u : kOob;
+            }
+            if (p.res) {
+#pragma unroll
+                for (int k = 0; k < NP; ++k)
+                    rv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, eo[k], 0, 0));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    eb[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * EW + j * 32 + (lane & 31)] = acc[i][j][r];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                f32x4 v = *reinterpret_cast<const f32x4*>(&eb[(k * RPI + er) * EW + ec]) * sc + sh;
+                if (p.res) {
+                    if (p.relu == 2) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = rv[k][e] > 0.f ? v[e] : 0.f;
+                    } else {
+                        v += rv[k];
+                    }
+                }
+                if (p.relu == 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, eo[k], 0, 0);
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int n = n0 + wn0 + j * 32 + (lane & 31);
+        const bool nok = n < p.K;
+        const float sc = (p.scale && nok) ? p.scale[n] : 1.f;
+        const float sh = (p.shift && nok) ? p.shift[n] : 0.f;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            unsigned eo[16];
+            float rv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                eo[r] = (unsigned)(row * p.K + n);
+            }
+            if (p.res) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, nok ? eo[r] * 4u : kOob, 0, 0));
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = acc[i][j][r] * sc + sh;
+                if (p.res) v = p.relu == 2 ? (rv[r] > 0.f ? v : 0.f) : v + rv[r];
+                if (p.relu == 1) v = fmaxf(v, 0.f);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rsrc, nok ? eo[r] * 4u : kOob, 0, 0);
+            }
+        }
+    }
+}
+
+// fp32-packed weights [slab][chunk][row][32 floats] -> [slab][chunk][plane][row][32 bf16], the truncation split of split3_bf16
+__global__ void split3_weight_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, size_t total, int slab_bn) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const float x = in[i];
+        const unsigned x0 = __builtin_bit_cast(unsigned, x) & 0xffff0000u;
+        const float r = x - __builtin_bit_cast(float, x0);
+        const unsigned y0 = __builtin_bit_cast(unsigned, r) & 0xffff0000u;
+        const float s = r - __builtin_bit_cast(float, y0);
+        const size_t rowchunk = i >> 5;
+        const int col = (int)(i & 31);
+        const size_t slabchunk = rowchunk / (size_t)slab_bn;
+        const int row = (int)(rowchunk - slabchunk * slab_bn);
+        unsigned short* o = out + slabchunk * 3 * (size_t)slab_bn * 32 + (size_t)row * 32 + col;
+        o[0] = (unsigned short)(x0 >> 16);
+        o[(size_t)slab_bn * 32] = (unsigned short)(y0 >> 16);
+        o[(size_t)slab_bn * 64] = (unsigned short)(__builtin_bit_cast(unsigned, s) >> 16);
+    }
+}
+
 // Re-layout of fp32-packed weights [..][row][32 floats] -> [..][row][32 hi bf16 | 32 lo bf16] (same 128 B per row-chunk)
 __global__ void split_weight_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, size_t total) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -957,7 +1327,7 @@ int pack_weight(const float* w, void* w_packed, int K, int Cin, int R, int S, in
 // r by tiles that touch it ~40 us apart), so halving the weight traffic with the 256x128 / 8-wave tile buys only
 // 2-6 % (fp16 / split-bf16) and nothing for exact fp32, which is MFMA-bound.  The lever that remains is staging the
 // input patch of a tile in LDS once per channel chunk and running all taps from it (next round).
-enum Prec { P_F32 = 0, P_F16 = 1, P_BX3 = 2 };
+enum Prec { P_F32 = 0, P_F16 = 1, P_BX3 = 2, P_SX = 3 };      // P_SX: the three-plane split (conv_igemm_sx), 4-wave tiles only
 
 inline int tile_weight(int prec, int bm, int bn, int taps) {
     const int area = bm * bn;
@@ -965,6 +1335,8 @@ inline int tile_weight(int prec, int bm, int bn, int taps) {
     // fp16: the 256 x 128 / 8-wave tile wins on the 3x3 layers (859 vs 752 TFLOP/s at 80 x 200^2 x 256 -> 256, +3-5 % at 100^2 and on
     // the 14 x 14 ROI maps) and loses 3-5 % on the 1x1 layers (profiles/r02_f16_wave128.txt)
     if (prec == P_F16 && area == 256 * 128) return taps >= 9 ? 92 : 105;
+    // three-plane split: 64 x 128 (two blocks per CU, the 96 KiB 128 x 128 tile only one) measured fastest on every served shape
+    if (prec == P_SX) return area == 128 * 128 ? 117 : area == 64 * 64 ? 110 : bm == 64 ? 100 : 106;
     return area == 256 * 128 ? 95 : area == 128 * 128 ? 100 : area == 64 * 64 ? 200 : 150;
 }
 
@@ -975,7 +1347,7 @@ inline void choose_tile(int prec, int M, int K, int& best_bm, int& best_bn, int 
     if (force) {
         const int fm = force / 1000, fn = force % 1000;
         if ((fm == 256 || fm == 128 || fm == 64) && (fn == 128 || fn == 64) &&
-            fn <= slab && (fm != 256 || fn == 128)) {
+            fn <= slab && (fm != 256 || (fn == 128 && prec != P_SX))) {
             best_bm = fm; best_bn = fn;
             return;
         }
@@ -985,7 +1357,7 @@ inline void choose_tile(int prec, int M, int K, int& best_bm, int& best_bn, int 
     best_bn = slab;
     for (int bm = 256; bm >= 64; bm >>= 1)
         for (int bn = slab; bn >= 64; bn -= 64) {
-            if (bm == 256 && (bn != 128 || prec == P_F32)) continue;       // 8-wave tile: 256x128 only; no gain for exact fp32
+            if (bm == 256 && (bn != 128 || prec == P_F32 || prec == P_SX)) continue;       // 8-wave tile: 256x128 only; no gain for exact fp32
             const long nb = (long)((M + bm - 1) / bm) * (rows / bn);
             const long cost = ((nb + 255) / 256) * bm * bn * tile_weight(prec, bm, bn, taps);
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_bm = bm; best_bn = bn; }
@@ -1078,8 +1450,9 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
     return (int)hipGetLastError();
 }
 
+// terms: 3 = conv_igemm_bx3 (two planes), 6 / 9 = conv_igemm_sx (three planes)
 int conv2d_bx3(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
-               int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
+               int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream, int terms = 3) {
     if ((C % 4) || (C >= 32 && C % 32) || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
     ConvArgs a;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
@@ -1100,11 +1473,25 @@ int conv2d_bx3(const void* x, const void* w_packed, const float* scale, const fl
     const int rows = ((K + 63) / 64) * 64;
     a.slab_bn = rows % 128 == 0 ? 128 : 64;
     int best_bm, best_bn;
-    choose_tile(P_BX3, a.M, K, best_bm, best_bn);
+    choose_tile(terms == 3 ? P_BX3 : P_SX, a.M, K, best_bm, best_bn);
     a.tiles_m = (a.M + best_bm - 1) / best_bm;
     a.tiles_n = rows / best_bn;
     const dim3 grid(a.tiles_m * a.tiles_n);
     hipStream_t st = (hipStream_t)stream;
+    if (terms != 3) {
+        if (terms != 6 && terms != 9) return (int)hipErrorInvalidValue;
+#define SEAM_SX_LAUNCH(BM_, BN_)                                                                          \
+        do {                                                                                              \
+            if (terms == 6) hipLaunchKernelGGL((conv_igemm_sx<BM_, BN_, 6>), grid, dim3(256), 0, st, a);  \
+            else hipLaunchKernelGGL((conv_igemm_sx<BM_, BN_, 9>), grid, dim3(256), 0, st, a);             \
+        } while (0)
+        if (best_bm == 128 && best_bn == 128) SEAM_SX_LAUNCH(128, 128);
+        else if (best_bm == 128) SEAM_SX_LAUNCH(128, 64);
+        else if (best_bn == 128) SEAM_SX_LAUNCH(64, 128);
+        else SEAM_SX_LAUNCH(64, 64);
+#undef SEAM_SX_LAUNCH
+        return (int)hipGetLastError();
+    }
     if (best_bm == 256) hipLaunchKernelGGL((conv_igemm_bx3<256, 128, 8>), grid, dim3(512), 0, st, a);
     else if (best_bm == 128 && best_bn == 128) hipLaunchKernelGGL((conv_igemm_bx3<128, 128, 4>), grid, dim3(256), 0, st, a);
     else if (best_bm == 128) hipLaunchKernelGGL((conv_igemm_bx3<128, 64, 4>), grid, dim3(256), 0, st, a);
@@ -1206,6 +1593,29 @@ int seam_pack_conv_weight_bx3(const float* w, void* w_packed, float* tmp, int K,
 int seam_conv2d_bx3(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual,
                     float* y, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream) {
     return conv2d_bx3(x, w_packed, scale, shift, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream);
+}
+
+/* Three-plane split path (conv_igemm_sx): weights = the fp32 pack's slabs with every chunk re-written as three bf16 planes
+ * [plane][slab rows][32 bf16] (truncation split, the planes sum to the fp32 weight exactly): 1.5x the fp32 pack's bytes;
+ * `tmp` = rows_padded*kred floats of scratch (the fp32 pack). */
+int seam_pack_conv_weight_sx(const float* w, void* w_packed, float* tmp, int K, int Cin, int R, int S, int Cstore, int mode,
+                             void* stream) {
+    const int rc = pack_weight<float>(w, tmp, K, Cin, R, S, Cstore, mode, stream);
+    if (rc) return rc;
+    const int rows = ((K + 63) / 64) * 64;
+    const size_t total = (size_t)rows * kred_of<float>(Cstore, R, S);
+    int grid = (int)((total + 255) / 256);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(split3_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, tmp, (unsigned short*)w_packed, total,
+                       rows % 128 == 0 ? 128 : 64);
+    return (int)hipGetLastError();
+}
+
+int seam_conv2d_sx(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual,
+                   float* y, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, int terms,
+                   void* stream) {
+    if (terms != 6 && terms != 9) return (int)hipErrorInvalidValue;
+    return conv2d_bx3(x, w_packed, scale, shift, residual, y, N, H, W, C, K, R, S, stride, pad, relu, stream, terms);
 }
 
 }  // extern "C"

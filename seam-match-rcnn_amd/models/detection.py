@@ -33,6 +33,9 @@ BBOX_XFORM_CLIP = math.log(1000.0 / 16)
 NMS_MAX_BOXES = 16384     # per-image capacity of seam_nms_sorted_f32 (csrc/seam_detect.hip)
 
 
+import os as _os
+
+
 def _key(params, dtype=None) -> tuple:
     return tuple((p.data_ptr(), p._version) for p in params) + (dtype,)
 
@@ -47,6 +50,31 @@ def cdt(module):
 def adt(module) -> torch.dtype:
     """Storage type of a module's activations: fp16 only on the fp16 path."""
     return torch.float16 if cdt(module) == torch.float16 else torch.float32
+
+
+# fp32 path, inference only: the layer classes below run the fp32 product as bf16 piece products on the bf16 matrix pipe
+# (ops.SX6: three exact bf16 pieces per operand, six products each -- DESIGN 3.x); results are fp32 to within one rounding of each
+# product, where the exact kernels are one rounding of each partial sum away.  The module attribute ``split_f32`` (set for a whole
+# model with ``set_split_f32``; SEAM_SPLIT_F32=0 for the process) switches it off and restores the exact-fp32 kernels bit for bit.
+# Classes: c1 = bottleneck 1x1 reductions, c3 = 1x1 expansions with their residual (C >= SPLIT_C3_MIN_C), c2s2 = the three
+# stride-2 3x3s.  The two-source shortcut GEMMs and the FPN laterals keep their fused fp32 kernels (the split kernel has neither form).
+SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
+SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
+SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; the short reductions of layer1 / layer2 (C = 64, 128) are faster on conv1x1_sw
+SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2").split(",") if c)
+
+
+def split_on(module) -> bool:
+    """The split kernels serve this call: fp32 compute, an eval-mode module, no gradient tape, not switched off.  (A module in
+    training mode keeps the exact kernels under no_grad too: its plain forward stays the bits of its taped forward.)"""
+    return (SPLIT_F32 and getattr(module, "split_f32", True) and cdt(module) == torch.float32 and not module.training
+            and not torch.is_grad_enabled())
+
+
+def set_split_f32(model: nn.Module, on: bool) -> nn.Module:
+    for m in model.modules():
+        m.split_f32 = bool(on)
+    return model
 
 
 def set_compute_dtype(model: nn.Module, dtype) -> nn.Module:
@@ -116,7 +144,6 @@ class FrozenBatchNorm2d(nn.Module):
 # Projection-shortcut blocks (first block of each ResNet layer) as one dual-source GEMM (ops.conv2d_dual).  The two
 # FrozenBN scales are folded into the weights, so results differ from the two-launch form by ~1e-7 relative (one extra
 # rounding per weight); SEAM_FUSE_SHORTCUT=0 keeps the two launches.
-import os as _os
 FUSE_SHORTCUT = _os.environ.get("SEAM_FUSE_SHORTCUT", "1") != "0"
 # The stem on a space-to-depth input: 7x7 / stride 2 / pad 3 over 3 colours == 4x4 / stride 1 / pad (2 before, 1 after) over the 12
 # channels (dy, dx, c) -- the same 147 products per output in 192 reduction steps instead of 224 (SEAM_STEM_S2D=0: NHWC4 form).
@@ -165,7 +192,8 @@ class ResNet50Body(nn.Module):
 
     def packed(self):
         dt = cdt(self)
-        key = _key(self._all(), dt)
+        sx = dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True)
+        key = _key(self._all(), dt) + (sx,)
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
                 pk = {"stem": ops.pack_conv(self.conv1.weight, None, self.bn1.tensors(), stride=2, pad=3,
@@ -191,6 +219,14 @@ class ResNet50Body(nn.Module):
                             if dt in (torch.float32, torch.float16) and FUSE_SHORTCUT:     # conv3 + projection shortcut as one GEMM
                                 e["c3ds"] = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight,
                                                                b.downsample[1].tensors(), bn_eps=b.bn3.eps, dtype=dt)
+                        if sx:      # split twins of the exact packs (the exact ones stay: the switch and the grad-enabled walk use them)
+                            if "c1" in SPLIT_CLASSES:
+                                e["c1x"] = ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=SPLIT_DTYPE)
+                            if "c2s2" in SPLIT_CLASSES and b.stride == 2:
+                                e["c2x"] = ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=2, pad=1, bn_eps=b.bn2.eps,
+                                                         dtype=SPLIT_DTYPE)
+                            if "c3" in SPLIT_CLASSES and "c3ds" not in e and b.conv3.in_channels >= SPLIT_C3_MIN_C:
+                                e["c3x"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=SPLIT_DTYPE)
                         pk[(li, bi)] = e
             self._pk, self._pk_key = pk, key
         return self._pk
@@ -247,18 +283,19 @@ class ResNet50Body(nn.Module):
 
     def _run(self, x, pk, outs, s2d_padded=False):
         x = self._stem(x, pk, s2d_padded)
+        sx = split_on(self)
         feats = []
         for li in range(1, 5):
             nblk = len(getattr(self, f"layer{li}"))
             for bi in range(nblk):
                 e = pk[(li, bi)]
-                o = ops.conv2d(x, e["c1"], relu=True)
-                o = ops.conv2d(o, e["c2"], relu=True)
+                o = ops.conv2d(x, e.get("c1x", e["c1"]) if sx else e["c1"], relu=True)
+                o = ops.conv2d(o, e.get("c2x", e["c2"]) if sx else e["c2"], relu=True)
                 if "c3ds" in e:       # projection-shortcut block: bn3(conv3(o)) + bn_d(conv_d(x)) + ReLU in one launch
                     x = ops.conv2d_dual(o, x, e["c3ds"], getattr(self, f"layer{li}")[bi].stride, relu=True)
                     continue
                 idt = ops.conv2d(x, e["ds"]) if "ds" in e else x
-                x = ops.conv2d(o, e["c3"], relu=True, residual=idt,   # bn3 + add + ReLU fused
+                x = ops.conv2d(o, e.get("c3x", e["c3"]) if sx else e["c3"], relu=True, residual=idt,   # bn3 + add + ReLU fused
                                out=outs[li - 1] if (outs is not None and bi == nblk - 1) else None)
             feats.append(x)
         return feats

@@ -56,7 +56,7 @@ class PackedConv:
     stride: int = 1
     pad: int = 0
     Cin: int = 0                    # real (unpadded) input channels: algorithmic FLOP accounting
-    dtype: object = F32             # operand precision of the packed weights: torch.float32 | torch.float16 | BX3
+    dtype: object = F32             # operand precision of the packed weights: torch.float32 | torch.float16 | BX3 | SX6 | SX9
     u: Optional[torch.Tensor] = None  # fp32 stride-1 3x3 layers: Winograd F(2x2,3x3) weights (seam_pack_conv_weight_wino_f32)
     u24: Optional[torch.Tensor] = None  # ... and F(2x4,3x3) weights (seam_pack_conv_weight_wino24_f32)
     wn: Optional[torch.Tensor] = None   # fp32 1x1 layers with <= 16 outputs: register-resident weights of seam_linear_narrow_f32
@@ -69,6 +69,11 @@ class PackedConv:
 
 
 BX3 = "bf16x3"      # fp32 activations, split-bf16 operands (3 bf16 MFMAs per product, fp32 accumulate)
+# fp32 activations and results, each operand cut into three bf16 pieces that sum to it exactly (csrc/seam_conv.hip conv_igemm_sx):
+# six piece products per fp32 product (what is dropped is below one fp32 rounding of it) or all nine (the exact product)
+SX6 = "bf16x6"
+SX9 = "bf16x9"
+_SX_TERMS = {SX6: 6, SX9: 9}
 
 
 # Exact-fp32 path: run the stride-1 3x3 layers through the Winograd F(2x2,3x3) kernel (csrc/seam_wino.hip).  All fp32
@@ -222,6 +227,12 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         tmp = torch.empty((rows, kred), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_conv_weight_bx3(_ptr(weight), _ptr(wp), _ptr(tmp), K, cin, R, S, cs, mode, _stream()),
                       "seam_pack_conv_weight_bx3")
+    elif dtype in _SX_TERMS:
+        kred = lib.seam_conv_kred(cs, R, S)
+        wp = torch.empty((rows, kred * 3), dtype=torch.bfloat16, device=weight.device)      # opaque: three bf16 planes per chunk
+        tmp = torch.empty((rows, kred), dtype=F32, device=weight.device)
+        _native.check(lib.seam_pack_conv_weight_sx(_ptr(weight), _ptr(wp), _ptr(tmp), K, cin, R, S, cs, mode, _stream()),
+                      "seam_pack_conv_weight_sx")
     else:
         kred = lib.seam_conv_kred_f16(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F16, device=weight.device)
@@ -522,6 +533,10 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
         _native.check(lib.seam_conv2d_f32(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                           n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, int(relu), _stream()),
                       "seam_conv2d_f32")
+    elif pc.dtype in _SX_TERMS:
+        _native.check(lib.seam_conv2d_sx(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
+                                         n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, int(relu), _SX_TERMS[pc.dtype], _stream()),
+                      "seam_conv2d_sx")
     elif pc.dtype == BX3:
         _native.check(lib.seam_conv2d_bx3(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                           n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, int(relu), _stream()),
@@ -535,7 +550,8 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
                                           1 if out_f32 else 0, _stream()), "seam_conv2d_f16")
     if trace is not None:
         e1.record()
-        tile = lib.seam_conv_tile_taps(2 if pc.dtype == BX3 else 1 if pc.dtype == F16 else 0, n * ho * wo, pc.K, pc.R * pc.S)
+        tile = lib.seam_conv_tile_taps(3 if pc.dtype in _SX_TERMS else 2 if pc.dtype == BX3 else 1 if pc.dtype == F16 else 0,
+                                       n * ho * wo, pc.K, pc.R * pc.S)
         if pwhpc:
             variant = "conv1x1_f16pc"
         elif swh:
@@ -553,6 +569,8 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
             variant = f"conv3x3_wino<{lib.seam_wino_tile_variant(n, h, w, c, pc.K, pc.pad)}>"
         elif f16pc:
             variant = "conv3x3_f16pc"
+        elif pc.dtype in _SX_TERMS:
+            variant = f"conv_igemm_sx<{tile // 1000},{tile % 1000},{_SX_TERMS[pc.dtype]}>"
         elif pc.dtype == BX3:
             variant = f"conv_igemm_bx3<{tile // 1000},{tile % 1000}>"
         else:
