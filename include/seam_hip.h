@@ -607,11 +607,17 @@ int seam_match_trunk_f32(const float* roi, const seam_trunk_layer_t* conv, const
  *   axis; ws: >= seam_conv_wgrad_workspace_floats(M = N*Ho*Wo, C, K, R, S) floats.  (Linear: R=S=1, H=W=1.)
  *   Refused (non-zero return, nothing launched or written): N <= 0, Ho <= 0, Wo <= 0, C % 4, K % 4, and either
  *   operand of 2^31 bytes or more -- M*K*4 >= 2^31 (dy) or N*H*W*C*4 >= 2^31 (x): the kernel's buffer offsets are 32-bit.
+ * seam_conv_wgrad_crop_f32: the same sum for a conv whose output was cropped to its first Ho x Wo positions (the stem on the
+ *   space-to-depth frame: 4x4 / stride 1 / pad 2 cropped to the input grid): dy NHWC [N,Ho,Wo,K] is read as it lies, no copy
+ *   onto the conv's own grid.  ws for M = N*Ho*Wo.  Refused as above, and: Ho or Wo beyond the conv's own output grid,
+ *   R, S, stride, H, W <= 0, pad < 0, a NULL pointer.
  * seam_colsum_f32: out[k] = sum_m x[m,k]  (bias gradients); ws: >= seam_colsum_workspace_floats(M,K) floats.
  *   M = 0 writes zeros; K <= 0 returns 0 and writes nothing. */
 int64_t seam_conv_wgrad_workspace_floats(int M, int C, int K, int R, int S);
 int seam_conv_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
                         int R, int S, int stride, int pad, float* ws, seam_stream_t stream);
+int seam_conv_wgrad_crop_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
+                             int R, int S, int stride, int pad, int Ho, int Wo, float* ws, seam_stream_t stream);
 int64_t seam_colsum_workspace_floats(int M, int K);
 int seam_colsum_f32(const float* x, float* out, int M, int K, float* ws, seam_stream_t stream);
 
@@ -825,11 +831,21 @@ int seam_subsample_add_bwd_f32(float* d, const float* dpool, int N, int H, int W
  *   Refused, nothing launched or written: N, H, W <= 0, C % 32, K % 32, a NULL dy / w_packed / dx, dy or dx of 2^31 bytes or more
  *   (split the batch over images).  The pack refuses K % 32, C % 32 and a NULL w / w_packed.
  * seam_relu_mask_add_f32: out[m,c] = y[m,c] > 0 ? a[m,c] + b[m,c] : 0 over [M,C], b NULL or a second gradient; 16 bytes per
- *   lane.  Refused: M <= 0, C <= 0, C % 4, a NULL y / a / out. */
+ *   lane.  Refused: M <= 0, C <= 0, C % 4, a NULL y / a / out.
+ * seam_maxpool3s2_relu_bwd_f32: the adjoint of the stem's max-pool (3x3 / stride 2 / pad 1) fused with the stem's ReLU mask.
+ *   y NHWC [N,H,W,C] is the pool's input (the stem output after FrozenBN + ReLU; finite), dpool NHWC [N,Ho,Wo,C] with
+ *   Ho = (H-1)/2+1, Wo = (W-1)/2+1 the gradient of the pooled map, dy NHWC [N,H,W,C]:
+ *     dy[n,h,w,c] = y[n,h,w,c] > 0 ? sum over the windows (ph,pw), |2ph-h| <= 1, |2pw-w| <= 1, 0 <= ph < Ho, 0 <= pw < Wo, whose
+ *                   argmax is (h,w), of dpool[n,ph,pw,c] : 0      (1, 2 or 4 windows, added in ascending (ph,pw) order)
+ *   The argmax of a window is torch's: the first maximum in row-major order of its cells inside the image (strict > to replace).
+ *   A gather: a lane owns the pixels (2a+{0,1}, 2b+{0,1}) of four channels, which lie in the windows (a+{0,1}, b+{0,1}) only;
+ *   16 bytes per lane along C, every dy element written exactly once.
+ *   Refused, nothing launched or written: N, H, W, C <= 0, C % 4, a NULL pointer, y of 2^31 bytes or more. */
 int seam_pack_conv3x3s2_dgrad_f32(const float* w, const float* scale, float* w_packed, int K, int C, seam_stream_t stream);
 int seam_conv3x3s2_dgrad_f32(const float* dy, const float* w_packed, const float* mask, float* dx, int N, int H, int W, int C, int K,
                              seam_stream_t stream);
 int seam_relu_mask_add_f32(const float* y, const float* a, const float* b, float* out, int64_t M, int C, seam_stream_t stream);
+int seam_maxpool3s2_relu_bwd_f32(const float* y, const float* dpool, float* dy, int N, int H, int W, int C, seam_stream_t stream);
 
 #ifdef __cplusplus
 }

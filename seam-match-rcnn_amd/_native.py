@@ -144,6 +144,7 @@ SIGNATURES = {
     "seam_mask_select_f32": (_i, [_p, _p, _p, _i, _i, _p]),
     "seam_conv_wgrad_workspace_floats": (_i64, [_i, _i, _i, _i, _i]),
     "seam_conv_wgrad_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "seam_conv_wgrad_crop_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "seam_colsum_workspace_floats": (_i64, [_i, _i]),
     "seam_colsum_f32": (_i, [_p, _p, _i, _i, _p, _p]),
     "seam_avgpool_relu_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _p]),
@@ -175,6 +176,7 @@ SIGNATURES = {
     "seam_pack_conv3x3s2_dgrad_f32": (_i, [_p, _p, _p, _i, _i, _p]),
     "seam_conv3x3s2_dgrad_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "seam_relu_mask_add_f32": (_i, [_p, _p, _p, _p, _i64, _i, _p]),
+    "seam_maxpool3s2_relu_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -507,12 +507,26 @@ class BodyFunction(torch.autograd.Function):
     dgrad masked by o2; conv2: wgrad + dgrad masked by o1 (stride 1: the rotated-weight conv, stride 2: ``conv3x3s2_dgrad``);
     conv1: wgrad + 1x1 dgrad whose epilogue adds the shortcut gradient -- g itself, or for a projection block the 1x1 dgrad of
     the downsample conv on the coarse grid, scattered to the even pixels when the stride is 2.  A weight gradient is computed
-    only for a weight that requires one, an input gradient only where a block below still needs it (never for the first)."""
+    only for a weight that requires one, an input gradient only where a block below still needs it (for the first only when the stem trains).
+
+    ``stem`` = (the stem conv + FrozenBN + ReLU on the body's packed weights, the FrozenBN scale) when the stem trains, else
+    None.  Then ``x`` is the frame (NHWC4 or space-to-depth), ``weights`` starts with ``conv1.weight`` and the run is all sixteen
+    blocks; the frame and the stem output y0 are kept too.  The first block then computes its input gradient as well, which is the
+    gradient of the pooled map: dy0 = ``maxpool3s2_relu_bwd(y0, .)``, and conv1's gradient is ``conv_wgrad`` of the frame
+    the forward consumed -- 7x7 / stride 2 on NHWC4 (the padding channel dropped), or the cropped 4x4 / stride 1 of the
+    space-to-depth form mapped back by ``detection.stem_s2d_grad_to_oihw`` -- scaled by row.  No gradient for the frame."""
 
     @staticmethod
-    def forward(ctx, meta, x, *weights):
+    def forward(ctx, meta, stem, x, *weights):
         from .models.detection import body_block
         x = x.detach()
+        ctx.stem_scale = None
+        stem_saved = ()
+        if stem is not None:
+            conv, ctx.stem_scale = stem
+            y0 = conv(x)
+            stem_saved = (x, y0)
+            x = ops.maxpool2d(y0, 3, 2, 1)
         xs, o1s, o2s, outs = [x], [], [], []
         for e, stride, _, last in meta:
             x, o1, o2 = body_block(x, e, stride)
@@ -521,7 +535,7 @@ class BodyFunction(torch.autograd.Function):
             o2s.append(o2)
             if last:
                 outs.append(x)
-        ctx.save_for_backward(*xs, *o1s, *o2s, *(w.detach() for w in weights))
+        ctx.save_for_backward(*xs, *o1s, *o2s, *stem_saved, *(w.detach() for w in weights))
         ctx.meta = [(dict(s1=e["c1"].scale, s2=e["c2"].scale, s3=e["c3"].scale, sd=e["ds"].scale if "ds" in e else None),
                      stride, proj, last) for e, stride, proj, last in meta]
         ctx.n_blocks = len(meta)
@@ -532,7 +546,11 @@ class BodyFunction(torch.autograd.Function):
         nb = ctx.n_blocks
         saved = ctx.saved_tensors
         xs, o1s, o2s, ws = saved[:nb + 1], saved[nb + 1:2 * nb + 1], saved[2 * nb + 1:3 * nb + 1], saved[3 * nb + 1:]
-        need = ctx.needs_input_grad[2:]
+        need = ctx.needs_input_grad[3:]
+        stem = ctx.stem_scale is not None
+        if stem:                                      # (frame, y0, conv1.weight) ahead of the blocks' weights
+            frame, y0, ws = ws[0], ws[1], ws[3:]
+            need_stem, need = need[0], need[1:]
         wpos, k = [], 0
         for _, _, proj, _ in ctx.meta:
             wpos.append(k)
@@ -552,7 +570,7 @@ class BodyFunction(torch.autograd.Function):
             g = ops.relu_mask_add(y, first, second)
             p = wpos[b]
             w1, w2, w3 = ws[p], ws[p + 1], ws[p + 2]
-            need_dx = b > 0
+            need_dx = b > 0 or stem
             need1 = need[p] or need_dx                # the gradient of o1 is wanted
             need2 = need[p + 1] or need1              # ... of o2
             if need[p + 2]:
@@ -582,4 +600,15 @@ class BodyFunction(torch.autograd.Function):
             else:
                 short = g
             g_up = ops.conv2d(d1, ops.pack_conv_dgrad(_scaled(w1, sc["s1"])), relu=False, residual=short)
-        return (None, None, *dws)
+        if not stem:
+            return (None, None, None, *dws)
+        dw0 = None
+        if need_stem:
+            from .models.detection import stem_s2d_grad_to_oihw
+            dy0 = ops.maxpool3s2_relu_bwd(y0, g_up)
+            if frame.shape[-1] == 4:
+                dw0 = ops.conv_wgrad_chunked(frame, dy0, 7, 7, 2, 3)[:, :3].contiguous()
+            else:
+                dw0 = stem_s2d_grad_to_oihw(ops.conv_wgrad_chunked(frame, dy0, 4, 4, 1, 2, out_hw=dy0.shape[1:3]))
+            dw0 = dw0 * ctx.stem_scale.view(-1, 1, 1, 1)
+        return (None, None, None, dw0, *dws)

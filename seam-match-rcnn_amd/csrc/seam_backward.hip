@@ -623,13 +623,14 @@ int64_t seam_conv_wgrad_workspace_floats(int M, int C, int K, int R, int S) {
     return (int64_t)splits * R * S * K * C;
 }
 
-int seam_conv_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
-                        int stride, int pad, float* ws, void* stream) {
+// Ho, Wo: the rows / columns of dy -- the conv's own output grid, or its first Ho x Wo outputs (a cropped conv)
+static int conv_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                      int Ho, int Wo, float* ws, void* stream) {
     WgradArgs a;
     a.x = x; a.dy = dy; a.ws = ws;
     a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-    a.Ho = (H + 2 * pad - R) / stride + 1;
-    a.Wo = (W + 2 * pad - S) / stride + 1;
+    a.Ho = Ho;
+    a.Wo = Wo;
     if (N <= 0 || a.Ho <= 0 || a.Wo <= 0 || (C % 4) || (K % 4)) return (int)hipErrorInvalidValue;
     a.M = N * a.Ho * a.Wo;
     if ((double)a.M * K * 4 >= 2147483648.0 || (double)N * H * W * C * 4 >= 2147483648.0) return (int)hipErrorInvalidValue;
@@ -641,6 +642,19 @@ int seam_conv_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ws, dw, splits, R * S, K, C);
     return (int)hipGetLastError();
+}
+
+int seam_conv_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                        int stride, int pad, float* ws, void* stream) {
+    return conv_wgrad(x, dy, dw, N, H, W, C, K, R, S, stride, pad, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, ws,
+                      stream);
+}
+
+int seam_conv_wgrad_crop_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
+                             int stride, int pad, int Ho, int Wo, float* ws, void* stream) {
+    if (R <= 0 || S <= 0 || stride <= 0 || pad < 0 || H <= 0 || W <= 0 || !x || !dy || !dw || !ws) return (int)hipErrorInvalidValue;
+    if (Ho > (H + 2 * pad - R) / stride + 1 || Wo > (W + 2 * pad - S) / stride + 1) return (int)hipErrorInvalidValue;
+    return conv_wgrad(x, dy, dw, N, H, W, C, K, R, S, stride, pad, Ho, Wo, ws, stream);
 }
 
 static int colsum_slabs(int M) {

@@ -3,6 +3,7 @@
 //   seam_pack_conv3x3s2_dgrad_f32  OIHW weight (+ FrozenBN scale) -> the tap-major [9][C][K] rows of the kernel below
 //   seam_conv3x3s2_dgrad_f32       input gradient of a 3x3 / stride-2 / pad-1 conv (layer{2,3,4}.0.conv2), gather form
 //   seam_relu_mask_add_f32         out = y > 0 ? a + b : 0 (the ReLU at a block's output, where two gradients meet)
+//   seam_maxpool3s2_relu_bwd_f32   adjoint of the stem's 3x3 / stride-2 / pad-1 max-pool with the stem's ReLU mask (below)
 //
 // The stride-2 input gradient.  h = 2*ho + r - 1, so an even input row has the one tap r = 1 (ho = h/2) and an odd row the taps
 // r = 0 (ho = (h+1)/2) and r = 2 (ho = (h-1)/2); columns alike.  The input pixels fall into four (row parity, column parity)
@@ -188,6 +189,101 @@ __global__ __launch_bounds__(256) void relu_mask_add_kernel(const f32x4* __restr
     }
 }
 
+// The adjoint of max-pool(3, 2, 1) behind a ReLU, gather form.  Window ph covers the rows 2ph-1 .. 2ph+1, so the 2 x 2 pixels
+// (2a + {0,1}, 2b + {0,1}) lie in the windows (a + {0,1}, b + {0,1}) and in no other: a lane owns those four pixels of 4 channels.
+// It reads the 5 x 5 cells (2a-1 .. 2a+3) x (2b-1 .. 2b+3) once, scans them in row-major order and keeps per window the first
+// maximum among the POSITIVE cells (strict > to replace, starting from 0) -- torch's argmax wherever it matters: a pixel with
+// y > 0 is the first maximum of a window exactly when it is the first maximum of the window's positive cells, and a pixel with
+// y <= 0 gets a zero from the ReLU mask whatever the pool gave it.  Cells outside the image are read as 0 (a buffer load past the
+// descriptor's range), so they take no part.  Each pixel then takes the dpool of the windows whose argmax it is, added in ascending
+// (ph, pw) order onto 0, and is zeroed where y <= 0.
+// 25 loads of y per 4 outputs (6.25 per pixel, where a pixel-per-lane gather re-reads 16); no LDS: the overlap between
+// neighbouring patches -- columns inside a block, rows between the blocks of two pooled rows -- is served by L1 / L2.
+// A block is (n * Ho + a) * nchunks + chunk; a chunk is 256 lanes of one pooled row, lane = (b, 16-byte channel vector).  Blocks
+// are dealt round-robin over the 8 XCDs, so blockIdx.x is remapped (a bijection, for speed only) to give each XCD one contiguous
+// run of pooled rows: the three y rows two neighbouring pooled rows share then meet in one L2 instead of being fetched by two.
+struct PoolBwdArgs {
+    const float* y;
+    const float* dpool;
+    float* dy;
+    int N, H, W, C, Ho, Wo, cv, nchunks, nblocks;
+};
+
+__global__ __launch_bounds__(256) void maxpool3s2_relu_bwd_kernel(const PoolBwdArgs p) {
+    const int xcd = (int)(blockIdx.x & 7u), per = p.nblocks >> 3, rem = p.nblocks & 7;
+    const int bid = xcd * per + min(xcd, rem) + (int)(blockIdx.x >> 3);
+    const int row = bid / p.nchunks;                                   // n * Ho + a
+    const int j = (bid - row * p.nchunks) * 256 + (int)threadIdx.x;
+    if (j >= p.Wo * p.cv) return;
+    const int n = row / p.Ho, a = row - n * p.Ho;
+    const int b = j / p.cv, c = (j - b * p.cv) * 4;
+    const int h0 = 2 * a - 1, w0 = 2 * b - 1;
+    // y of the whole launch is below 2^31 bytes (checked by the launcher): 32-bit byte offsets, 0x80000000 = out of range = 0.0f
+    const __amdgpu_buffer_rsrc_t y_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)((unsigned)p.N * p.H * p.W * p.C * 4u), 0x00020000);
+
+    f32x4 m[4];                        // running maximum of window (a + (q >> 1), b + (q & 1)) over its positive cells
+    int am[4][4];                      // ... and the cell r * 5 + s that holds it, per channel (-1: no positive cell)
+    f32x4 own[4];                      // y at the lane's pixels: cells (1,1) (1,2) (2,1) (2,2)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        m[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) am[q][e] = -1;
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        const int hi = h0 + r;
+        const bool rok = (unsigned)hi < (unsigned)p.H;
+        const int rbase = ((n * p.H + hi) * p.W + w0) * p.C + c;
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            const bool ok = rok && (unsigned)(w0 + s) < (unsigned)p.W;
+            const unsigned off = ok ? (unsigned)(rbase + s * p.C) * 4u : 0x80000000u;
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(y_rsrc, off, 0, 0));
+            if ((r == 1 || r == 2) && (s == 1 || s == 2)) own[(r - 1) * 2 + (s - 1)] = v;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool in = ((q >> 1) ? r >= 2 : r <= 2) && ((q & 1) ? s >= 2 : s <= 2);
+                if (!in) continue;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    am[q][e] = v[e] > m[q][e] ? r * 5 + s : am[q][e];
+                    m[q][e] = fmaxf(m[q][e], v[e]);
+                }
+            }
+        }
+    }
+
+    const bool a1 = a + 1 < p.Ho, b1 = b + 1 < p.Wo;                 // the windows below / right of (a, b) exist
+    const float* dpn = p.dpool + (((size_t)n * p.Ho + a) * p.Wo + b) * p.C + c;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dp[4];
+    dp[0] = *reinterpret_cast<const f32x4*>(dpn);
+    dp[1] = b1 ? *reinterpret_cast<const f32x4*>(dpn + p.C) : zero;
+    dp[2] = a1 ? *reinterpret_cast<const f32x4*>(dpn + (size_t)p.Wo * p.C) : zero;
+    dp[3] = (a1 && b1) ? *reinterpret_cast<const f32x4*>(dpn + ((size_t)p.Wo + 1) * p.C) : zero;
+
+    float* dyn = p.dy + (size_t)n * p.H * p.W * p.C + c;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {      // pixel (2a + (o >> 1), 2b + (o & 1)) = cell (1 + (o >> 1), 1 + (o & 1))
+        const int hi = 2 * a + (o >> 1), wi = 2 * b + (o & 1);
+        if (hi >= p.H || wi >= p.W) continue;
+        const int id = (1 + (o >> 1)) * 5 + 1 + (o & 1);
+        f32x4 g = zero;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // ascending (ph, pw); a pixel on an even row / column is in no window q with that bit set
+            if (((q >> 1) && !(o >> 1)) || ((q & 1) && !(o & 1))) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                g[e] += am[q][e] == id ? dp[q][e] : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = own[o][e] > 0.f ? g[e] : 0.f;
+        *reinterpret_cast<f32x4*>(dyn + ((size_t)hi * p.W + wi) * p.C) = g;
+    }
+}
+
 inline unsigned grid_for(size_t total) { return (unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256); }
 
 }  // namespace
@@ -234,6 +330,22 @@ int seam_relu_mask_add_f32(const float* y, const float* a, const float* b, float
     hipLaunchKernelGGL(relu_mask_add_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(a), reinterpret_cast<const f32x4*>(b),
                        reinterpret_cast<f32x4*>(out), total);
+    return (int)hipGetLastError();
+}
+
+int seam_maxpool3s2_relu_bwd_f32(const float* y, const float* dpool, float* dy, int N, int H, int W, int C, void* stream) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || !y || !dpool || !dy) return (int)hipErrorInvalidValue;
+    if ((double)N * H * W * C * 4 >= 2147483648.0) return (int)hipErrorInvalidValue;      // dpool is never the larger one
+    PoolBwdArgs a;
+    a.y = y; a.dpool = dpool; a.dy = dy;
+    a.N = N; a.H = H; a.W = W; a.C = C;
+    a.Ho = (H - 1) / 2 + 1;
+    a.Wo = (W - 1) / 2 + 1;
+    a.cv = C >> 2;
+    a.nchunks = (a.Wo * a.cv + 255) / 256;
+    const long long blocks = (long long)N * a.Ho * a.nchunks;         // < 2^31: at most one block per 16 bytes of y
+    a.nblocks = (int)blocks;
+    hipLaunchKernelGGL(maxpool3s2_relu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

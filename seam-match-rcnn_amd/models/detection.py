@@ -186,6 +186,9 @@ class ResNet50Body(nn.Module):
                 inpl = planes * 4
             setattr(self, f"layer{li}", nn.Sequential(*blocks))
         self._pk, self._pk_key = None, None
+        # opt-in: ``forward_taped`` tapes the stem (conv1 + ReLU + max-pool) when conv1.weight requires a gradient; off, such a
+        # weight is refused.  The stem tape is the largest activation of the network (N x H/2 x W/2 x 64 fp32).
+        self.train_stem = False
 
     def _all(self):
         return list(self.parameters()) + list(self.buffers())
@@ -266,8 +269,8 @@ class ResNet50Body(nn.Module):
             return outs
         return self._run(x, pk, None, s2d_padded)
 
-    def _stem(self, x, pk, s2d_padded=False):
-        """Stem conv (either input form) + FrozenBN + ReLU + the 3x3 / stride-2 max-pool."""
+    def _stem(self, x, pk, s2d_padded=False, pool=True):
+        """Stem conv (either input form) + FrozenBN + ReLU + the 3x3 / stride-2 max-pool (``pool=False``: the pool's input)."""
         if x.shape[-1] in (12, 16):    # space-to-depth input [N,H/2,W/2,12] (fp16: 16): the stem as a 4x4 / stride-1 conv, output grid = input grid
             streaming = ("stem_rows" in pk and x.dtype == torch.float16 and x.shape[-1] == 16
                          and (x.shape[1] - (3 if s2d_padded else 0)) * (x.shape[2] - (3 if s2d_padded else 0)) >= 128)
@@ -279,7 +282,7 @@ class ResNet50Body(nn.Module):
                 x = ops.conv2d(x, pk["stem_s2d"], relu=True, out_hw=(x.shape[1], x.shape[2]))
         else:
             x = ops.conv2d(x, pk["stem"], relu=True)           # 7x7/s2 + FrozenBN + ReLU
-        return ops.maxpool2d(x, 3, 2, 1)
+        return ops.maxpool2d(x, 3, 2, 1) if pool else x
 
     def _run(self, x, pk, outs, s2d_padded=False):
         x = self._stem(x, pk, s2d_padded)
@@ -308,18 +311,27 @@ class ResNet50Body(nn.Module):
         """The same four maps (the same bits: the launches of ``_run`` on the packed weights, on one stream) with a tape into the
         conv weights of ``layer1..layer4`` that require a gradient (``autograd.BodyFunction``): what ``MatchRCNN.forward`` runs
         in training mode when the body can learn.  The tape starts at the first block that holds a trainable parameter: the stem
-        and the blocks below it run as in ``forward``, nothing of them is kept and no gradient is computed for them.  fp32; the
-        stem (``conv1``) has no backward and must be frozen."""
+        and the blocks below it run as in ``forward``, nothing of them is kept and no gradient is computed for them.  fp32.
+        A trainable ``conv1.weight`` is refused unless ``train_stem`` is set; with both, the tape starts at the stem: the frame
+        and the stem's output (the pool's input) are kept as well, all sixteen blocks are taped whatever they hold, and the
+        gradient runs through the max-pool and the stem's ReLU into ``conv1.weight`` (never into the frame)."""
         from ..autograd import BodyFunction
         if cdt(self) != torch.float32 or x.dtype != torch.float32:
             raise NotImplementedError("the training branch of the ResNet body is fp32 only: call set_compute_dtype(torch.float32)")
-        if self.conv1.weight.requires_grad:
+        stem = self.conv1.weight.requires_grad
+        if stem and not self.train_stem:
             raise NotImplementedError(
                 "ResNet body training: the stem of the backbone (backbone.body.conv1 and its max-pool) has no backward; freeze "
                 "it with `model.backbone.body.conv1.weight.requires_grad_(False)` or build the model with "
-                "trainable_backbone_layers <= 4 (layer1..layer4 may learn)")
+                "trainable_backbone_layers <= 4 (layer1..layer4 may learn).  Stem training is opt-in: set `train_stem=True` "
+                "(constructor keyword, or the attribute of backbone.body).")
         pk = self.packed()
         blocks = self.blocks()
+        if stem:
+            weights = [self.conv1.weight] + [w for _, _, b in blocks for w in block_weights(b)]
+            meta = [(pk[(li, bi)], b.stride, b.downsample is not None, bi == len(getattr(self, f"layer{li}")) - 1) for li, bi, b in blocks]
+            stem_fwd = (lambda f: self._stem(f, pk, s2d_padded, pool=False), pk["stem"].scale)
+            return list(BodyFunction.apply(meta, stem_fwd, x, *weights))
         start = next((i for i, (_, _, b) in enumerate(blocks) if any(p.requires_grad for p in b.parameters())), len(blocks))
         with torch.no_grad():
             x = self._stem(x.detach(), pk, s2d_padded)
@@ -333,7 +345,18 @@ class ResNet50Body(nn.Module):
         rest = blocks[start:]
         weights = [w for _, _, b in rest for w in block_weights(b)]
         meta = [(pk[(li, bi)], b.stride, b.downsample is not None, bi == len(getattr(self, f"layer{li}")) - 1) for li, bi, b in rest]
-        return feats + list(BodyFunction.apply(meta, x, *weights))
+        return feats + list(BodyFunction.apply(meta, None, x, *weights))
+
+
+def stem_s2d_grad_to_oihw(dws: torch.Tensor) -> torch.Tensor:
+    """The weight gradient of the stem in its space-to-depth form, [K,12,4,4], back onto the 7x7 taps, [K,3,7,7]: the inverse of
+    the packing in ``ResNet50Body.packed``, dW[k, c, 2r'+dy-1, 2s'+dx-1] = dWs[k, (dy*2+dx)*3 + c, r', s'].  A pure index
+    permutation onto the 49 taps that exist: the slots of the padded tap -1 are dropped, nothing is summed."""
+    k = dws.shape[0]
+    if tuple(dws.shape[1:]) != (12, 4, 4):
+        raise ValueError(f"stem_s2d_grad_to_oihw: expected [K,12,4,4], got {tuple(dws.shape)}")
+    w8 = dws.reshape(k, 2, 2, 3, 4, 4).permute(0, 3, 4, 1, 5, 2).reshape(k, 3, 8, 8)          # [k, c, 2r'+dy, 2s'+dx]
+    return w8[:, :, 1:, 1:].contiguous()
 
 
 def block_weights(b: Bottleneck):
@@ -464,10 +487,11 @@ class BackboneWithFPN(nn.Module):
 BODY_LAYER_ORDER = ['layer4', 'layer3', 'layer2', 'layer1', 'conv1']
 
 
-def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_layers=None, **_):
+def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_layers=None, train_stem=False, **_):
     """``trainable_layers`` is torchvision's keyword: an integer 0..5 freezes every parameter of the body whose name does not start
     with one of the first ``n`` entries of ['layer4', 'layer3', 'layer2', 'layer1', 'conv1'] (3: the reference's configuration;
-    5 unfreezes the stem, which the training forward refuses).  None (the default) leaves every ``requires_grad`` as built."""
+    5 unfreezes the stem, which the training forward refuses unless ``train_stem`` is set).  None (the default) leaves every
+    ``requires_grad`` as built.  ``train_stem`` sets ``backbone.body.train_stem``: a trainable ``conv1.weight`` then learns."""
     if trainable_layers is not None and (isinstance(trainable_layers, bool) or not isinstance(trainable_layers, int)
                                          or not 0 <= trainable_layers <= 5):
         raise ValueError(f"trainable_layers must be None or an integer in 0..5, got {trainable_layers!r}")
@@ -478,6 +502,7 @@ def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_la
         warnings.warn("pretrained_backbone=True ignored: no network in this environment; load weights with "
                       "load_state_dict() (keys are torchvision-compatible)")
     backbone = BackboneWithFPN()
+    backbone.body.train_stem = bool(train_stem)
     if trainable_layers is not None:
         keep = BODY_LAYER_ORDER[:trainable_layers]
         for name, p in backbone.body.named_parameters():

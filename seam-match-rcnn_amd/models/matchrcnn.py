@@ -16,8 +16,9 @@ of the box, mask and match heads, and of the feature maps when they carry a tape
 ``MatchRCNN.forward(images, targets)`` in training mode adds the RPN's two losses (``detection.RegionProposalNetwork``)
 and returns the six-entry loss dict of the reference's phase-1 loop (ref stuffs/engine.py:40-43).  ``backbone.fpn`` learns from
 all six losses when its parameters require a gradient (``autograd.FPNFunction``), and so do the bottlenecks of
-``backbone.body.layer1..layer4`` (``autograd.BodyFunction``); the stem stays frozen.  ``trainable_backbone_layers=3`` is the
-reference's configuration (torchvision's default of ``resnet_fpn_backbone``: layer2..layer4 learn).
+``backbone.body.layer1..layer4`` (``autograd.BodyFunction``); the stem (``conv1``) learns only with ``train_stem=True`` and is
+refused without it.  ``trainable_backbone_layers=3`` is the reference's configuration (torchvision's default of
+``resnet_fpn_backbone``: layer2..layer4 learn).
 """
 from __future__ import annotations
 
@@ -236,18 +237,19 @@ class MatchRCNN(VideoMatchRCNN):
         loss_objectness, loss_rpn_box_reg from the RPN.  ``backward()`` reaches ``rpn.head``, the RoI heads and -- when one of
         its parameters requires a gradient -- the sixteen parameters of ``backbone.fpn`` (through RoIAlign, the RPN's windows
         and the top-down merges) and the conv weights of ``backbone.body.layer1..layer4`` that require one
-        (``autograd.BodyFunction``; the tape starts at the first block that holds such a weight).  The stem has no backward:
-        ``backbone.body.conv1.weight`` must be frozen.  With the whole backbone frozen nothing is taped and the launches are
-        unchanged; with only the body frozen the step is the FPN-training one."""
+        (``autograd.BodyFunction``; the tape starts at the first block that holds such a weight).  The stem is opt-in:
+        ``backbone.body.conv1.weight`` must be frozen unless ``backbone.body.train_stem`` is set, and then it learns too.  With
+        the whole backbone frozen nothing is taped and the launches are unchanged; with only the body frozen the step is the
+        FPN-training one."""
         if not self.training or targets is None:
             return super().forward(images, targets)
         body = self.backbone.body
-        if body.conv1.weight.requires_grad:
+        if body.conv1.weight.requires_grad and not body.train_stem:
             raise NotImplementedError(
                 "MatchRCNN training: the stem of the backbone (backbone.body.conv1 and its max-pool) has no backward, so it cannot "
                 "learn; freeze it with `model.backbone.body.conv1.weight.requires_grad_(False)` or build the model with "
                 "trainable_backbone_layers <= 4 (layer1..layer4 and backbone.fpn may stay trainable; a silent partial gradient "
-                "would be worse)")
+                "would be worse).  Stem training is opt-in: build the model with `train_stem=True`.")
         body_learns = any(p.requires_grad for p in body.parameters())
         fpn_learns = any(p.requires_grad for p in self.backbone.fpn.parameters())
         if any(det.cdt(m) != torch.float32 for m in (self, self.backbone, self.rpn, self.roi_heads)):
@@ -298,12 +300,14 @@ def resize_masks_nearest(masks: torch.Tensor, hw) -> torch.Tensor:
 
 
 def matchrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=True,
-                           trainable_backbone_layers=None, **kwargs):
+                           trainable_backbone_layers=None, train_stem=False, **kwargs):
     """``trainable_backbone_layers``: torchvision's keyword, passed to ``det.resnet_fpn_backbone`` (None: nothing is frozen here;
-    3: the reference's layer2..layer4)."""
+    3: the reference's layer2..layer4).  ``train_stem``: a trainable ``backbone.body.conv1`` learns (5, or None) instead of being
+    refused: ``ResNet50Body.train_stem``."""
     if pretrained:
         pretrained_backbone = False
-    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone, trainable_layers=trainable_backbone_layers)
+    backbone = det.resnet_fpn_backbone('resnet50', pretrained_backbone, trainable_layers=trainable_backbone_layers,
+                                       train_stem=train_stem)
     model = MatchRCNN(backbone, num_classes, **kwargs)
     if pretrained:
         raise RuntimeError("pretrained=True needs a download (" + model_urls['maskrcnn_resnet50_fpn_coco'] +

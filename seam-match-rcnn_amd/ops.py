@@ -309,15 +309,26 @@ def pack_conv_dgrad(weight: torch.Tensor, pad_fwd: int = 0, wino: bool = True) -
     return PackedConv(wp, None, None, cin, cout, R, S, 1, R - 1 - pad_fwd, cout, F32, u, u24)
 
 
-def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0) -> torch.Tensor:
-    """x NHWC [N,H,W,C], dy NHWC [N,Ho,Wo,K] -> dW in PyTorch OIHW layout [K,C,R,S] (fp32 MFMA, split over pixels)."""
+def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0,
+               out_hw: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """x NHWC [N,H,W,C], dy NHWC [N,Ho,Wo,K] -> dW in PyTorch OIHW layout [K,C,R,S] (fp32 MFMA, split over pixels).
+    ``out_hw``: dy belongs to a conv cropped to its first ``out_hw`` output positions (``conv2d(..., out_hw=)``); it is read as it
+    lies (``seam_conv_wgrad_crop_f32``)."""
     lib = _native.lib()
     x, dy = _req(x, name="x"), _req(dy, name="dy")
     n, h, w, c = x.shape
     k = dy.shape[-1]
     m = dy.numel() // k
+    if out_hw is not None:
+        ho, wo = int(out_hw[0]), int(out_hw[1])
+        if tuple(dy.shape[:3]) != (n, ho, wo) or ho > (h + 2 * pad - R) // stride + 1 or wo > (w + 2 * pad - S) // stride + 1:
+            raise ValueError(f"conv_wgrad: dy {tuple(dy.shape)} is not the output of this conv on x {tuple(x.shape)} cropped to {ho} x {wo}")
     dw = torch.empty((k, c, R, S), dtype=F32, device=x.device)
     ws = torch.empty((int(lib.seam_conv_wgrad_workspace_floats(m, c, k, R, S)),), dtype=F32, device=x.device)
+    if out_hw is not None:
+        _native.check(lib.seam_conv_wgrad_crop_f32(_ptr(x), _ptr(dy), _ptr(dw), n, h, w, c, k, R, S, stride, pad, ho, wo, _ptr(ws),
+                                                   _stream()), "seam_conv_wgrad_crop_f32")
+        return dw
     _native.check(lib.seam_conv_wgrad_f32(_ptr(x), _ptr(dy), _ptr(dw), n, h, w, c, k, R, S, stride, pad, _ptr(ws), _stream()),
                   "seam_conv_wgrad_f32")
     return dw
@@ -328,7 +339,8 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 
 WGRAD_MAX_OPERAND_BYTES = (1 << 31) - 1
 
 
-def conv_wgrad_chunked(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0) -> torch.Tensor:
+def conv_wgrad_chunked(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0,
+                       out_hw: Optional[Sequence[int]] = None) -> torch.Tensor:
     """``conv_wgrad`` for operands of any size: the images are split into equal consecutive chunks (the last may be shorter) whose
     operands stay within ``WGRAD_MAX_OPERAND_BYTES``, and the partial dW are added in chunk order -- a fixed order, so two calls
     give the same bits.  One chunk is exactly ``conv_wgrad``."""
@@ -341,10 +353,10 @@ def conv_wgrad_chunked(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride
         raise ValueError(f"conv_wgrad_chunked: one image's operand ({per} bytes) exceeds the limit of {WGRAD_MAX_OPERAND_BYTES}")
     step = max(1, min(n, WGRAD_MAX_OPERAND_BYTES // per))
     if step >= n:
-        return conv_wgrad(x, dy, R, S, stride, pad)
+        return conv_wgrad(x, dy, R, S, stride, pad, out_hw)
     dw = None
     for i in range(0, n, step):
-        part = conv_wgrad(x[i:i + step], dy[i:i + step], R, S, stride, pad)
+        part = conv_wgrad(x[i:i + step], dy[i:i + step], R, S, stride, pad, out_hw)
         dw = part if dw is None else dw.add_(part)
     return dw
 
@@ -1558,6 +1570,30 @@ def relu_mask_add(y: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = 
     _native.check(_native.lib().seam_relu_mask_add_f32(_ptr(y), _ptr(a), _ptr(b), _ptr(out), y.numel() // c, c, _stream()),
                   "seam_relu_mask_add_f32")
     return out
+
+
+def maxpool3s2_relu_bwd(y: torch.Tensor, dpool: torch.Tensor) -> torch.Tensor:
+    """Adjoint of ``maxpool2d(y, 3, 2, 1)`` behind the ReLU that made ``y`` (``seam_maxpool3s2_relu_bwd_f32``): y NHWC
+    [N,H,W,C], the pool's input; dpool NHWC [N,(H-1)//2+1,(W-1)//2+1,C] -> dy [N,H,W,C], each pixel the sum of the dpool of the
+    windows whose argmax it is (torch's: the first maximum in row-major order), zero where y <= 0.  A batch whose y passes
+    ``WGRAD_MAX_OPERAND_BYTES`` is split over images, as ``conv_wgrad_chunked`` splits: images are independent, no bit changes."""
+    y, dpool = _req(y, name="y"), _req(dpool, name="dpool")
+    if y.dim() != 4 or y.shape[0] == 0 or y.shape[-1] % 4:
+        raise ValueError(f"maxpool3s2_relu_bwd: y must be a non-empty NHWC tensor with C % 4 == 0, got {tuple(y.shape)}")
+    n, h, w, c = y.shape
+    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise ValueError(f"maxpool3s2_relu_bwd: dpool {tuple(dpool.shape)} must be [N,(H-1)//2+1,(W-1)//2+1,C] of y {tuple(y.shape)}")
+    per = h * w * c * 4
+    if per > WGRAD_MAX_OPERAND_BYTES:
+        raise ValueError(f"maxpool3s2_relu_bwd: one image's y ({per} bytes) exceeds the limit of {WGRAD_MAX_OPERAND_BYTES}")
+    step = max(1, min(n, WGRAD_MAX_OPERAND_BYTES // per))
+    dy = torch.empty_like(y)
+    lib = _native.lib()
+    for i in range(0, n, step):
+        m = min(step, n - i)
+        _native.check(lib.seam_maxpool3s2_relu_bwd_f32(_ptr(y[i:i + m]), _ptr(dpool[i:i + m]), _ptr(dy[i:i + m]), m, h, w, c, _stream()),
+                      "seam_maxpool3s2_relu_bwd_f32")
+    return dy
 
 
 @dataclass
