@@ -349,7 +349,11 @@ int seam_pair_logits_f32(const float* a, const float* b, const float* w, const f
 
 /* Score + rank: evaluate_movingfashion.py:97-99,265-269.  Reads logits [Q,G,2]; ranks by
  * softmax(x)[...,1] (== monotone in x1-x0), descending, ties -> lower index first.
- * idx int64 [Q,k], score [Q,k] = softmax(x)[...,1] of the selected entries. k <= G. */
+ * idx int64 [Q,k], score [Q,k] = softmax(x)[...,1] of the selected entries.
+ * k <= G, k <= seam_rank_topk_max_k() (256): the selection keeps its winners in on-chip memory; a larger k is refused with
+ * hipErrorInvalidValue and nothing is launched or written (a full ranking is what seam_rank_of_f32 is for).
+ * NaN differences rank last (as -inf), -0 ties with +0. */
+int seam_rank_topk_max_k(void);
 int seam_rank_topk_f32(const float* logits, int64_t* idx, float* score, int Q, int G, int k,
                        seam_stream_t stream);
 
@@ -380,10 +384,13 @@ int seam_rank_of_f32(const float* logits, const int64_t* target, int64_t* rank, 
 /* Rankings over per-frame score rows (evaluate_movingfashion.py:293-315): out[g] = mean (mode 0) or max
  * (mode 1) over the n rows of score [n,G];  seam_rank_of_scores_f32: rank of target[q] in the descending
  * order of the plain score row q of [Q,G] (ties -> lower index first; what `np.argsort(x)[::-1] ==
- * shop_prod_index` extracts at :296-297,306-307). */
+ * shop_prod_index` extracts at :296-297,306-307).
+ * Edge behaviour (pinned by the tests): a NaN score makes the column's mean NaN and is ignored by the max (a column of
+ * nothing but NaN gives -inf); n <= 0 and a mode other than 0 / 1 are refused with hipErrorInvalidValue. */
 int seam_score_reduce_f32(const float* score, float* out, int n, int G, int mode, seam_stream_t stream);
 /* ... over row segments: rows seg[p] .. seg[p+1]-1 (seg: P+1 int32 offsets on the device) -> out [P,G], one launch for all
- * products of an evaluator pass; bit-identical to P calls of seam_score_reduce_f32 (P <= 65535). */
+ * products of an evaluator pass; bit-identical to P calls of seam_score_reduce_f32 (P <= 65535, more is refused).
+ * An empty segment (seg[p] == seg[p+1]) is not refused: its row of out is NaN (mean, 0 / 0) or -inf (max). */
 int seam_score_reduce_seg_f32(const float* score, const int* seg, float* out, int P, int G, int mode, seam_stream_t stream);
 int seam_rank_of_scores_f32(const float* score, const int64_t* target, int64_t* rank, int Q, int G,
                             seam_stream_t stream);
@@ -405,7 +412,7 @@ int seam_gt_select_f32(const float* det_boxes, const float* det_scores, const in
 
 /* Fused pairwise logits + top-k (a13 + a14 in one pass; no [Q,G,2] round trip through HBM):
  * same ranking rule and bit-identical x1-x0 as seam_pair_logits_f32 + seam_rank_topk_f32.
- * k <= 256, k <= G; ws: >= seam_pair_topk_workspace_floats(Q,G,k) floats of scratch. */
+ * k <= seam_rank_topk_max_k() (256), k <= G; ws: >= seam_pair_topk_workspace_floats(Q,G,k) floats of scratch. */
 int64_t seam_pair_topk_workspace_floats(int Q, int G, int k);
 int seam_pair_topk_f32(const float* a, const float* b, const float* w, const float* bias,
                        int64_t* idx, float* score, int Q, int G, int D, int k, float* ws,
@@ -531,8 +538,9 @@ int seam_conv3x3_wino_f32(const float* x, const float* u_packed, const float* sc
  * 1x1 convolutions / Linear layers with at most 16 outputs (csrc/seam_narrow.hip): y[M,K] = act(x[M,C] . w[K,C]^T + bias),
  * C a multiple of 16, C <= 256, K <= 16 (seam_linear_narrow_supported).  Call sites: RPNHead.cls_logits + bbox_pred [TV]
  * (3 + 12 outputs per pixel, packed as one [15, 256] weight) and MaskRCNNPredictor.mask_fcn_logits [TV] (14 classes).
- * HBM-bound row stream on v_mfma_f32_16x16x4_f32 with the weights register-resident; w_packed = 64 * C floats from
- * seam_pack_linear_narrow_f32 (source: the fp32 [K, C] weight). */
+ * HBM-bound row stream on v_mfma_f32_16x16x4_f32 with the weights register-resident; w_packed = a buffer of 64 * C floats
+ * from seam_pack_linear_narrow_f32 (source: the fp32 [K, C] weight), which writes -- and the kernel reads -- its first 16 * C
+ * floats ([C / 16][64 lanes][4]) and leaves the rest alone. */
 int seam_linear_narrow_supported(int C, int K);
 int seam_pack_linear_narrow_f32(const float* w, float* w_packed, int K, int C, seam_stream_t stream);
 int seam_linear_narrow_f32(const float* x, const float* w_packed, const float* bias, float* y, long long M, int C, int K,

@@ -117,6 +117,7 @@ SIGNATURES = {
     "seam_nlb_mfma_max_len": (_i, []),
     "seam_nlb_attnpool_mfma_f32": (_i, [_p, _i64, _i64, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     "seam_pair_logits_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "seam_rank_topk_max_k": (_i, []),
     "seam_rank_topk_f32": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "seam_match_scores_f32": (_i, [_p, _p, _i64, _p]),
     "seam_host_build_tracklets": (_i, [_p, _p, _p, _p, _i, C.c_double, _p, _p, _p]),

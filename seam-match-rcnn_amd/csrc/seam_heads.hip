@@ -609,7 +609,8 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const float* __restrict_
 // 256-product logit tile into LDS with the same register tiling / FMA order as pair_logits_kernel<4,4>
 // (so d = x1 - x0 is bit-identical to the unfused path) and selects the tile's k best per query;
 // stage 2 merges the per-segment candidates.  Candidate = (x0, x1, index).
-constexpr int TK_SEG = 256;
+constexpr int TK_SEG = seam_topk::TOPK_MAX_K;     // columns per stage-1 segment == the most winners a segment can pass on
+static_assert(TK_SEG == 256, "pair_topk_stage1 maps its 256 segment columns onto 4 x 64 lanes");
 
 __device__ __forceinline__ bool tk_better(float d, int g, float bd, int bg) { return d > bd || (d == bd && g < bg); }
 
@@ -880,7 +881,7 @@ int64_t seam_pair_topk_workspace_floats(int Q, int G, int k) {
 int seam_pair_topk_f32(const float* a, const float* b, const float* w, const float* bias, int64_t* idx, float* score,
                        int Q, int G, int Dd, int k, float* ws, void* stream) {
     if (Q <= 0 || k <= 0) return 0;
-    if (k > G || k > TK_SEG || (Dd % 32)) return (int)hipErrorInvalidValue;
+    if (k > G || k > seam_topk::TOPK_MAX_K || (Dd % 32)) return (int)hipErrorInvalidValue;
     const int nseg = (G + TK_SEG - 1) / TK_SEG;
     hipLaunchKernelGGL(pair_topk_stage1, dim3(nseg, (Q + 31) / 32), dim3(256), 0, (hipStream_t)stream, a, b, w, bias, ws,
                        Q, G, Dd, k, nseg);
@@ -888,9 +889,11 @@ int seam_pair_topk_f32(const float* a, const float* b, const float* w, const flo
     return (int)hipGetLastError();
 }
 
+int seam_rank_topk_max_k(void) { return seam_topk::TOPK_MAX_K; }
+
 int seam_rank_topk_f32(const float* logits, int64_t* idx, float* score, int Q, int G, int k, void* stream) {
     if (Q <= 0 || k <= 0) return 0;
-    if (k > G) return (int)hipErrorInvalidValue;
+    if (k > G || k > seam_topk::TOPK_MAX_K) return (int)hipErrorInvalidValue;      // block_topk holds TOPK_MAX_K winners in LDS
     hipLaunchKernelGGL(rank_topk_kernel, dim3(Q), dim3(256), 0, (hipStream_t)stream, logits, idx, score, G, k);
     return (int)hipGetLastError();
 }

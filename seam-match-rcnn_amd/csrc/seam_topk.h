@@ -32,11 +32,15 @@ __device__ __forceinline__ float tk_score(float x0, float x1) {
     return e1 / (e0 + e1);
 }
 
+// Capacity of one selection: block_topk keeps its k winners in TopkShared::key / item / gidx and orders them with one thread
+// each (256-thread workgroups), so every launcher refuses k > TOPK_MAX_K (seam_rank_topk_max_k()).
+constexpr int TOPK_MAX_K = 256;
+
 struct TopkShared {
     unsigned hist[256];
-    unsigned key[256];
-    int item[256];
-    int gidx[256];
+    unsigned key[TOPK_MAX_K];
+    int item[TOPK_MAX_K];
+    int gidx[TOPK_MAX_K];
     unsigned prefix, krem, cnt;
     int red[4];
 };
@@ -215,7 +219,7 @@ __device__ void block_topk(Load load, int n, int k, int64_t* __restrict__ idx_ou
     unsigned T, krem;
     block_kth(load, n, k, sh, T, krem);
     block_collect(load, n, k, T, krem, sh);
-    if (tid < k) {                               // order the k winners by counting (k <= 256)
+    if (tid < k) {                               // order the k winners by counting (k <= TOPK_MAX_K)
         const int mg = sh.gidx[tid], mj = sh.item[tid];
         const int rank = block_winner_rank(sh, tid, k);
         float sc = 0.f;

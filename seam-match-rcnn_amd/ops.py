@@ -1021,11 +1021,23 @@ def pair_logits(a: torch.Tensor, b: torch.Tensor, w: torch.Tensor, bias: torch.T
     return out
 
 
+def _topk_k(k: int, g: int, what: str) -> int:
+    """min(k, G), refused above the selection's capacity (``seam_rank_topk_max_k()``: the kernels keep their winners on chip).
+    Raised before anything is allocated or launched; there is no silent clamp -- a full ranking is what ``rank_of`` gives."""
+    k = min(int(k), int(g))
+    cap = int(_native.lib().seam_rank_topk_max_k())
+    if k > cap:
+        raise ValueError(f"{what}: k = {k} exceeds the top-k capacity of {cap} (seam_rank_topk_max_k()); "
+                         "use rank_of for positions in the full ranking")
+    return k
+
+
 def rank_topk(logits: torch.Tensor, k: int):
-    """logits[Q,G,2] -> (idx int64 [Q,k], score [Q,k]) by descending softmax(x)[...,1]."""
+    """logits[Q,G,2] -> (idx int64 [Q,k], score [Q,k]) by descending softmax(x)[...,1].
+    min(k, G) <= seam_rank_topk_max_k() (256), else ValueError."""
+    k = _topk_k(k, logits.shape[1], "rank_topk")
     logits = _req(logits)
     q, g = logits.shape[0], logits.shape[1]
-    k = min(k, g)
     idx = torch.empty((q, k), dtype=torch.int64, device=logits.device)
     sc = torch.empty((q, k), dtype=F32, device=logits.device)
     _native.check(_native.lib().seam_rank_topk_f32(_ptr(logits), _ptr(idx), _ptr(sc), q, g, k, _stream()),
@@ -1163,11 +1175,13 @@ def pair_topk(a: torch.Tensor, b: torch.Tensor, w: torch.Tensor, bias: torch.Ten
       per-query error bound proves the top k (``stats``: optional int32[4] device tensor that receives [queries redone with the
       direct form, largest candidate list, overflowed lists, 0]; ``force_exact``: test hook, every query takes the direct form);
     * query chunks of ``q_chunk`` through seam_pair_logits_f32 + seam_rank_topk_f32 with one reused logits buffer (small banks);
-    * ``fused=True``: seam_pair_topk_f32, the single-pass VALU kernel."""
+    * ``fused=True``: seam_pair_topk_f32, the single-pass VALU kernel.
+
+    Every branch: min(k, G) <= seam_rank_topk_max_k() (256), else ValueError before anything is allocated or launched."""
     lib = _native.lib()
+    k = _topk_k(k, b.shape[0], "pair_topk")
     a, b, w, bias = _req(a), _req(b), _req(w.detach()), _req(bias.detach())
     q, g, d = a.shape[0], b.shape[0], a.shape[1]
-    k = min(k, g)
     idx = torch.empty((q, k), dtype=torch.int64, device=a.device)
     sc = torch.empty((q, k), dtype=F32, device=a.device)
     can_mfma = d == 256 and g >= lib.seam_pair_topk_mfma_min_gallery() and 0 < k <= lib.seam_pair_topk_mfma_max_k() and q > 0

@@ -136,10 +136,13 @@ def gather_product_bank(local: torch.Tensor, g_total: int, group=None, side_stre
 def match_sequences(aggregator, x3_1b: torch.Tensor, bank: torch.Tensor, k: int = 20):
     """Aggregated street descriptors [S,256] vs the full bank [G,256] with the aggregator's
     pairwise classifier (ref models/match_head.py:161-162), then score + rank
-    (ref evaluate_movingfashion.py:263-269).  -> (x5 [S,G,2], idx [S,k] int64, score [S,k])."""
+    (ref evaluate_movingfashion.py:263-269).  -> (x5 [S,G,2], idx [S,k] int64, score [S,k]).
+    min(k, G) may not exceed the top-k capacity ``seam_rank_topk_max_k()`` (256): ``ops.rank_topk`` raises ValueError above it
+    (no clamp; ``ops.rank_of`` gives positions in the full ranking)."""
     from . import ops
+    k = ops._topk_k(k, bank.shape[0], "match_sequences")        # refused before the logits are computed
     x5 = aggregator.pair(x3_1b, bank)
-    idx, score = ops.rank_topk(x5, min(k, bank.shape[0]))
+    idx, score = ops.rank_topk(x5, k)
     return x5, idx, score
 
 
@@ -149,7 +152,8 @@ def match_sequences_topk(aggregator, x3_1b: torch.Tensor, bank: torch.Tensor, k:
     G = 20 000 / 50 000): ``ops.pair_topk`` -- banks of >= 8192 products go through the MFMA similarity + fused top-k
     (seam_pair_topk_mfma_f32: candidates from the logit-difference GEMM, exact re-scoring, rounding-error proof), smaller ones
     through query chunks of seam_pair_logits_f32 + seam_rank_topk_f32; bit-identical either way.
-    -> (idx [S,k] int64, score [S,k])."""
+    -> (idx [S,k] int64, score [S,k]).  min(k, G) may not exceed ``seam_rank_topk_max_k()`` (256): ``ops.pair_topk`` raises
+    ValueError above it, whichever implementation would have run."""
     from . import ops
     return ops.pair_topk(x3_1b, bank, aggregator.last.weight, aggregator.last.bias, min(k, bank.shape[0]))
 
