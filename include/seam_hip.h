@@ -476,6 +476,19 @@ int seam_rpn_topk_decode_f32(const float* obj, const float* deltas, const float*
 int seam_paste_masks_f32(const float* masks, const float* boxes, float* out, int K, int H, int W,
                          seam_stream_t stream);
 
+/* Mask intersections for COCO-style segm AP (evaluator_det.py), without the paste.  The mask of detection d is the set of
+ * image pixels where seam_paste_masks_f32(probs, boxes) would write a value > 0.5 (strict; bit for bit: both kernels take
+ * the value from one device function).  probs [D,28,28] (the selected-class probabilities of seam_mask_select_*),
+ * boxes [D,4] xyxy in pixels of the original image, gt [G,H,W] uint8 (a pixel is set iff its byte != 0) ->
+ * inter [D,G] = pixels set in both, det_area [D] = pixels set in the detection's mask inside the image.  Only the pixels
+ * of each clipped integer box are visited: sum_d box_area_d x G byte reads, nothing image-sized is written.  Both outputs
+ * are zeroed on the stream and accumulated with integer atomics, so repeated launches give identical results.
+ * D == 0: no-op, returns 0.  G == 0: only det_area is written; inter and gt may be NULL.  A NULL required pointer, a
+ * negative size or H*W >= 2^31 returns non-zero and writes nothing.  Degenerate, inverted and off-image boxes give what
+ * the paste gives (usually no pixel) and read nothing outside gt. */
+int seam_mask_inter_f32(const float* probs, const float* boxes, int D, const uint8_t* gt, int G, int H,
+                        int W, int* inter, int* det_area, seam_stream_t stream);
+
 /* maskrcnn_inference [TV] (call models/video_matchrcnn.py:291): logits laid out
  * [K,14,14,(a,b),ncls] (sub-pixel groups from the transposed conv) -> prob [K,1,28,28] of the
  * channel labels[k] (int64), after sigmoid. */

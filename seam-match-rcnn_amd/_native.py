@@ -142,6 +142,7 @@ SIGNATURES = {
     "seam_rpn_topk_max": (_i, []),
     "seam_rpn_topk_decode_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _i, _i64, _i, _i64, _i, _p]),
     "seam_paste_masks_f32": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "seam_mask_inter_f32": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p, _p]),
     "seam_mask_select_f32": (_i, [_p, _p, _p, _i, _i, _p]),
     "seam_conv_wgrad_workspace_floats": (_i64, [_i, _i, _i, _i, _i]),
     "seam_conv_wgrad_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -2,6 +2,7 @@
 // (64x64 bitmask tiles + one-wave scan), mask-channel select.  Latency-bound integer/bit work.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 
 namespace {
 
@@ -268,37 +269,111 @@ __global__ void mask_select_kernel(const T* __restrict__ logits, const int64_t* 
 
 // paste_masks_in_image [TV]: mask prob [K,1,28,28] zero-padded to 30x30, box expanded by 30/28 and
 // truncated to int, bilinear (align_corners=False) resize of the padded map to the integer box size,
-// pasted into [K,1,H,W] (zeros elsewhere).  One thread per output pixel quad.
+// pasted into [K,1,H,W] (zeros elsewhere).  paste_box / paste_value are the one definition of a pasted pixel: the paste
+// kernel writes the value, the mask-intersection kernel thresholds it, and the two must agree to the bit.  So contraction
+// is off in both functions and every fused multiply-add is spelled out (they are the ones the compiler used to pick for
+// the plain expressions, which keeps seam_paste_masks_f32's results what they were): no caller can round differently.
+struct PasteBox {
+    int x0, y0, x1, y1, bw, bh;     // the integer box (inclusive corners) and its size
+    float sx, sy;                   // 30 / size: padded-map cells per pixel
+};
+
+__device__ __forceinline__ PasteBox paste_box(float4 bx) {
+#pragma clang fp contract(off)
+    PasteBox b;
+    const float scale = 30.f / 28.f;
+    const float wh = (bx.z - bx.x) * 0.5f * scale, hh = (bx.w - bx.y) * 0.5f * scale;
+    const float xs = bx.z + bx.x, ys = bx.w + bx.y;
+    b.x0 = (int)__builtin_fmaf(xs, 0.5f, -wh); b.y0 = (int)__builtin_fmaf(ys, 0.5f, -hh);    // trunc toward 0 (int64 cast)
+    b.x1 = (int)__builtin_fmaf(xs, 0.5f, wh); b.y1 = (int)__builtin_fmaf(ys, 0.5f, hh);
+    b.bw = max(b.x1 - b.x0 + 1, 1); b.bh = max(b.y1 - b.y0 + 1, 1);
+    b.sx = 30.f / (float)b.bw; b.sy = 30.f / (float)b.bh;
+    return b;
+}
+
+// value of pixel (y, x) of the pasted mask; m = the detection's 28x28 map (global or LDS)
+__device__ __forceinline__ float paste_value(const float* m, const PasteBox& b, int y, int x) {
+#pragma clang fp contract(off)
+    const int ry = y - b.y0, rx = x - b.x0;
+    if (!(ry >= 0 && ry < b.bh && rx >= 0 && rx < b.bw && y <= b.y1 && x <= b.x1)) return 0.f;
+    float fy = __builtin_fmaf(b.sy, (float)ry + 0.5f, -0.5f), fx = __builtin_fmaf(b.sx, (float)rx + 0.5f, -0.5f);
+    if (fy < 0.f) fy = 0.f;
+    if (fx < 0.f) fx = 0.f;
+    int iy = min((int)fy, 29), ix = min((int)fx, 29);
+    const int iy1 = iy < 29 ? iy + 1 : iy, ix1 = ix < 29 ? ix + 1 : ix;
+    const float ly = fminf(fmaxf(fy - (float)iy, 0.f), 1.f), lx = fminf(fmaxf(fx - (float)ix, 0.f), 1.f);
+    auto at = [&](int yy, int xx) -> float {      // 30x30 zero-padded view of the 28x28 map
+        return (yy >= 1 && yy <= 28 && xx >= 1 && xx <= 28) ? m[(yy - 1) * 28 + (xx - 1)] : 0.f;
+    };
+    const float top = __builtin_fmaf(1.f - lx, at(iy, ix), lx * at(iy, ix1));
+    const float bot = __builtin_fmaf(1.f - lx, at(iy1, ix), lx * at(iy1, ix1));
+    return __builtin_fmaf(1.f - ly, top, ly * bot);
+}
+
+// One thread per output pixel quad.
 __global__ void paste_masks_kernel(const float* __restrict__ masks, const float* __restrict__ boxes,
                                    float* __restrict__ out, int K, int H, int W) {
     const int k = blockIdx.y;
-    const float4 bx = reinterpret_cast<const float4*>(boxes)[k];
-    const float scale = 30.f / 28.f;
-    const float wh = (bx.z - bx.x) * 0.5f * scale, hh = (bx.w - bx.y) * 0.5f * scale;
-    const float xc = (bx.z + bx.x) * 0.5f, yc = (bx.w + bx.y) * 0.5f;
-    const int x0 = (int)(xc - wh), y0 = (int)(yc - hh), x1 = (int)(xc + wh), y1 = (int)(yc + hh);   // trunc toward 0 (int64 cast)
-    const int bw = max(x1 - x0 + 1, 1), bh = max(y1 - y0 + 1, 1);
-    const float sx = 30.f / (float)bw, sy = 30.f / (float)bh;
+    const PasteBox b = paste_box(reinterpret_cast<const float4*>(boxes)[k]);
     const float* m = masks + (size_t)k * 784;
     float* o = out + (size_t)k * H * W;
     const int total = H * W;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int y = i / W, x = i - y * W;
-        float v = 0.f;
-        const int ry = y - y0, rx = x - x0;
-        if (ry >= 0 && ry < bh && rx >= 0 && rx < bw && y <= y1 && x <= x1) {
-            float fy = sy * ((float)ry + 0.5f) - 0.5f, fx = sx * ((float)rx + 0.5f) - 0.5f;
-            if (fy < 0.f) fy = 0.f;
-            if (fx < 0.f) fx = 0.f;
-            int iy = min((int)fy, 29), ix = min((int)fx, 29);
-            const int iy1 = iy < 29 ? iy + 1 : iy, ix1 = ix < 29 ? ix + 1 : ix;
-            const float ly = fminf(fmaxf(fy - (float)iy, 0.f), 1.f), lx = fminf(fmaxf(fx - (float)ix, 0.f), 1.f);
-            auto at = [&](int yy, int xx) -> float {      // 30x30 zero-padded view of the 28x28 map
-                return (yy >= 1 && yy <= 28 && xx >= 1 && xx <= 28) ? m[(yy - 1) * 28 + (xx - 1)] : 0.f;
-            };
-            v = (1.f - ly) * ((1.f - lx) * at(iy, ix) + lx * at(iy, ix1)) + ly * ((1.f - lx) * at(iy1, ix) + lx * at(iy1, ix1));
+        o[i] = paste_value(m, b, y, x);
+    }
+}
+
+// Mask intersections for COCO-style segm AP without the paste: for detection d only the pixels of its integer box clipped
+// to the image are visited (flattened row-major, so consecutive lanes read consecutive ground-truth bytes along x), the pixel
+// is set iff paste_value > 0.5, and a set pixel counts into det_area[d] and, for every ground truth whose byte there is
+// non-zero, into inter[d][g].  kMiTile ground truths are counted per pass in registers; more take further passes over the
+// box (the 28x28 map sits in LDS, so a pass re-reads no global memory but the ground-truth bytes).  Integer counts: wave
+// sums, then one global atomic per wave and counter into outputs the launcher zeroed -- any order gives the same numbers.
+constexpr int kMiTile = 8;
+
+template <int NG>      // kMiTile, or 0: no ground truth, det_area only
+__global__ __launch_bounds__(256) void mask_inter_kernel(const float* __restrict__ probs, const float* __restrict__ boxes,
+                                                         int D, const uint8_t* __restrict__ gt, int G, int H, int W,
+                                                         int* __restrict__ inter, int* __restrict__ det_area) {
+    __shared__ float sm[784];
+    const size_t hw = (size_t)H * W;
+    for (int d = blockIdx.y; d < D; d += gridDim.y) {
+        __syncthreads();                                  // the previous detection's readers are done with sm
+        for (int i = threadIdx.x; i < 784; i += 256) sm[i] = probs[(size_t)d * 784 + i];
+        __syncthreads();
+        const PasteBox b = paste_box(reinterpret_cast<const float4*>(boxes)[d]);
+        const int xlo = max(b.x0, 0), xhi = min(b.x1, W - 1), ylo = max(b.y0, 0), yhi = min(b.y1, H - 1);
+        if (xlo > xhi || ylo > yhi) continue;             // block-uniform: nothing of the box inside the image
+        const int ncol = xhi - xlo + 1, total = (yhi - ylo + 1) * ncol;      // <= H*W < 2^31
+        for (int g0 = 0; g0 < (NG ? G : 1); g0 += kMiTile) {
+            int area = 0;
+            int cnt[NG ? NG : 1] = {};
+            size_t goff[NG ? NG : 1];                     // past the last ground truth: re-read it (uniform, no branch per load)
+#pragma unroll
+            for (int j = 0; j < NG; ++j) goff[j] = (size_t)min(g0 + j, G - 1) * hw;
+            for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+                const int r = i / ncol;
+                const int y = ylo + r, x = xlo + (i - r * ncol);
+                if (paste_value(sm, b, y, x) > 0.5f) {
+                    ++area;
+                    const uint8_t* p = gt + (size_t)y * W + x;
+#pragma unroll
+                    for (int j = 0; j < NG; ++j) cnt[j] += p[goff[j]] != 0;
+                }
+            }
+            const bool lane0 = (threadIdx.x & 63) == 0;
+            if (g0 == 0) {
+                for (int o = 32; o > 0; o >>= 1) area += __shfl_xor(area, o, 64);
+                if (lane0 && area) atomicAdd(det_area + d, area);
+            }
+#pragma unroll
+            for (int j = 0; j < NG; ++j) {
+                int v = cnt[j];
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane0 && v && g0 + j < G) atomicAdd(inter + (size_t)d * G + g0 + j, v);
+            }
         }
-        o[i] = v;
     }
 }
 
@@ -431,6 +506,28 @@ int seam_paste_masks_f32(const float* masks, const float* boxes, float* out, int
     int gx = (H * W + 255) / 256;
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(paste_masks_kernel, dim3(gx, K), dim3(256), 0, (hipStream_t)stream, masks, boxes, out, K, H, W);
+    return (int)hipGetLastError();
+}
+
+int seam_mask_inter_f32(const float* probs, const float* boxes, int D, const uint8_t* gt, int G, int H, int W, int* inter,
+                        int* det_area, void* stream) {
+    if (D < 0 || G < 0 || H < 0 || W < 0) return (int)hipErrorInvalidValue;
+    if (D == 0) return 0;
+    if (!probs || !boxes || !det_area || (G > 0 && (!gt || !inter)) || (int64_t)H * W >= (int64_t(1) << 31))
+        return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(det_area, 0, (size_t)D * sizeof(int), s);
+    if (e == hipSuccess && G > 0) e = hipMemsetAsync(inter, 0, (size_t)D * G * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    if (H == 0 || W == 0) return 0;
+    // a box covering the image gives each thread about 8 pixels per pass until 64 blocks share it; small boxes leave the
+    // later blocks of their row of the grid without a pixel
+    const int gx = (int)std::min<int64_t>(((int64_t)H * W + 2047) / 2048, 64);
+    const dim3 grid(gx, std::min(D, 65535));
+    if (G > 0)
+        hipLaunchKernelGGL(mask_inter_kernel<kMiTile>, grid, dim3(256), 0, s, probs, boxes, D, gt, G, H, W, inter, det_area);
+    else
+        hipLaunchKernelGGL(mask_inter_kernel<0>, grid, dim3(256), 0, s, probs, boxes, D, gt, G, H, W, inter, det_area);
     return (int)hipGetLastError();
 }
 

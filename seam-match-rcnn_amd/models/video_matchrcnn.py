@@ -244,6 +244,10 @@ class VideoMatchRCNN(nn.Module):
     # rpn_post_nms_top_n_test <= 1000 -- the video model -- and False beyond (MatchRCNN's 4000: the padded rows would multiply the
     # box head's work when NMS keeps far fewer).  An instance may set its own `model.ONE_SYNC`.
     ONE_SYNC = None
+    # True (default): `postprocess` pastes every detection's 28x28 mask into the image ([K,1,H,W] under "masks", as torchvision
+    # does).  False: the boxes are rescaled as before, nothing is pasted, and the [K,1,28,28] probabilities are handed out under
+    # "mask_probs" instead -- what `evaluator_det` and `ops.mask_inter` read (K x H x W fp32 per image is never written).
+    paste_masks = True
 
     def __init__(self, backbone, num_classes, n_frames=3, min_size=800, max_size=1333,
                  rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_test=1000, rpn_nms_thresh=0.7,
@@ -281,7 +285,10 @@ class VideoMatchRCNN(nn.Module):
             boxes = det.GeneralizedRCNNTransform.rescale_boxes(r["boxes"], sz, o)
             r["boxes"] = boxes
             if "masks" in r:
-                r["masks"] = det.paste_masks_in_image(r["masks"], boxes, o)
+                if self.paste_masks:
+                    r["masks"] = det.paste_masks_in_image(r["masks"], boxes, o)
+                else:
+                    r["mask_probs"] = r.pop("masks")
         return result
 
     def forward(self, images, targets=None):

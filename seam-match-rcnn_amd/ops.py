@@ -1288,6 +1288,29 @@ def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, hw) -> torch.Tensor:
     return out
 
 
+def mask_inter(probs: torch.Tensor, boxes: torch.Tensor, gt_masks: torch.Tensor):
+    """probs [D,1,28,28] or [D,28,28] (``mask_select``'s output), boxes [D,4] original-image px, gt_masks uint8 [G,H,W]
+    (set iff != 0) -> (inter int32 [D,G], det_area int32 [D]): pixel counts of ``paste_masks(probs, boxes, (H, W)) > 0.5``
+    against every ground truth and on its own, bit for bit, without the [D,1,H,W] paste (``seam_mask_inter_f32``)."""
+    probs, boxes = _req(probs, name="probs"), _req(boxes, name="boxes")
+    gt_masks = _req(gt_masks, torch.uint8, "gt_masks")
+    d = probs.shape[0]
+    if tuple(probs.shape[1:]) not in ((1, 28, 28), (28, 28)) or tuple(boxes.shape) != (d, 4):
+        raise ValueError("mask_inter: probs must be [D,1,28,28] or [D,28,28] and boxes [D,4]")
+    if gt_masks.dim() != 3:
+        raise ValueError("mask_inter: gt_masks must be uint8 [G,H,W]")
+    g, h, w = (int(s) for s in gt_masks.shape)
+    if h * w >= 2 ** 31:
+        raise ValueError("mask_inter: H*W must stay below 2^31")
+    inter = torch.empty((d, g), dtype=torch.int32, device=probs.device)
+    area = torch.empty((d,), dtype=torch.int32, device=probs.device)
+    if d:
+        _native.check(_native.lib().seam_mask_inter_f32(_ptr(probs), _ptr(boxes), d, _ptr(gt_masks) if g else None, g, h, w,
+                                                        _ptr(inter) if g else None, _ptr(area), _stream()),
+                      "seam_mask_inter_f32")
+    return inter, area
+
+
 def mask_select(logits: torch.Tensor, labels: torch.Tensor, ncls: int) -> torch.Tensor:
     """logits [K,14,14,4*ncls] (sub-pixel groups) -> sigmoid prob of channel labels[k]: [K,1,28,28]."""
     logits = _req_fp(logits)
