@@ -868,6 +868,34 @@ int seam_conv3x3s2_dgrad_f32(const float* dy, const float* w_packed, const float
 int seam_relu_mask_add_f32(const float* y, const float* a, const float* b, float* out, int64_t M, int C, seam_stream_t stream);
 int seam_maxpool3s2_relu_bwd_f32(const float* y, const float* dpool, float* dy, int N, int H, int W, int C, seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Ground-truth masks from annotations, csrc/seam_masks.hip: COCO-style polygon lists and RLE counts rasterised into the
+ * uint8 0/1 [n,H,W] stacks that the mask loss and the segm AP read (ref datasets/DF2Dataset.py:152-155: annToMask on the CPU,
+ * then n*H*W bytes over the bus).  One call serves a batch of n objects from images of different sizes; object o's [h,w]
+ * bytes go to out + obj_out_off[o] (int64 byte offsets), obj_hw int32 [n][2] = (h, w), 1 <= h, w <= 16384.  Every byte of
+ * every object is written (nothing relies on a zeroed `out`); nothing is allocated, nothing synchronises.  The arithmetic
+ * restates maskApi.c's rleFrPoly / rleMerge / rleDecode (float64, multiply and add kept apart); two calls give the same bits.
+ * Not pinned against pycocotools itself.
+ *
+ * seam_poly_masks_u8: P polygon parts with V vertices in all.  pts int32 [V][2]: the vertices upsampled by 5 on the host,
+ *   (int)(5*x + 0.5), (int)(5*y + 0.5), the ring NOT closed; part_off int32 [P+1]: CSR of the parts over the vertices;
+ *   part_obj int32 [P]: each part's object, non-decreasing (an object's parts are adjacent; an object without parts is zeros);
+ *   edge_pt_off int32 [V+1]: running sum of max(|dx|,|dy|) + 1 over the ring edges (vertex e -> vertex e+1, a part's last
+ *   vertex back to its first), T = edge_pt_off[V] < 2^31 points in all; part_ws_off int64 [P+1]: running sum, in 32-bit words,
+ *   of seam_poly_masks_ws_bytes(h, w) / 4 over the parts; ws: ws_bytes = 4 * part_ws_off[P] bytes, cleared by the call.
+ *   An object is the union of its parts.  All tables are DEVICE arrays.
+ * seam_poly_masks_ws_bytes: bytes of one part's bitmap on an h x w image, 4 * w * ceil((h+1)/32); 0 for a size out of range.
+ * seam_rle_masks_u8: run_start int32: per object the exclusive running sum of its RLE counts (column-major runs of 0 and 1
+ *   alternating, the first a run of zeros; a zero-length run repeats a start); obj_run_off int32 [n+1]: CSR of the objects over
+ *   the runs.  A pixel's value is (index of the last run starting at or before its column-major position) & 1.
+ * Refused, nothing launched or written: a negative count, a NULL table that the counts make necessary, ws_bytes % 4. */
+int64_t seam_poly_masks_ws_bytes(int h, int w);
+int seam_poly_masks_u8(const int* pts, const int* part_off, const int* part_obj, const int* edge_pt_off,
+                       const int64_t* part_ws_off, const int* obj_hw, const int64_t* obj_out_off, uint8_t* out, void* ws,
+                       int64_t ws_bytes, int P, int V, int T, int n, seam_stream_t stream);
+int seam_rle_masks_u8(const int* run_start, const int* obj_run_off, const int* obj_hw, const int64_t* obj_out_off,
+                      uint8_t* out, int n, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,9 @@ SIGNATURES = {
     "seam_conv3x3s2_dgrad_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "seam_relu_mask_add_f32": (_i, [_p, _p, _p, _p, _i64, _i, _p]),
     "seam_maxpool3s2_relu_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "seam_poly_masks_ws_bytes": (_i64, [_i, _i]),
+    "seam_poly_masks_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "seam_rle_masks_u8": (_i, [_p, _p, _p, _p, _p, _i, _p]),
 }
 
 _lib = None

@@ -1,0 +1,251 @@
+// seam_masks.hip -- ground-truth masks on the device: COCO-style `segmentation` entries (polygon lists, RLE counts) rasterised
+// into the uint8 [n,H,W] stacks that the mask loss and the segm AP read (ref datasets/DF2Dataset.py:152-155 builds them on the CPU
+// with pycocotools' annToMask and copies n*H*W bytes per image).  The arithmetic restates maskApi.c's rleFrPoly / rleMerge /
+// rleDecode operation for operation: vertices upsampled by 5 (on the host), every integer point of every edge in float64 with the
+// multiply and the add kept apart, a crossing wherever the upsampled x changes onto a pixel centre, then a parity fill.
+//
+// Polygons, three kernels over a whole batch of objects (images of different sizes in one call):
+//   toggle  one thread per emitted boundary point: finds its edge by binary search in the cumulative point table, recomputes the
+//           point and its predecessor in closed form from the edge's integer ends, and flips bit y of column x of its part's
+//           bitmap with an integer atomicXor (order-independent: two launches give the same bits; no float atomic anywhere).
+//   scan    prefix-XOR down every column, inside each 32-bit word and carried across words: toggles become the packed mask.
+//           Every image column carries an even number of crossings (tests/test_mask_refs_host.py pins that), so filling each
+//           column on its own equals maskApi.c's fill of the sorted column-major positions.
+//   expand  OR over the object's parts, one byte per pixel, row-major: a wave per row, 8 bytes per lane per store.
+// A part's bitmap is [ceil((h+1)/32)][w] words (bit r&31 of word [r>>5][c]): rows 0..h, row h taking the crossings clamped to h;
+// words of one row band lie along c, so the scan's and the expand's lanes read consecutive words.
+// RLE: one kernel; a pixel binary-searches its column-major index in the object's run starts, its value is the run index & 1.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#pragma STDC FP_CONTRACT OFF
+
+namespace {
+
+constexpr int MAX_SIDE = 16384;
+
+// largest i in [lo, hi) with tab[i] <= key; tab is non-decreasing and tab[lo] <= key
+__device__ __forceinline__ int last_le(const int* __restrict__ tab, int lo, int hi, int64_t key) {
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (tab[mid] <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// first i in [0, n] with tab[i] >= key (n if none)
+__device__ __forceinline__ int first_ge(const int* __restrict__ tab, int n, int key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (tab[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct Pt { int u, v; };
+
+// point `idx` (0 .. max(dx,dy)) of the edge (xs,ys) -> (xe,ye), counted from the edge's start (rleFrPoly's second loop).
+// s*t is rounded to double before the add: a fused multiply-add rounds the half cases (s = 1/6, t = 3) the other way.  Plain
+// operators under FP_CONTRACT OFF give that; HIP's __dmul_rn / __dadd_rn do NOT (they are inline `a * b` / `a + b` compiled
+// under the header's contraction mode, and hipcc fuses them into v_fma_f64).
+__device__ __forceinline__ Pt edge_point(int xs, int ys, int xe, int ye, int idx) {
+    const int64_t dx = llabs((int64_t)xe - xs), dy = llabs((int64_t)ye - ys);
+    const bool wide = dx >= dy;
+    const bool flip = wide ? xs > xe : ys > ye;
+    if (flip) {
+        int t = xs; xs = xe; xe = t;
+        t = ys; ys = ye; ye = t;
+    }
+    const int64_t len = wide ? dx : dy;
+    Pt p;
+    if (len == 0) {                       // zero-length edge: 0/0 in C; its v is never read (both neighbours share its u)
+        p.u = xs; p.v = ys;
+        return p;
+    }
+    const int64_t t = flip ? len - idx : idx;
+    if (wide) {
+        const double s = (double)((int64_t)ye - ys) / (double)dx;
+        const double st = s * (double)t;
+        p.u = (int)(t + xs);
+        p.v = (int)((double)ys + st + 0.5);
+    } else {
+        const double s = (double)((int64_t)xe - xs) / (double)dy;
+        const double st = s * (double)t;
+        p.v = (int)(t + ys);
+        p.u = (int)((double)xs + st + 0.5);
+    }
+    return p;
+}
+
+// point `idx` of ring edge e of the part whose vertices are [v0, v1): vertex e -> vertex e+1, the last edge back to v0
+__device__ __forceinline__ Pt ring_point(const int* __restrict__ pts, int v0, int v1, int e, int idx) {
+    const int e1 = e + 1 < v1 ? e + 1 : v0;
+    return edge_point(pts[2 * e], pts[2 * e + 1], pts[2 * e1], pts[2 * e1 + 1], idx);
+}
+
+__global__ void poly_toggle_kernel(const int* __restrict__ pts, const int* __restrict__ part_off, const int* __restrict__ part_obj,
+                                   const int* __restrict__ edge_pt_off, const int64_t* __restrict__ part_ws_off,
+                                   const int* __restrict__ obj_hw, uint32_t* __restrict__ ws, int64_t ws_words, int P, int V, int T) {
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < T; g += (int64_t)gridDim.x * blockDim.x) {
+        const int e = last_le(edge_pt_off, 0, V, g);
+        const int p = last_le(part_off, 0, P, e);
+        const int v0 = part_off[p], v1 = part_off[p + 1];
+        const int first = edge_pt_off[e];
+        if (e == v0 && g == first) continue;                         // the ring's first point has no predecessor
+        const Pt b = ring_point(pts, v0, v1, e, (int)(g - first));
+        const Pt a = g > first ? ring_point(pts, v0, v1, e, (int)(g - first) - 1)
+                               : ring_point(pts, v0, v1, e - 1, first - 1 - edge_pt_off[e - 1]);
+        if (a.u == b.u) continue;
+        const int o = part_obj[p];
+        const int h = obj_hw[2 * o], w = obj_hw[2 * o + 1];
+        double xd = (double)(b.u < a.u ? b.u : b.u - 1);
+        xd = (xd + 0.5) / 5.0 - 0.5;
+        if (floor(xd) != xd || xd < 0.0 || xd > (double)(w - 1)) continue;
+        double yd = (double)(b.v < a.v ? b.v : a.v);
+        yd = (yd + 0.5) / 5.0 - 0.5;
+        if (yd < 0.0) yd = 0.0; else if (yd > (double)h) yd = (double)h;
+        const int x = (int)xd, y = (int)ceil(yd);
+        const int64_t word = part_ws_off[p] + (int64_t)(y >> 5) * w + x;
+        if (word < ws_words) atomicXor(ws + word, 1u << (y & 31));
+    }
+}
+
+__global__ void poly_scan_kernel(const int* __restrict__ part_obj, const int64_t* __restrict__ part_ws_off,
+                                 const int* __restrict__ obj_hw, uint32_t* __restrict__ ws, int64_t ws_words, int P) {
+    for (int p = blockIdx.y; p < P; p += gridDim.y) {
+        const int o = part_obj[p];
+        const int h = obj_hw[2 * o], w = obj_hw[2 * o + 1];
+        const int bands = (h + 32) >> 5;                             // ceil((h + 1) / 32)
+        const int64_t base = part_ws_off[p];
+        if (base + (int64_t)bands * w > ws_words) continue;
+        for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < w; c += gridDim.x * blockDim.x) {
+            uint32_t carry = 0;
+            for (int k = 0; k < bands; ++k) {
+                uint32_t x = ws[base + (int64_t)k * w + c];
+                x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
+                x ^= carry;
+                ws[base + (int64_t)k * w + c] = x;
+                carry = 0u - (x >> 31);
+            }
+        }
+    }
+}
+
+// Writes an object's [h,w] bytes row by row: a wave takes one row per pass and its lanes consecutive 8-byte-aligned chunks of the
+// row's address range, stored whole; the chunks cut by the row's first and last byte are stored byte by byte, so any output
+// offset and any w work.  row(r, c, n) returns the bytes of pixels (r, c .. c+n-1), n <= 8, pixel c + k in byte k.
+template <class Row>
+__device__ __forceinline__ void write_object(uint8_t* __restrict__ dst, int h, int w, Row row) {
+    const int lane = threadIdx.x & 63, rows_per_pass = blockDim.x >> 6;
+    for (int r = blockIdx.x * rows_per_pass + (threadIdx.x >> 6); r < h; r += gridDim.x * rows_per_pass) {
+        uint8_t* rp = dst + (int64_t)r * w;
+        const int head = (int)((uintptr_t)rp & 7);
+        const int chunks = (w + head + 7) >> 3;
+        for (int q = lane; q < chunks; q += 64) {
+            const int i0 = q * 8 - head;
+            const int lo = i0 < 0 ? 0 : i0, hi = i0 + 8 < w ? i0 + 8 : w;
+            const uint64_t pack = row(r, lo, hi - lo);
+            if (hi - lo == 8) {
+                *reinterpret_cast<uint64_t*>(rp + lo) = pack;
+            } else {
+                for (int k = 0; k < hi - lo; ++k) rp[lo + k] = (uint8_t)(pack >> (8 * k));
+            }
+        }
+    }
+}
+
+__global__ void poly_expand_kernel(const int* __restrict__ part_obj, const int64_t* __restrict__ part_ws_off,
+                                   const int* __restrict__ obj_hw, const int64_t* __restrict__ obj_out_off,
+                                   const uint32_t* __restrict__ ws, int64_t ws_words, uint8_t* __restrict__ out, int P, int n) {
+    for (int o = blockIdx.y; o < n; o += gridDim.y) {
+        const int h = obj_hw[2 * o], w = obj_hw[2 * o + 1];
+        const int p0 = first_ge(part_obj, P, o);
+        int p1 = first_ge(part_obj, P, o + 1);
+        const int bands = (h + 32) >> 5;
+        while (p1 > p0 && part_ws_off[p1 - 1] + (int64_t)bands * w > ws_words) --p1;    // never read past the workspace
+        write_object(out + obj_out_off[o], h, w, [&](int r, int c, int m) -> uint64_t {
+            uint32_t wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int p = p0; p < p1; ++p) {
+                const uint32_t* src = ws + part_ws_off[p] + (int64_t)(r >> 5) * w + c;
+                if (m == 8) {                                    // the 8 columns' words: 32 contiguous bytes, dword-aligned
+                    uint32_t t[8];
+                    __builtin_memcpy(t, src, 32);
+                    for (int k = 0; k < 8; ++k) wd[k] |= t[k];
+                } else {
+                    for (int k = 0; k < m; ++k) wd[k] |= src[k];
+                }
+            }
+            uint64_t pack = 0;
+            for (int k = 0; k < 8; ++k) pack |= (uint64_t)((wd[k] >> (r & 31)) & 1u) << (8 * k);
+            return pack;
+        });
+    }
+}
+
+__global__ void rle_expand_kernel(const int* __restrict__ run_start, const int* __restrict__ obj_run_off,
+                                  const int* __restrict__ obj_hw, const int64_t* __restrict__ obj_out_off,
+                                  uint8_t* __restrict__ out, int n) {
+    for (int o = blockIdx.y; o < n; o += gridDim.y) {
+        const int h = obj_hw[2 * o], w = obj_hw[2 * o + 1];
+        const int r0 = obj_run_off[o], r1 = obj_run_off[o + 1];
+        write_object(out + obj_out_off[o], h, w, [&](int r, int c, int m) -> uint64_t {
+            uint64_t pack = 0;
+            if (r1 <= r0) return pack;
+            for (int k = 0; k < m; ++k)
+                pack |= (uint64_t)((last_le(run_start, r0, r1, (int64_t)(c + k) * h + r) - r0) & 1) << (8 * k);
+            return pack;
+        });
+    }
+}
+
+inline dim3 object_grid(int n) { return dim3(64, (unsigned)(n < 65535 ? n : 65535)); }
+
+}  // namespace
+
+extern "C" {
+
+// words * 4 of one part's bitmap on an h x w image
+int64_t seam_poly_masks_ws_bytes(int h, int w) {
+    if (h <= 0 || w <= 0 || h > MAX_SIDE || w > MAX_SIDE) return 0;
+    return (int64_t)((h + 32) >> 5) * w * 4;
+}
+
+int seam_poly_masks_u8(const int* pts, const int* part_off, const int* part_obj, const int* edge_pt_off,
+                       const int64_t* part_ws_off, const int* obj_hw, const int64_t* obj_out_off, uint8_t* out, void* ws,
+                       int64_t ws_bytes, int P, int V, int T, int n, void* stream) {
+    if (P < 0 || V < 0 || T < 0 || n < 0 || ws_bytes < 0 || (ws_bytes & 3)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!obj_hw || !obj_out_off || !out) return (int)hipErrorInvalidValue;
+    if (P > 0 && (!part_off || !part_obj || !part_ws_off || !ws || ws_bytes == 0)) return (int)hipErrorInvalidValue;
+    if (T > 0 && (P == 0 || V == 0 || T < V || !pts || !edge_pt_off)) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t ws_words = ws_bytes >> 2;
+    if (P > 0) {
+        hipError_t rc = hipMemsetAsync(ws, 0, (size_t)ws_bytes, s);
+        if (rc != hipSuccess) return (int)rc;
+        if (T > 0) {
+            int grid = (T + 255) / 256;
+            if (grid > 4096) grid = 4096;
+            hipLaunchKernelGGL(poly_toggle_kernel, dim3(grid), dim3(256), 0, s, pts, part_off, part_obj, edge_pt_off, part_ws_off,
+                               obj_hw, (uint32_t*)ws, ws_words, P, V, T);
+        }
+        hipLaunchKernelGGL(poly_scan_kernel, dim3(8, (unsigned)(P < 65535 ? P : 65535)), dim3(256), 0, s, part_obj, part_ws_off,
+                           obj_hw, (uint32_t*)ws, ws_words, P);
+    }
+    hipLaunchKernelGGL(poly_expand_kernel, object_grid(n), dim3(256), 0, s, part_obj, part_ws_off, obj_hw, obj_out_off,
+                       (const uint32_t*)ws, ws_words, out, P, n);
+    return (int)hipGetLastError();
+}
+
+int seam_rle_masks_u8(const int* run_start, const int* obj_run_off, const int* obj_hw, const int64_t* obj_out_off, uint8_t* out,
+                      int n, void* stream) {
+    if (n < 0) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!run_start || !obj_run_off || !obj_hw || !obj_out_off || !out) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(rle_expand_kernel, object_grid(n), dim3(256), 0, (hipStream_t)stream, run_start, obj_run_off, obj_hw,
+                       obj_out_off, out, n);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1708,3 +1708,224 @@ def conv3x3s2_dgrad(dy: torch.Tensor, pk: PackedS2Dgrad, hw: Sequence[int], mask
     for i in range(0, n, step):
         _conv3x3s2_dgrad_one(dy[i:i + step], pk, (h, w), None if mask is None else mask[i:i + step], out[i:i + step])
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- ground-truth masks (csrc/seam_masks.hip)
+MASK_MAX_SIDE = 16384              # h, w of an image whose annotations are rasterised
+MASK_MAX_POINTS = 2 ** 31          # boundary points of one poly_masks call (32-bit thread index), exclusive
+
+
+@dataclass
+class MaskLayout:
+    """Where every object's [h,w] bytes lie in the flat uint8 buffer of a batch: image after image, an image's objects adjacent,
+    so that image i's stack is the view ``flat[img_off[i]:img_off[i+1]].view(n_i, H_i, W_i)``."""
+    counts: list                   # objects per image
+    sizes: list                    # (h, w) per image
+    obj_hw: object                 # int32 [n,2]
+    obj_off: object                # int64 [n] byte offsets
+    img_off: list                  # len(images) + 1 byte offsets
+
+    @property
+    def total(self) -> int:
+        return self.img_off[-1]
+
+
+def mask_layout(counts: Sequence[int], sizes: Sequence[Sequence[int]]) -> MaskLayout:
+    import numpy as np
+    if len(counts) != len(sizes):
+        raise ValueError(f"masks: {len(counts)} images but {len(sizes)} sizes")
+    hw, off, img_off, pos = [], [], [0], 0
+    for i, (n, size) in enumerate(zip(counts, sizes)):
+        h, w = (int(size[0]), int(size[1])) if len(size) == 2 else (0, 0)
+        if len(size) != 2 or h != size[0] or w != size[1] or not (1 <= h <= MASK_MAX_SIDE and 1 <= w <= MASK_MAX_SIDE):
+            raise ValueError(f"masks: image {i}: size {tuple(size)} must be (h, w) with 1 <= h, w <= {MASK_MAX_SIDE}")
+        for _ in range(n):
+            hw.append((h, w))
+            off.append(pos)
+            pos += h * w
+        img_off.append(pos)
+    return MaskLayout(list(counts), [(int(s[0]), int(s[1])) for s in sizes], np.asarray(hw, np.int32).reshape(-1, 2),
+                      np.asarray(off, np.int64), img_off)
+
+
+def mask_views(flat: torch.Tensor, lay: MaskLayout) -> list:
+    return [flat[lay.img_off[i]:lay.img_off[i + 1]].view(n, h, w) for i, (n, (h, w)) in enumerate(zip(lay.counts, lay.sizes))]
+
+
+def _selected(objs_per_image):
+    """(image, object, flat object index, entry) of every entry that is not None."""
+    out, k = [], 0
+    for i, objs in enumerate(objs_per_image):
+        for j, o in enumerate(objs):
+            if o is not None:
+                out.append((i, j, k, o))
+            k += 1
+    return out
+
+
+def pack_poly_masks(polys: Sequence[Sequence], sizes: Sequence[Sequence[int]]):
+    """Host packing of ``seam_poly_masks_u8``: ``polys[i][j]`` is object j of image i as a list of parts, each a flat
+    ``[x0, y0, x1, y1, ...]`` sequence (an empty list: an object of zero parts, all zeros; None: not a polygon object, skipped).
+    Returns (layout, tables): the int32 / int64 NumPy tables of include/seam_hip.h, the vertices upsampled in float64 as
+    ``trunc(5*x + 0.5)``.  Raises ValueError, naming the object, for an odd-length or empty part, a coordinate that is not
+    finite or with ``|5x + 0.5| >= 2^31``, and for ``MASK_MAX_POINTS`` boundary points or more."""
+    import numpy as np
+    lay = mask_layout([len(o) for o in polys], sizes)
+    flat_xy, names, part_len, part_obj, part_words, sel_obj = [], [], [], [], [], []
+    words_of = {}
+    for i, j, k, parts in _selected(polys):
+        h, w = lay.sizes[i]
+        if (h, w) not in words_of:
+            words_of[(h, w)] = int(_native.lib().seam_poly_masks_ws_bytes(h, w)) // 4
+        for q, part in enumerate(parts):
+            what = f"poly_masks: image {i} object {j} part {q}"
+            try:
+                xy = np.asarray(part, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{what}: not a sequence of numbers") from e
+            if xy.ndim != 1 or xy.size == 0 or xy.size % 2:
+                raise ValueError(f"{what}: expected a flat, non-empty [x0, y0, x1, y1, ...] of even length, got shape {xy.shape}")
+            flat_xy.append(xy)
+            names.append(what)
+            part_len.append(xy.size // 2)
+            part_obj.append(len(sel_obj))
+            part_words.append(words_of[(h, w)])
+        sel_obj.append(k)
+    P = len(part_len)
+    part_len = np.asarray(part_len, np.int64)
+    part_off = np.zeros(P + 1, np.int64)
+    np.cumsum(part_len, out=part_off[1:])
+    V = int(part_off[-1])
+    up = 5.0 * (np.concatenate(flat_xy) if P else np.zeros(0))
+    up = up + 0.5                                               # the multiply and the add stay apart, as (int)(5*x + 0.5) has them
+    bad = ~(np.abs(up) < 2.0 ** 31)                             # also true for NaN
+    if bad.any():
+        at = int(np.flatnonzero(bad)[0])
+        who = names[int(np.searchsorted(part_off, at // 2, side="right")) - 1]
+        raise ValueError(f"{who}: a coordinate is not finite" if not np.isfinite(up[at]) else f"{who}: |5x + 0.5| must stay below 2^31")
+    allp = np.trunc(up).astype(np.int64).reshape(-1, 2)
+    nxt = np.arange(V, dtype=np.int64) + 1                      # ring successor of every vertex
+    nxt[part_off[1:] - 1] = part_off[:-1]
+    step = np.abs(allp[nxt] - allp)
+    edge_pts = np.maximum(step[:, 0], step[:, 1]) + 1
+    edge_pt_off = np.zeros(V + 1, np.int64)
+    np.cumsum(edge_pts, out=edge_pt_off[1:])
+    T = int(edge_pt_off[-1])
+    if T >= MASK_MAX_POINTS:
+        raise ValueError(f"poly_masks: {T} boundary points in one call, the limit is {MASK_MAX_POINTS} (split the batch)")
+    part_ws_off = np.zeros(P + 1, np.int64)
+    np.cumsum(part_words, out=part_ws_off[1:])
+    sel = np.asarray(sel_obj, np.int64)
+    tables = dict(pts=allp.astype(np.int32), part_off=part_off.astype(np.int32), part_obj=np.asarray(part_obj, np.int32),
+                  edge_pt_off=edge_pt_off.astype(np.int32), part_ws_off=part_ws_off, obj_hw=np.ascontiguousarray(lay.obj_hw[sel]),
+                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), P=P, V=V, T=T, n=len(sel_obj))
+    return lay, tables
+
+
+def pack_rle_masks(rles: Sequence[Sequence], sizes: Sequence[Sequence[int]]):
+    """Host packing of ``seam_rle_masks_u8``: ``rles[i][j]`` is object j of image i as its uncompressed counts (runs of 0 and 1
+    alternating in column-major order, the first a run of zeros; None: not an RLE object, skipped).  Raises ValueError, naming
+    the object, for counts that are negative, not integers, or do not sum to h*w."""
+    import numpy as np
+    lay = mask_layout([len(o) for o in rles], sizes)
+    starts, run_off, sel_obj = [], [0], []
+    for i, j, k, counts in _selected(rles):
+        what = f"image {i} object {j}"
+        h, w = lay.sizes[i]
+        try:
+            raw = np.asarray(counts)
+            c = raw.astype(np.int64)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"rle_masks: {what}: counts are not a sequence of integers") from e
+        if c.ndim != 1 or c.size == 0 or not (raw == c).all():
+            raise ValueError(f"rle_masks: {what}: counts must be a flat, non-empty sequence of integers")
+        if (c < 0).any() or int(c.sum()) != h * w:
+            raise ValueError(f"rle_masks: {what}: counts must be non-negative and sum to h*w = {h * w}, got sum {int(c.sum())}")
+        starts.append(np.cumsum(c) - c)
+        run_off.append(run_off[-1] + c.size)
+        sel_obj.append(k)
+    if run_off[-1] >= 2 ** 31:
+        raise ValueError("rle_masks: 2^31 runs or more in one call (split the batch)")
+    sel = np.asarray(sel_obj, np.int64)
+    tables = dict(run_start=(np.concatenate(starts) if starts else np.zeros(0, np.int64)).astype(np.int32),
+                  obj_run_off=np.asarray(run_off, np.int32), obj_hw=np.ascontiguousarray(lay.obj_hw[sel]),
+                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), n=len(sel_obj))
+    return lay, tables
+
+
+def _mask_device(device) -> torch.device:
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _native.SeamNativeError("masks are rasterised on the HIP device (no CPU path exists)")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _upload_tables(tables: dict, names, device) -> dict:
+    """One host-to-device copy for all tables of a call: the int64 ones first (8-byte alignment), everything as int32 words."""
+    import numpy as np
+    names = sorted(names, key=lambda k: -tables[k].dtype.itemsize)
+    words = [np.ascontiguousarray(tables[k]).reshape(-1).view(np.int32) for k in names]
+    dev = torch.from_numpy(np.concatenate(words)).to(device)
+    out, pos = {}, 0
+    for k, wd in zip(names, words):
+        t = dev[pos:pos + wd.size]
+        out[k] = t.view(torch.int64) if tables[k].dtype.itemsize == 8 else t
+        pos += wd.size
+    return out
+
+
+def mask_flat(lay: MaskLayout, device, flat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The flat uint8 buffer of a batch's masks on ``device``: allocated (uninitialised), or ``flat`` checked against the layout."""
+    device = _mask_device(device)
+    if flat is None:
+        return torch.empty((lay.total,), dtype=torch.uint8, device=device)
+    flat = _req(flat, torch.uint8, "flat")
+    if flat.dim() != 1 or flat.numel() != lay.total or flat.device != device:
+        raise ValueError(f"masks: flat must be a uint8 [{lay.total}] tensor on {device}")
+    return flat
+
+
+def launch_poly_masks(lay: MaskLayout, t: dict, device, flat: Optional[torch.Tensor] = None) -> list:
+    """``seam_poly_masks_u8`` over the tables of ``pack_poly_masks``: one upload, one launch sequence.  ``flat``: the batch's
+    flat buffer when another producer fills the objects that were None in the packing; allocated here otherwise."""
+    device = _mask_device(device)
+    flat = mask_flat(lay, device, flat)
+    if t["n"]:
+        names = ("pts", "part_off", "part_obj", "edge_pt_off", "part_ws_off", "obj_hw", "obj_out_off")
+        d = _upload_tables(t, names, device)
+        ws_bytes = 4 * int(t["part_ws_off"][-1])
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        p = [_ptr(d[k]) if d[k].numel() else None for k in names]
+        with torch.cuda.device(device):
+            _native.check(_native.lib().seam_poly_masks_u8(*p, _ptr(flat), _ptr(ws) if ws_bytes else None, ws_bytes, t["P"], t["V"],
+                                                           t["T"], t["n"], _stream()), "seam_poly_masks_u8")
+    return mask_views(flat, lay)
+
+
+def launch_rle_masks(lay: MaskLayout, t: dict, device, flat: Optional[torch.Tensor] = None) -> list:
+    """``seam_rle_masks_u8`` over the tables of ``pack_rle_masks`` (``flat`` as in ``launch_poly_masks``)."""
+    device = _mask_device(device)
+    flat = mask_flat(lay, device, flat)
+    if t["n"]:
+        names = ("run_start", "obj_run_off", "obj_hw", "obj_out_off")
+        d = _upload_tables(t, names, device)
+        with torch.cuda.device(device):
+            _native.check(_native.lib().seam_rle_masks_u8(*[_ptr(d[k]) for k in names], _ptr(flat), t["n"], _stream()),
+                          "seam_rle_masks_u8")
+    return mask_views(flat, lay)
+
+
+def poly_masks(polys: Sequence[Sequence], sizes: Sequence[Sequence[int]], device) -> list:
+    """Polygon annotations of a batch of images -> list of uint8 0/1 [n_i,H_i,W_i] device stacks (views of one flat buffer), one
+    table upload and one launch sequence for the batch; arguments and errors as ``pack_poly_masks``, no object may be None."""
+    if any(o is None for img in polys for o in img):
+        raise ValueError("poly_masks: every object needs a list of parts")
+    return launch_poly_masks(*pack_poly_masks(polys, sizes), device)
+
+
+def rle_masks(rles: Sequence[Sequence], sizes: Sequence[Sequence[int]], device) -> list:
+    """Uncompressed RLE annotations of a batch of images -> list of uint8 0/1 [n_i,H_i,W_i] device stacks; arguments and errors
+    as ``pack_rle_masks``, no object may be None."""
+    if any(o is None for img in rles for o in img):
+        raise ValueError("rle_masks: every object needs its counts")
+    return launch_rle_masks(*pack_rle_masks(rles, sizes), device)
