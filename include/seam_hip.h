@@ -896,6 +896,48 @@ int seam_poly_masks_u8(const int* pts, const int* part_off, const int* part_obj,
 int seam_rle_masks_u8(const int* run_start, const int* obj_run_off, const int* obj_hw, const int64_t* obj_out_off,
                       uint8_t* out, int n, seam_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Masks to COCO run-length encoding, csrc/seam_rle.hip: maskApi.c's rleEncode, the opposite direction of the block above.
+ * The mask is flattened COLUMN-MAJOR (position p = x*h + y); runs of 0 and 1 alternate, the first a run of zeros.  What the
+ * device produces, per object, is the ascending list of positions p with v(p) != v(p-1), v(-1) = 0 (the pixel before (0, x)
+ * is (h-1, x-1): a run goes on from the bottom of one column into the top of the next); counts = diff([0, positions, h*w]).
+ * A pixel is set iff its byte is non-zero, this project's rule everywhere -- pycocotools' rleEncode compares each byte with
+ * its predecessor instead, so it agrees for bytes 0/1 only.
+ *
+ * An object's workspace is seam_rle_encode_ws_bytes(h, w) = 4 * w * ceil(h/32) bytes (0 for a refused size): one 32-bit word
+ * per "cell" of 32 rows x 1 column.  A call works on `cells` = the sum over its objects, object o's first cell at
+ * obj_cell_off[o] (the running sum, in cells); ws and counts both hold ws_bytes = 4 * cells bytes and both are cleared by the
+ * encode call.  Two steps with the caller's prefix sum between them:
+ *   seam_rle_encode_*   ws <- packed value bits, every pixel read (or, for detections, evaluated) exactly once;
+ *                       counts int32 [cells] <- transitions per cell, an object's cells in column-major order (column, band).
+ *   scan int64 [cells]  the INCLUSIVE prefix sum of counts over the whole table (the caller's: a torch cumsum will do).
+ *                       scan[obj_cell_off[o+1] - 1] is the end of object o's positions: the CSR of the result.
+ *   seam_rle_positions_* positions int32 [capacity] <- every transition's p at its scanned slot, each slot written once at a
+ *                       computed offset.  capacity >= scan[cells-1]; a slot past it is not written.  capacity == 0: no-op.
+ * No atomics, no float arithmetic but paste_value's: two calls give identical bytes.  Nothing is allocated, nothing synchronises.
+ *
+ * _masks: n dense objects, object o the row-major uint8 [h,w] at masks + obj_off[o] (int64 byte offsets, any alignment, the
+ *   layout seam_poly_masks_u8 / seam_rle_masks_u8 write; masks holds mask_bytes bytes, an object reaching past them is
+ *   skipped).  obj_hw int32 [n][2], obj_off, obj_cell_off are DEVICE tables; obj_hw_host is the same [n][2] table in HOST
+ *   memory, read by the launcher to check the shapes and to size the grid.
+ * _paste: the D detections of one H x W image, probs [D,28,28], boxes [D,4] xyxy (16-byte aligned): the mask of detection d is
+ *   {seam_paste_masks_f32's value > 0.5f}, bit for bit (one device function, csrc/seam_paste.h), the set seam_mask_inter_f32
+ *   counts.  Only the clipped integer box is visited; a box that misses the image has no transition.  Object d's cells start
+ *   at d * ws_bytes(H, W) / 4.
+ * Refused with a non-zero return, nothing launched or written: a NULL pointer (positions may be NULL when capacity == 0), a
+ * negative count or size, ws_bytes % 4 or smaller than the objects need, h or w outside 1..16384, h*w >= 2^31.
+ * n == 0 / D == 0: no-op, returns 0. */
+int64_t seam_rle_encode_ws_bytes(int h, int w);
+int seam_rle_encode_masks_u8(const uint8_t* masks, int64_t mask_bytes, const int* obj_hw_host, const int* obj_hw,
+                             const int64_t* obj_off, const int64_t* obj_cell_off, void* ws, int64_t ws_bytes, int* counts, int n,
+                             seam_stream_t stream);
+int seam_rle_encode_paste_f32(const float* probs, const float* boxes, int D, int H, int W, void* ws, int64_t ws_bytes,
+                              int* counts, seam_stream_t stream);
+int seam_rle_positions_masks(const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off, const void* ws,
+                             int64_t ws_bytes, const int64_t* scan, int* positions, int64_t capacity, int n, seam_stream_t stream);
+int seam_rle_positions_paste(int D, int H, int W, const void* ws, int64_t ws_bytes, const int64_t* scan, int* positions,
+                             int64_t capacity, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

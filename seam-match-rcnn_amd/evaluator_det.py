@@ -5,6 +5,8 @@ The reference has no detector evaluation (its evaluators measure retrieval only)
 is a dependency here, so the protocol is restated in this file from the published COCO procedure (``COCOeval.evaluateImg``
 / ``accumulate`` / ``summarize``).  It has NOT been pinned against pycocotools itself: the tests pin it against an
 independent float64 restatement (tests/det_eval_refs.py) and against hand-checked known answers.
+``coco_results`` writes a run's detections as the entries of a COCO results file (boxes as xywh, masks as compressed RLE encoded on
+the device): with it, a machine that has pycocotools can make that comparison.
 
 Where the work runs:
 
@@ -70,9 +72,10 @@ def _xywh(boxes: np.ndarray):
             (b[:, 2] - b[:, 0]).astype(np.float64), (b[:, 3] - b[:, 1]).astype(np.float64))
 
 
-def _box_iou(det: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
-    dx, dy, dw, dh = (v[:, None] for v in _xywh(det))
-    gx, gy, gw, gh = (v[None, :] for v in _xywh(gt))
+def _box_iou_xywh(dx, dy, dw, dh, gx, gy, gw, gh, crowd: np.ndarray) -> np.ndarray:
+    """pycocotools' ``bbIou`` on float64 x, y, w, h columns: [D] against [G] -> [D,G]."""
+    dx, dy, dw, dh = (np.asarray(v, dtype=np.float64)[:, None] for v in (dx, dy, dw, dh))
+    gx, gy, gw, gh = (np.asarray(v, dtype=np.float64)[None, :] for v in (gx, gy, gw, gh))
     iw = np.minimum(dx + dw, gx + gw) - np.maximum(dx, gx)
     ih = np.minimum(dy + dh, gy + gh) - np.maximum(dy, gy)
     inter = iw * ih
@@ -80,6 +83,10 @@ def _box_iou(det: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     with np.errstate(divide="ignore", invalid="ignore"):
         iou = inter / union
     return np.where((iw <= 0) | (ih <= 0), 0.0, iou)
+
+
+def _box_iou(det: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    return _box_iou_xywh(*_xywh(det), *_xywh(gt), crowd)
 
 
 def _mask_iou(inter: np.ndarray, det_area: np.ndarray, gt_pix: np.ndarray, crowd: np.ndarray) -> np.ndarray:
@@ -279,6 +286,56 @@ class DetectionEvaluator:
                     print(f" {title:<18} ({kind}) @[ IoU={iou:<9} | area={AREA_NAMES[a]:>6s} | "
                           f"maxDets={self.max_dets[m]:>3d} ] = {s:0.3f}")
         return {t: list(self.stats[t]) for t in self.iou_types}
+
+
+def coco_results(outputs, image_ids, sizes, label_to_category=None, iou_types: Sequence[str] = ("bbox", "segm")) -> List[dict]:
+    """The detections of a batch as the entries of a COCO results file (what pycocotools' ``loadRes`` and the DeepFashion2
+    tooling read): per detection ``image_id``, ``category_id``, ``score`` and, by ``iou_types``, ``bbox`` = [x, y, w, h] (w and h
+    subtracted in fp32, as ``_xywh``) and ``segmentation`` = {"size": [h, w], "counts": <ascii str>}, the compressed RLE of the
+    mask thresholded at > 0.5.  ``outputs``: one dict per image as ``DetectionEvaluator.update`` takes them -- ``mask_probs``
+    (``model.paste_masks = False``) are encoded without a pasted mask (``mask_utils.encode_detections``), pasted ``masks``
+    [K,1,H,W] through ``mask_utils.encode``; ``sizes[i] = (h, w)`` of image i; ``label_to_category``: mapping (or sequence)
+    from the model's labels to the dataset's category ids, identity when None.  The list holds plain ``int``, ``float`` and
+    ``str`` only: ``json.dump(results, f)`` writes the file."""
+    from . import mask_utils
+    iou_types = tuple(iou_types)
+    if not iou_types or any(t not in ("bbox", "segm") for t in iou_types):
+        raise ValueError("iou_types must be drawn from 'bbox' and 'segm'")
+    outputs, image_ids, sizes = list(outputs), list(image_ids), list(sizes)
+    if not len(outputs) == len(image_ids) == len(sizes):
+        raise ValueError("one image id and one size per output dict are needed")
+    results = []
+    for out, image_id, size in zip(outputs, image_ids, sizes):
+        fetch = _HostFetch()
+        slots = {k: fetch.add(out[k]) for k in ("boxes", "labels", "scores")}
+        rles = None
+        if "segm" in iou_types:                                   # the encoder's copies first, then the image's one table copy
+            h, w = int(size[0]), int(size[1])
+            if "mask_probs" in out:
+                rles = mask_utils.encode_detections(out["mask_probs"], out["boxes"], (h, w))
+            else:
+                m = out["masks"]
+                m = m.reshape(m.shape[0], *m.shape[-2:])
+                if tuple(m.shape[1:]) != (h, w):
+                    raise ValueError(f"pasted masks of {tuple(m.shape[1:])} on an image of {(h, w)}")
+                rles = mask_utils.encode((m > 0.5).to(torch.uint8)) if m.shape[0] else []
+        fetch.run()
+        boxes = fetch.get(slots["boxes"]).reshape(-1, 4)
+        labels = fetch.get(slots["labels"]).reshape(-1).astype(np.int64)
+        scores = fetch.get(slots["scores"]).reshape(-1)
+        if not (len(labels) == len(scores) == len(boxes)) or (rles is not None and len(rles) != len(boxes)):
+            raise ValueError("boxes, labels, scores (and masks) of an image must have one row per detection")
+        x, y, bw, bh = _xywh(boxes)
+        image_id = image_id.item() if hasattr(image_id, "item") else image_id
+        for k in range(len(labels)):
+            cat = int(labels[k]) if label_to_category is None else label_to_category[int(labels[k])]
+            r = {"image_id": image_id, "category_id": int(cat), "score": float(scores[k])}
+            if "bbox" in iou_types:
+                r["bbox"] = [float(x[k]), float(y[k]), float(bw[k]), float(bh[k])]
+            if rles is not None:
+                r["segmentation"] = {"size": list(rles[k]["size"]), "counts": rles[k]["counts"].decode("ascii")}
+            results.append(r)
+    return results
 
 
 def evaluate(model, data_loader, device, iou_types: Sequence[str] = ("bbox", "segm"), verbose: bool = True,

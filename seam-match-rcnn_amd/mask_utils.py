@@ -1,5 +1,6 @@
-"""Ground-truth masks from COCO-style annotations, on the device: the counterpart of the reference's ``stuffs/mask_utils.py``
-(a wrapper over ``pycocotools._mask``), for what ``datasets/DF2Dataset.py:152-155`` does with it.
+"""COCO masks on the device, both directions: the counterpart of the reference's ``stuffs/mask_utils.py`` (a wrapper over
+``pycocotools._mask``).  Annotations -> masks is what ``datasets/DF2Dataset.py:152-155`` does with it; masks -> RLE is what a
+COCO results file needs (``evaluator_det.coco_results``).
 
 The reference rasterises every object on a dataloader worker and ships the uint8 ``[n,H,W]`` stack to the device each step
 (7.8 MB for 8 objects at 800 x 1216).  Here the annotations themselves go up -- a few KB of integers for a batch -- and
@@ -9,7 +10,12 @@ pycocotools itself, which is not installed where this project is tested (DESIGN.
 
 A ``segmentation`` entry is one of: a polygon list ``[[x0, y0, x1, y1, ...], ...]`` (several parts are merged), an uncompressed
 RLE ``{"counts": [..], "size": [h, w]}``, or a compressed RLE ``{"counts": "<string>", "size": [h, w]}``.
-Not here: ``encode``, ``area``, ``toBbox``, ``iou``.
+
+The other direction: ``encode`` (dense masks, NumPy or device) and ``encode_detections`` (28x28 probabilities and boxes, no pasted
+mask) run ``csrc/seam_rle.hip`` and bring a few hundred integers per object to the host, where ``counts_to_bytes`` writes the
+compressed strings with vectorised NumPy; ``decode``, ``area``, ``toBbox``, ``annToRLE`` and ``iou`` complete the reference's
+module.  A pixel is set iff its byte is non-zero (pycocotools' ``encode`` agrees for bytes 0/1 only).
+Not here: ``merge``, ``frPyObjects``.
 """
 from __future__ import annotations
 
@@ -138,3 +144,174 @@ def targets_to_device(targets: Sequence[dict], device) -> list:
         for i, m in zip(with_segm, masks):
             out[i]["masks"] = m
     return out
+
+
+# ------------------------------------------------------------------------------------------------ masks -> RLE
+def counts_to_bytes(counts_per_object: Sequence) -> list:
+    """``rle_to_string`` for a batch of counts arrays at once, as ASCII bytes, without a Python loop per character.  A value
+    (a count; from the fourth of an object on, its difference to the count two places before) takes the fewest 5-bit groups
+    that hold it as a signed number; group g of all values that have one is computed and stored in one pass, with 0x20 added
+    unless it is the value's last, so the loop runs seven times at the most for 32-bit counts."""
+    arrs = [np.asarray(c, dtype=np.int64).reshape(-1) for c in counts_per_object]
+    if not arrs:
+        return []
+    lens = np.asarray([a.size for a in arrs], np.int64)
+    x = np.concatenate(arrs)
+    starts = np.cumsum(lens) - lens
+    idx = np.arange(x.size, dtype=np.int64) - np.repeat(starts, lens)
+    prev2 = np.concatenate([np.zeros(2, np.int64), x])[:x.size]
+    x = x - np.where(idx > 2, prev2, 0)
+    mag = np.where(x < 0, ~x, x)                                     # fits n groups iff mag < 2^(5n-1)
+    if x.size and int(mag.max()) < 2 ** 31:
+        x, mag = x.astype(np.int32), mag.astype(np.int32)            # the usual case, half the bytes to move
+    n = np.ones(x.size, np.int64)
+    for g in range(1, 13):
+        over = mag >= (1 << (5 * g - 1))
+        if not over.any():
+            break
+        n += over
+    first = np.cumsum(n) - n                                         # each value's first character
+    out = np.empty(int(n.sum()), np.uint8)
+    sel, xs, ns, g = first, x, n, 0
+    while sel.size:                                                  # group g of every value that has one
+        out[sel + g] = ((xs >> (5 * g)) & 0x1F) + np.where(ns - 1 > g, 0x20 + 48, 48)
+        g += 1
+        more = ns > g
+        sel, xs, ns = sel[more], xs[more], ns[more]
+    blob = out.tobytes()
+    char_end = np.concatenate([[0], np.cumsum(n)])[starts + lens]    # characters up to each object's last count
+    return [blob[lo:hi] for lo, hi in zip(np.concatenate([[0], char_end[:-1]]).tolist(), char_end.tolist())]
+
+
+def _rle_dicts(counts_per_object, sizes) -> list:
+    return [{"size": [int(h), int(w)], "counts": c} for c, (h, w) in zip(counts_to_bytes(counts_per_object), sizes)]
+
+
+def encode(bimask):
+    """The reference's ``encode``: NumPy uint8 ``[h,w]`` -> one RLE dict ``{"size": [h, w], "counts": <compressed bytes>}``,
+    ``[h,w,n]`` (any memory order) -> a list of n.  A uint8 device tensor ``[n,H,W]`` (or ``[H,W]``) is encoded where it lies,
+    without a copy to the host.  A pixel is set iff its byte is non-zero."""
+    if isinstance(bimask, torch.Tensor):
+        if bimask.dtype != torch.uint8 or bimask.dim() not in (2, 3):
+            raise ValueError("encode: a device mask must be uint8 [n,H,W] or [H,W]")
+        single = bimask.dim() == 2
+        stack = (bimask[None] if single else bimask).contiguous()
+    else:
+        m = np.asarray(bimask)
+        if m.dtype != np.uint8 or m.ndim not in (2, 3):
+            raise ValueError("encode: a mask must be uint8 [h,w] or [h,w,n]")
+        single = m.ndim == 2
+        m = m[:, :, None] if single else m
+        stack = torch.from_numpy(np.ascontiguousarray(m.transpose(2, 0, 1))).to(torch.device("cuda"))
+    n, h, w = (int(v) for v in stack.shape)
+    lay = ops.mask_layout([n], [(h, w)])
+    out = _rle_dicts(ops.rle_encode(stack.reshape(-1), lay), [(h, w)] * n)
+    return out[0] if single else out
+
+
+def encode_detections(mask_probs: torch.Tensor, boxes: torch.Tensor, size) -> list:
+    """The detections of one image as RLE dicts, straight from what the model returns with ``paste_masks = False``:
+    ``mask_probs`` [K,1,28,28], ``boxes`` [K,4] in pixels of the ``size = (h, w)`` image.  Equal to
+    ``encode(paste_masks(mask_probs, boxes, size) > 0.5)`` bit for bit; no pasted mask is written (``ops.rle_encode_paste``)."""
+    h, w = int(size[0]), int(size[1])
+    counts = ops.rle_encode_paste(mask_probs, boxes.to(torch.float32), (h, w))
+    return _rle_dicts(counts, [(h, w)] * len(counts))
+
+
+# ------------------------------------------------------------------------------------------------ RLE -> everything else
+def _as_list(rles):
+    return (rles, False) if isinstance(rles, list) else ([rles], True)
+
+
+def _counts(rle, what: str) -> np.ndarray:
+    h, w = (int(v) for v in rle["size"])
+    _, counts = _split(rle, (h, w), what)
+    return np.asarray(counts, dtype=np.int64).reshape(-1)
+
+
+def decode(rleObjs, keep_on_device: bool = False):
+    """The reference's ``decode``: one RLE dict -> NumPy uint8 ``[h,w]``; a list of n (of one size) -> ``[h,w,n]`` in Fortran
+    order.  Rasterised on the device by ``rle_masks``; ``keep_on_device`` returns the uint8 ``[n,H,W]`` tensor instead."""
+    rles, single = _as_list(rleObjs)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"decode: the RLEs of one call must share a size, got {sorted(sizes)}")
+    if not rles:
+        raise ValueError("decode: needs at least one RLE")
+    size = sizes.pop()
+    stack = ops.rle_masks([[_counts(r, f"decode: object {j}") for j, r in enumerate(rles)]], [size], torch.device("cuda"))[0]
+    if keep_on_device:
+        return stack
+    m = np.asfortranarray(stack.cpu().numpy().transpose(1, 2, 0))
+    return m[:, :, 0] if single else m
+
+
+def area(rleObjs):
+    """Set pixels of each RLE (``rleArea``: the odd-indexed counts), uint32."""
+    rles, single = _as_list(rleObjs)
+    a = np.asarray([_counts(r, f"area: object {j}")[1::2].sum() for j, r in enumerate(rles)], dtype=np.uint32)
+    return a[0] if single else a
+
+
+def toBbox(rleObjs):
+    """Tight ``[x, y, w, h]`` of each RLE's set pixels, float64 (``rleToBbox``): from the counts, on the host.  ``[0,0,0,0]`` for
+    an empty mask; a run of ones that reaches into the next column makes the box full height."""
+    rles, single = _as_list(rleObjs)
+    out = np.zeros((len(rles), 4), dtype=np.float64)
+    for j, r in enumerate(rles):
+        h = int(r["size"][0])
+        c = _counts(r, f"toBbox: object {j}")
+        m = (c.size // 2) * 2
+        if m == 0:
+            continue
+        t = np.cumsum(c[:m]) - (np.arange(m) & 1)                     # first pixel of a run of ones, last pixel of it
+        y, x = t % h, t // h
+        ys, ye = int(y.min()), int(y.max())
+        if (x[0::2] < x[1::2]).any():
+            ys, ye = 0, h - 1
+        xs, xe = int(x.min()), int(x.max())
+        out[j] = (xs, ys, xe - xs + 1, ye - ys + 1)
+    return out[0] if single else out
+
+
+def annToRLE(ann, size) -> dict:
+    """The reference's ``annToRLE(ann, size)``: polygons or uncompressed RLE -> compressed RLE dict (rasterised and encoded on
+    the device); an already compressed RLE is returned as it is."""
+    segm = _segm(ann)
+    h, w = int(size[0]), int(size[1])
+    if isinstance(segm, dict) and isinstance(segm.get("counts"), (str, bytes, bytearray)):
+        return segm
+    if isinstance(segm, dict):
+        _, counts = _split(segm, (h, w), "annToRLE")
+        ops.pack_rle_masks([[counts]], [(h, w)])                       # validates: integers, non-negative, sum h*w
+        return _rle_dicts([np.asarray(counts, dtype=np.int64)], [(h, w)])[0]
+    return encode(masks_from_annotations([[ann]], [size], torch.device("cuda"))[0])[0]
+
+
+def iou(dt, gt, iscrowd) -> np.ndarray:
+    """The reference's ``iou(dt, gt, iscrowd)`` -> float64 ``[len(dt), len(gt)]``.  Boxes (``[n,4]`` xywh arrays or lists of
+    4-lists) go through ``evaluator_det``'s restatement of ``bbIou``; lists of RLE dicts are decoded on the device and the
+    intersections counted there (not a hot path).  A crowd ground truth divides by the detection's area."""
+    from . import evaluator_det as E
+    crowd = np.asarray(iscrowd, dtype=np.int64).reshape(-1) != 0
+
+    def is_rle(v):
+        return isinstance(v, list) and len(v) > 0 and isinstance(v[0], dict)
+
+    if is_rle(dt) != is_rle(gt) and len(dt) and len(gt):
+        raise ValueError("iou: dt and gt must both be boxes or both be RLEs")
+    if len(crowd) != len(gt):
+        raise ValueError("iou: one iscrowd flag per ground truth is needed")
+    if len(dt) == 0 or len(gt) == 0:
+        return np.zeros((len(dt), len(gt)), dtype=np.float64)
+    if not is_rle(dt):
+        d, g = (np.asarray(v, dtype=np.float64).reshape(-1, 4) for v in (dt, gt))
+        return E._box_iou_xywh(*(d[:, i] for i in range(4)), *(g[:, i] for i in range(4)), crowd)
+    dm, gm = decode(dt, keep_on_device=True) != 0, decode(gt, keep_on_device=True) != 0
+    if tuple(dm.shape[1:]) != tuple(gm.shape[1:]):
+        raise ValueError("iou: dt and gt RLEs differ in size")
+    inter = torch.stack([(dm & g[None]).sum((1, 2)) for g in gm], 1)
+    table = torch.cat([inter.reshape(-1).to(torch.float64), dm.sum((1, 2)).to(torch.float64),
+                       gm.sum((1, 2)).to(torch.float64)]).cpu().numpy()
+    nd, ng = len(dt), len(gt)
+    return E._mask_iou(table[:nd * ng].reshape(nd, ng), table[nd * ng:nd * ng + nd], table[nd * ng + nd:], crowd)

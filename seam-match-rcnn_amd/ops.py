@@ -1929,3 +1929,112 @@ def rle_masks(rles: Sequence[Sequence], sizes: Sequence[Sequence[int]], device) 
     if any(o is None for img in rles for o in img):
         raise ValueError("rle_masks: every object needs its counts")
     return launch_rle_masks(*pack_rle_masks(rles, sizes), device)
+
+
+# ---------------------------------------------------------------------------------------------------- masks to RLE (csrc/seam_rle.hip)
+def _rle_cells(h: int, w: int) -> int:
+    b = int(_native.lib().seam_rle_encode_ws_bytes(int(h), int(w)))
+    if b == 0:
+        raise ValueError(f"rle_encode: size ({h}, {w}) must be (h, w) with 1 <= h, w <= {MASK_MAX_SIDE} and h*w < 2^31")
+    return b // 4
+
+
+def _rle_finish(counts: torch.Tensor, last_cell: torch.Tensor, hws, positions_launch) -> list:
+    """The second half of both encoders: prefix sum, the per-object ends to the host (copy 1), the positions kernel into a
+    buffer of exactly that size, the positions to the host (copy 2), then ``diff([0, *positions, h*w])`` per object."""
+    import numpy as np
+    scan = torch.cumsum(counts, 0)                                   # int64, inclusive
+    ends = scan[last_cell].cpu().numpy()                             # device-to-host copy 1 of 2: the totals
+    total = int(ends[-1])
+    pos = torch.empty((total,), dtype=torch.int32, device=counts.device)
+    positions_launch(scan, pos, total)
+    pos = pos.cpu().numpy().astype(np.int64) if total else np.zeros(0, np.int64)      # copy 2 of 2: the positions
+    return rle_counts_from_positions(pos, ends, hws)
+
+
+def rle_counts_from_positions(pos, ends, hws) -> list:
+    """Host: the batch's run boundaries (object o's are ``pos[ends[o-1]:ends[o]]``, ascending) -> per object
+    ``diff([0, *positions, h*w])``, all objects in one pass."""
+    import numpy as np
+    n = len(hws)
+    ends = np.asarray(ends, dtype=np.int64)
+    lens = np.diff(ends, prepend=0)
+    first = np.cumsum(lens + 2) - (lens + 2)                         # each object's slot for its leading 0
+    edges = np.zeros(int(ends[-1]) + 2 * n, np.int64)
+    edges[np.arange(pos.size, dtype=np.int64) + 2 * np.repeat(np.arange(n, dtype=np.int64), lens) + 1] = pos
+    edges[first + lens + 1] = [h * w for h, w in hws]
+    runs = np.diff(edges)
+    keep = np.ones(runs.size, dtype=bool)
+    keep[first[1:] - 1] = False                                      # the step from one object's h*w to the next one's 0
+    return np.split(runs[keep], np.cumsum(lens + 1)[:-1])
+
+
+def rle_encode(flat: torch.Tensor, lay: MaskLayout) -> list:
+    """The objects of a flat uint8 mask buffer (``mask_flat`` / ``mask_views``; a pixel is set iff its byte != 0) -> one NumPy
+    int64 ``counts`` array per object, maskApi's ``rleEncode``: column-major runs of 0 and 1 alternating, the first a run of
+    zeros (``[h*w]`` for an empty mask, ``[0, h*w]`` for a full one).  Two device-to-host copies whatever the number of objects:
+    the per-object totals, then the run boundaries."""
+    import numpy as np
+    flat = _req(flat, torch.uint8, "flat")
+    if flat.dim() != 1 or flat.numel() != lay.total or not flat.is_cuda:
+        raise ValueError(f"rle_encode: flat must be a uint8 [{lay.total}] tensor on the HIP device")
+    n = int(len(lay.obj_off))
+    if n == 0:
+        return []
+    hw_host = np.ascontiguousarray(lay.obj_hw, dtype=np.int32).reshape(n, 2)
+    cells_of = {}
+    for h, w in {(int(h), int(w)) for h, w in hw_host}:
+        cells_of[(h, w)] = _rle_cells(h, w)
+    cell_off = np.zeros(n + 1, np.int64)
+    np.cumsum([cells_of[(int(h), int(w))] for h, w in hw_host], out=cell_off[1:])
+    cells = int(cell_off[-1])
+    tables = dict(obj_hw=hw_host, obj_off=np.ascontiguousarray(lay.obj_off, dtype=np.int64), cell_off=cell_off)
+    d = _upload_tables(tables, ("obj_hw", "obj_off", "cell_off"), flat.device)
+    ws = torch.empty((cells,), dtype=torch.int32, device=flat.device)
+    counts = torch.empty((cells,), dtype=torch.int32, device=flat.device)
+    lib = _native.lib()
+    hw_ptr = hw_host.ctypes.data_as(C.c_void_p)
+    with torch.cuda.device(flat.device):
+        _native.check(lib.seam_rle_encode_masks_u8(_ptr(flat), flat.numel(), hw_ptr, _ptr(d["obj_hw"]), _ptr(d["obj_off"]),
+                                                   _ptr(d["cell_off"]), _ptr(ws), 4 * cells, _ptr(counts), n, _stream()),
+                      "seam_rle_encode_masks_u8")
+
+        def positions(scan, pos, total):
+            _native.check(lib.seam_rle_positions_masks(hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]), _ptr(ws), 4 * cells,
+                                                       _ptr(scan), _ptr(pos) if total else None, total, n, _stream()),
+                          "seam_rle_positions_masks")
+
+        return _rle_finish(counts, d["cell_off"][1:] - 1, [(int(h), int(w)) for h, w in hw_host], positions)
+
+
+def rle_encode_paste(probs: torch.Tensor, boxes: torch.Tensor, hw) -> list:
+    """The detections of one image, probs [D,1,28,28] or [D,28,28] and boxes [D,4] in pixels of the ``hw = (H, W)`` image ->
+    one NumPy int64 ``counts`` array per detection: the RLE of ``paste_masks(probs, boxes, hw) > 0.5`` bit for bit (the set
+    ``mask_inter`` counts), without the [D,1,H,W] paste -- only each clipped integer box is evaluated, each pixel once.  Two
+    device-to-host copies, as ``rle_encode``."""
+    probs, boxes = _req(probs, name="probs"), _req(boxes, name="boxes")
+    d = probs.shape[0]
+    if tuple(probs.shape[1:]) not in ((1, 28, 28), (28, 28)) or tuple(boxes.shape) != (d, 4):
+        raise ValueError("rle_encode_paste: probs must be [D,1,28,28] or [D,28,28] and boxes [D,4]")
+    if not probs.is_cuda or boxes.device != probs.device:
+        raise ValueError("rle_encode_paste: probs and boxes must be on one HIP device")
+    if boxes.data_ptr() & 15:                                       # the kernel reads a box as one float4
+        boxes = boxes.clone()
+    h, w = int(hw[0]), int(hw[1])
+    per = _rle_cells(h, w)
+    if d == 0:
+        return []
+    cells = per * d
+    ws = torch.empty((cells,), dtype=torch.int32, device=probs.device)
+    counts = torch.empty((cells,), dtype=torch.int32, device=probs.device)
+    lib = _native.lib()
+    with torch.cuda.device(probs.device):
+        _native.check(lib.seam_rle_encode_paste_f32(_ptr(probs), _ptr(boxes), d, h, w, _ptr(ws), 4 * cells, _ptr(counts),
+                                                    _stream()), "seam_rle_encode_paste_f32")
+
+        def positions(scan, pos, total):
+            _native.check(lib.seam_rle_positions_paste(d, h, w, _ptr(ws), 4 * cells, _ptr(scan), _ptr(pos) if total else None,
+                                                       total, _stream()), "seam_rle_positions_paste")
+
+        last = torch.arange(1, d + 1, device=probs.device, dtype=torch.int64) * per - 1
+        return _rle_finish(counts, last, [(h, w)] * d, positions)
