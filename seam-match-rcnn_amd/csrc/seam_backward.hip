@@ -10,32 +10,15 @@
 //   avg-pool+ReLU, BatchNorm1d (batch statistics), pairwise classifier, non-local block + attention pooling:
 //   small fused kernels (training batches are a few dozen ROIs / a few sequences).
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
+#include "seam_launch.h"
 #include <stdint.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
 constexpr int D = 256;
 constexpr int DI = 128;
 constexpr int TB = 64;          // longest sequence the NLB backward keeps in LDS
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// block-wide sum of one value per thread (256 threads), result broadcast; `red` = 4 floats of LDS
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // ------------------------------------------------------------------------------------------------ wgrad
 struct WgradArgs {
@@ -638,8 +621,7 @@ static int conv_wgrad(const float* x, const float* dy, float* dw, int N, int H, 
     wgrad_plan(a.M, C, K, R, S, a.tiles_k, a.tiles_c, a.nchunks, a.chunks_per_split, splits);
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3(a.tiles_k * a.tiles_c * R * S, splits), dim3(256), 0, (hipStream_t)stream, a);
     const size_t per = (size_t)R * S * K * C;
-    int grid = (int)((per + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(per);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ws, dw, splits, R * S, K, C);
     return (int)hipGetLastError();
 }
@@ -676,8 +658,7 @@ int seam_colsum_f32(const float* x, float* out, int M, int K, float* ws, void* s
 int seam_avgpool_relu_bwd_f32(const float* dpool, const float* y, float* dy, int N, int HW, int C, void* stream) {
     const size_t total = (size_t)N * HW * C;
     if (total == 0) return 0;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 8192) grid = 8192;
+    const unsigned grid = seam_launch::grid256(total, 8192);
     hipLaunchKernelGGL(avgpool_relu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dpool, y, dy, HW, C, total);
     return (int)hipGetLastError();
 }

@@ -18,10 +18,8 @@
 // the 16-byte fragment reads of 32 consecutive rows then spread over all banks), each lane reads 4 consecutive k of its row per
 // k-slot, and the global loads of chunk q+1 are in flight while the MFMAs of chunk q run.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 

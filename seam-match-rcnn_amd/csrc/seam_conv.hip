@@ -27,6 +27,8 @@
 //   vmcnt(0)).  Epilogue: scale/shift (bias / folded BN) + residual + ReLU, branch-free buffer ops.
 //   blockIdx -> tile mapping is XCD-aware (consecutive tiles stay on one XCD's L2; bijective form).
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
+#include "seam_launch.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,16 +36,10 @@
 #include "seam_fpn_common.h"
 #include "seam_opts.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int CHUNK_BYTES = 128;                    // k bytes per row per chunk
 constexpr int LDB = CHUNK_BYTES + 16;               // padded LDS row (bytes)
-constexpr unsigned kOob = 0x80000000u;
 
 struct ConvArgs {
     const void* x;
@@ -598,10 +594,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm(const Con
 // LDS: hi and lo planes, rows of exactly 64 B (32 bf16), XOR-swizzled 16-B slots (slot ^ ((row >> 2) & 3)): the
 //   ds_read_b128 lane groups {0-3,12-15,20-27}/{4-11,16-19,28-31} land on 4 distinct slots => conflict-free without
 //   padding; 64 KiB per block at 128x128 (two blocks per CU).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void split_bf16(const f32x4 v, u32x2& hi, u32x2& lo) {
 #pragma unroll
@@ -1313,8 +1305,7 @@ int pack_weight(const float* w, void* w_packed, int K, int Cin, int R, int S, in
     const int kred = kred_of<T>(Cstore, R, S);
     const int rows = ((K + 63) / 64) * 64;
     const size_t total = (size_t)rows * kred;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(pack_weight_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (T*)w_packed, K, Cin, R, S,
                        Cstore, kred, rows, rows % 128 == 0 ? 128 : 64, mode);
     return (int)hipGetLastError();
@@ -1419,11 +1410,10 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
     a.tiles_n = rows / best_bn;
     // persistent blocks: one per resident slot (256 CUs x 2 blocks of 4 waves, or x 1 block of 8 waves); a multiple of 8 so
     // that a block's tiles stay on its XCD
-    const int slots4 = seam_opt::get(seam_opt::CONV_SLOTS);      // dev knob
+    const int slots4 = 512;
     const int ntiles = a.tiles_m * a.tiles_n;
     const int slots = best_bm == 256 ? slots4 / 2 : slots4;
     const dim3 grid(ntiles < slots ? ntiles : slots);
-    const int dyn = seam_opt::get(seam_opt::CONV_DYNLDS);   // dev knob: occupancy experiments
     hipStream_t st = (hipStream_t)stream;
     {
         if (dual) {
@@ -1432,21 +1422,21 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
                 a.tiles_m = (a.M + best_bm - 1) / best_bm;
                 const int nt2 = a.tiles_m * a.tiles_n;
                 const dim3 grid2(nt2 < slots4 ? nt2 : slots4);
-                hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4, true>), grid2, dim3(256), dyn, st, a);
+                hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4, true>), grid2, dim3(256), 0, st, a);
                 return (int)hipGetLastError();
             }
-            if (best_bm == 128 && best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4, true>), grid, dim3(256), dyn, st, a);
-            else if (best_bm == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 64, 4, true>), grid, dim3(256), dyn, st, a);
-            else if (best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 64, 128, 4, true>), grid, dim3(256), dyn, st, a);
-            else hipLaunchKernelGGL((conv_igemm<T, 64, 64, 4, true>), grid, dim3(256), dyn, st, a);
+            if (best_bm == 128 && best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4, true>), grid, dim3(256), 0, st, a);
+            else if (best_bm == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 64, 4, true>), grid, dim3(256), 0, st, a);
+            else if (best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 64, 128, 4, true>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((conv_igemm<T, 64, 64, 4, true>), grid, dim3(256), 0, st, a);
             return (int)hipGetLastError();
         }
     }
-    if (best_bm == 256) hipLaunchKernelGGL((conv_igemm<T, 256, 128, 8>), grid, dim3(512), dyn, st, a);
-    else if (best_bm == 128 && best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4>), grid, dim3(256), dyn, st, a);
-    else if (best_bm == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 64, 4>), grid, dim3(256), dyn, st, a);
-    else if (best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 64, 128, 4>), grid, dim3(256), dyn, st, a);
-    else hipLaunchKernelGGL((conv_igemm<T, 64, 64, 4>), grid, dim3(256), dyn, st, a);
+    if (best_bm == 256) hipLaunchKernelGGL((conv_igemm<T, 256, 128, 8>), grid, dim3(512), 0, st, a);
+    else if (best_bm == 128 && best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 128, 4>), grid, dim3(256), 0, st, a);
+    else if (best_bm == 128) hipLaunchKernelGGL((conv_igemm<T, 128, 64, 4>), grid, dim3(256), 0, st, a);
+    else if (best_bn == 128) hipLaunchKernelGGL((conv_igemm<T, 64, 128, 4>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_igemm<T, 64, 64, 4>), grid, dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
@@ -1584,8 +1574,7 @@ int seam_pack_conv_weight_bx3(const float* w, void* w_packed, float* tmp, int K,
     const int rc = pack_weight<float>(w, tmp, K, Cin, R, S, Cstore, mode, stream);
     if (rc) return rc;
     const size_t total = (size_t)(((K + 63) / 64) * 64) * kred_of<float>(Cstore, R, S);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(split_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, tmp, (unsigned short*)w_packed, total);
     return (int)hipGetLastError();
 }
@@ -1604,8 +1593,7 @@ int seam_pack_conv_weight_sx(const float* w, void* w_packed, float* tmp, int K, 
     if (rc) return rc;
     const int rows = ((K + 63) / 64) * 64;
     const size_t total = (size_t)rows * kred_of<float>(Cstore, R, S);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(split3_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, tmp, (unsigned short*)w_packed, total,
                        rows % 128 == 0 ? 128 : 64);
     return (int)hipGetLastError();

@@ -5,13 +5,11 @@
 //   transposes   NCHW <-> NHWC bridges at the module boundary (LDS-tiled, both sides coalesced)
 //   avgpool      AvgPool2d((6,6)) of the match trunk
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
 
 #include "seam_fastdiv.h"
 #include "seam_fpn_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 

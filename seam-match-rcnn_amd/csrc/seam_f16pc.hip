@@ -28,26 +28,18 @@
 // 3x3 shape whose tiles are >= 3/4 full; 192 x 336 x 256 -> 256: 1.2 PFLOP/s, matrix pipe busy 0.845 -- at 1.50 GHz: the 1300 W
 // package limit, not the issue rate, bounds it (bare MFMAs out of registers sustain 1.76 PFLOP/s at 1.72 GHz on dense operands).
 #include <hip/hip_runtime.h>
-#include <atomic>
+#include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
 #include "seam_fastdiv.h"
-#include "seam_opts.h"
+#include "seam_launch.h"
 #if defined(SEAM_F16PC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/f16pc_abl.sh)
 #endif
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
 constexpr int PXB = 144;                    // LDS bytes per patch pixel: 128 (64 fp16 channels) + 16 -- nine 16-byte slots: consecutive pixels
                                             // fall into consecutive-times-nine bank groups (mod 16: all different)
 constexpr int NPIXMAX = 352;                // patch pixels per buffer (8 x 32 outputs: 10 x 34 = 340)
@@ -77,11 +69,8 @@ constexpr int f16_rb(int nm) { return nm <= 6 ? 18 : 12; }
 #ifndef SEAM_F16PC_ABL
 #define SEAM_F16PC_ABL 0     // experiments: 1 no in-loop A fragment reads, 2 no in-loop B fragment loads, 4 no patch staging
 #endif
-#define LDSQ __attribute__((address_space(3)))
-#define F16_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #ifdef SEAM_F16PC_TRACE
-#define F16_TR(tag) do { if (tr_on) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && tr_k < 2048) p.trace[wave * 2048 + tr_k] = tm_ | ((unsigned long long)(tag) << 56); ++tr_k; } } while (0)
+#define F16_TR(tag) SEAM_STAMP(2048, tag)
 #else
 #define F16_TR(tag) do { } while (0)
 #endif
@@ -105,9 +94,6 @@ struct F16Args {
     int per_img;           // mode 0: bx * by
     unsigned long long* trace;   // SEAM_F16PC_TRACE builds only
 };
-
-// a / d for a < the bound f16pc_plan() checks for that divisor (seam_fastdiv.h)
-__device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 // wave-uniform geometry of one tile
 struct F16Geo { int tn, img0, n_here, y0, x0; };
@@ -154,16 +140,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
     constexpr int MODE = PWI == 34 ? 0 : PWI == 18 ? 2 : 1;      // large maps in 8 x 32 or 16 x 16 patches | G whole small maps per block
     const int n = p.nchunks;
 
-    // ---- the block's tiles: XCD x (= blockIdx & 7) owns a contiguous range of the launch's tiles; its blocks walk it interleaved ----
-    const int T = p.total_tiles, G = gridDim.x;
-    const int xcd = blockIdx.x & 7, sl0 = blockIdx.x >> 3;
-    const int q8 = T >> 3, rem8 = T & 7;
-    const int cnt = q8 + (xcd < rem8 ? 1 : 0);
-    const int start = xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8;
-    const int S = (G >> 3) + ((G & 7) > xcd ? 1 : 0);
-    const int ntiles = sl0 < cnt ? (cnt - sl0 + S - 1) / S : 0;
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
-    const int tile0 = start + sl0;
+    const int tile0 = xt.tile0();
     const size_t img_bytes = (size_t)p.H * p.W * p.C * 2;
     const size_t out_img = (size_t)p.Ho * p.Wo * p.K * 2;
 #ifdef SEAM_F16PC_TRACE
@@ -243,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
         request(rq[1]);                         // chunk 1
         store_chunk(rq[0], 0);
         request(rq[0]);                         // chunk 2
-        F16_BAR();                              // P: chunk 0 visible
+        LDS_BAR();                              // P: chunk 0 visible
         const int total_chunks = ntiles * n;
         int c = 0;
         for (int k = 0; k < ntiles; ++k) {
@@ -264,17 +244,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
                 request(rq[1]);
 #endif
                 F16_TR(12);
-                F16_BAR();
+                LDS_BAR();
                 ++c;
 #if !(SEAM_F16PC_ABL & 4)
                 if (c + 1 < total_chunks) store_chunk(rq[0], 0);
                 request(rq[0]);
 #endif
-                F16_BAR();
+                LDS_BAR();
                 ++c;
             }
             // the tile's epilogue: the consumers' finished fp16 tile -> memory, beside the next tile's first chunk
-            F16_BAR();                          // E: the tile is in LDS
+            LDS_BAR();                          // E: the tile is in LDS
             {
                 const F16Geo qe = f16_geo<MODE>(p, tile0 + k * S);
                 const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -342,7 +322,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
         f32x4 af[NM];                            // A fragments: the one of pixel group m at the current step, refilled right behind its MFMA
         f32x4 bf[RB];                           // B fragments: step s in slot s % RB
         int tile = tile0;
-        F16_BAR();                              // P
+        LDS_BAR();                              // P
         __amdgpu_buffer_rsrc_t w_rsrc;
         auto load_b = [&](const int slot, const int step) {         // step = global step of the tile: chunk * 36 + tap * 4 + ks
             bf[slot] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, blane, step * 1024, 0));
@@ -391,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
                 }
                 SB();
                 F16_TR(2);
-                F16_BAR();                      // chunk t + 1 is in the other buffer; this one may be overwritten
+                LDS_BAR();                      // chunk t + 1 is in the other buffer; this one may be overwritten
                 F16_TR(3);
             }
             // ---- epilogue ----
@@ -434,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc(const F16Args p) {
             };
             if (p.relu) finish_tile(std::true_type{}); else finish_tile(std::false_type{});
             F16_TR(5);
-            F16_BAR();                          // E: the producers take it from here
+            LDS_BAR();                          // E: the producers take it from here
             F16_TR(6);
         }
     }
@@ -482,15 +462,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc64(const F16Args p) {
     const bool consumer = wave < 4;
     constexpr int ROWP = ROWP64;
 
-    const int T = p.total_tiles, G = gridDim.x;
-    const int xcd = blockIdx.x & 7, sl0 = blockIdx.x >> 3;
-    const int q8 = T >> 3, rem8 = T & 7;
-    const int cnt = q8 + (xcd < rem8 ? 1 : 0);
-    const int start = xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8;
-    const int S = (G >> 3) + ((G & 7) > xcd ? 1 : 0);
-    const int ntiles = sl0 < cnt ? (cnt - sl0 + S - 1) / S : 0;
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
-    const int tile0 = start + sl0;
+    const int tile0 = xt.tile0();
     const size_t img_bytes = (size_t)p.H * p.W * 64 * 2;
     const size_t out_img = (size_t)p.Ho * p.Wo * 64 * 2;
     LDSQ unsigned* const dcnt = reinterpret_cast<LDSQ unsigned*>((LDSQ char*)smem + DC64);
@@ -579,23 +554,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc64(const F16Args p) {
         request(rq[1]);                         // tile 1
         store_patch(rq[0], 0);
         request(rq[0]);                         // tile 2
-        F16_BAR();                              // P: tile 0's patch, the epilogue vectors and the count are visible
+        LDS_BAR();                              // P: tile 0's patch, the epilogue vectors and the count are visible
         // interval k (the consumers multiply tile k out of patch[k & 1]): tile k - 1 out of the exchange region; tile k + 1
         // registers -> patch[(k + 1) & 1]; request tile k + 3 into the freed registers; barrier
         drain(-1);
         store_patch(rq[1], 1);
         request(rq[1]);
-        F16_BAR();                              // E(0)
+        LDS_BAR();                              // E(0)
         for (int k = 1; k < ntiles; k += 2) {
             drain(k - 1);
             store_patch(rq[0], 0);              // (past the last tile: zeros into a buffer nobody reads)
             request(rq[0]);
-            F16_BAR();                          // E(k)
+            LDS_BAR();                          // E(k)
             if (k + 1 >= ntiles) break;
             drain(k);
             store_patch(rq[1], 1);
             request(rq[1]);
-            F16_BAR();                          // E(k + 1)
+            LDS_BAR();                          // E(k + 1)
         }
         drain(ntiles - 1);
     } else {
@@ -613,7 +588,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc64(const F16Args p) {
         LDSQ char* const ab0 = (LDSQ char*)smem + ((8 * ph + ((lane >> 4) & 1)) * ROWP + (lane & 15) * 9) * 16 + (lane >> 5) * 16;
         f32x16 acc[4];
         f32x4 af[4];
-        F16_BAR();                              // P
+        LDS_BAR();                              // P
         for (int k = 0; k < ntiles; ++k) {
             LDSQ char* const ac = ab0 + (k & 1) * PB64;
             auto read_a = [&](const int m, const int st) -> f32x4 {
@@ -675,7 +650,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16pc64(const F16Args p) {
             };
             if (SEAM_F16PC64_ABL & 2) { if (acc[0][0] + acc[1][0] + acc[2][0] + acc[3][0] == 123456.75f) *reinterpret_cast<float LDSQ*>(row0) = 1.f; }
             else if (p.relu) finish_tile(std::true_type{}); else finish_tile(std::false_type{});
-            F16_BAR();                          // E(k)
+            LDS_BAR();                          // E(k)
         }
     }
 }
@@ -735,7 +710,7 @@ int f16pc_plan(F16Args& a, int N, int H, int W, int C, int K, int pad) {
         a.bx = (a.Wo + 31) / 32; a.by = (a.Ho + 7) / 8;
         {   // 16 x 16 patches where they leave fewer empty slots (the same sums in the same order: the results do not depend on it)
             const int bx2 = (a.Wo + 15) / 16, by2 = (a.Ho + 15) / 16;
-            if (!c64 && bx2 * by2 < a.bx * a.by && seam_opt::get(seam_opt::F16PC_TILE16)) {
+            if (!c64 && bx2 * by2 < a.bx * a.by) {
                 a.mode = 2; a.PWi = 18; a.PHi = 18; a.npix = 324; a.imgp = 18 * f16_rowp(18); a.bx = bx2; a.by = by2;
             }
         }
@@ -764,20 +739,9 @@ int f16pc_plan(F16Args& a, int N, int H, int W, int C, int K, int pad) {
 
 template <int PWI>
 int f16pc_launch(const F16Args& a, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
-    static std::atomic<int> cus[32];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned bit = 1u << (dev & 31);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_f16pc<PWI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        int ncu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        cus[dev & 31].store(ncu, std::memory_order_relaxed);
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const int ncu = cus[dev & 31].load(std::memory_order_relaxed);
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv3x3_f16pc<PWI>>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
 #ifdef SEAM_F16PC_TRACE
     static seam_dev::TraceBuf tb;
@@ -792,20 +756,9 @@ int f16pc_launch(const F16Args& a, hipStream_t st) {
 }
 
 int f16pc64_launch(const F16Args& a, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
-    static std::atomic<int> cus[32];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned bit = 1u << (dev & 31);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_f16pc64, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64);
-        if (e != hipSuccess) return (int)e;
-        int ncu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        cus[dev & 31].store(ncu, std::memory_order_relaxed);
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const int ncu = cus[dev & 31].load(std::memory_order_relaxed);
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv3x3_f16pc64>(LDS64, &ncu);
+    if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
     hipLaunchKernelGGL(conv3x3_f16pc64, dim3(grid), dim3(512), LDS64, st, a);
     return (int)hipGetLastError();
@@ -838,8 +791,7 @@ long long seam_f16pc_weight_halves(int K, int Cstore) { return (long long)K * Cs
 int seam_pack_conv_weight_f16pc(const float* w, void* w_packed, int K, int Cin, int Cstore, void* stream) {
     if ((K % 128 && !(K == 64 && Cstore == 64)) || Cstore % 64 || Cin > Cstore) return (int)hipErrorInvalidValue;
     const size_t total = (size_t)(K / 32) * (Cstore / 64) * 36 * 64;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(f16pc_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)w_packed, K, Cin, Cstore);
     return (int)hipGetLastError();
 }

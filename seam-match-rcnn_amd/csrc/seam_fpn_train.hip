@@ -23,10 +23,9 @@
 // The sample positions are formed WITHOUT fused multiply-adds (torchvision's own operation sequence, and the oracle's); the
 // forward kernel lets the compiler fuse `y1 + ph * bh`, which can move a position by an ulp.  The level is the forward's.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
 #include "seam_fpn_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

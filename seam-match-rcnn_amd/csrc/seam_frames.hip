@@ -8,6 +8,7 @@
 //   rounded to uint8 before the vertical pass) so the result is bit-identical to Pillow's.
 // ToTensor (/255) and GeneralizedRCNNTransform are fused further down the line in seam_preprocess_u8.
 #include <hip/hip_runtime.h>
+#include "seam_launch.h"
 #include <stdint.h>
 
 #pragma STDC FP_CONTRACT OFF
@@ -139,8 +140,7 @@ int seam_frame_noise_u8(const uint8_t* bgr, const double* noise, uint8_t* rgb, i
                         void* stream) {
     const size_t n = (size_t)H * W * 3;
     if (n == 0) return 0;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 8192) grid = 8192;
+    const unsigned grid = seam_launch::grid256(n, 8192);
     hipLaunchKernelGGL(frame_noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, bgr, noise, rgb, n, sigma, seed);
     return (int)hipGetLastError();
 }

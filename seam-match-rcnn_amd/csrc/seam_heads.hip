@@ -6,11 +6,11 @@
 //                 form is the parity reference; no a^2+b^2-2ab cancellation)
 //   rank_topk     descending rank of softmax(x5)[...,1], k rounds of a workgroup arg-max
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
+#include "seam_launch.h"
 #include <stdint.h>
 
 #include "seam_topk.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -21,12 +21,6 @@ constexpr int D = 256;       // descriptor width
 constexpr int DI = 128;      // NLB inter channels
 constexpr int RC = 16;       // rows per chunk (a 10-frame sequence is one pass over the projection weights)
 constexpr int T_LDS = 96;    // sequences up to this length keep G/a/b in LDS
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct NlbArgs {
     const float* seq;
@@ -234,7 +228,6 @@ struct NlbMfArgs {
     int use_nlb;
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void nlb_attnpool_mfma_kernel(const NlbMfArgs p) {
     __shared__ __attribute__((aligned(16))) float Xs[32 * XLD];
@@ -437,7 +430,6 @@ __global__ __launch_bounds__(256) void nlb_attnpool_mfma_kernel(const NlbMfArgs 
 // Same operation order per pair as the scalar form (sub, mul, fma chain over k) => bit-identical logits.
 // Chunks are software pipelined: next chunk global -> registers while the current one is consumed from
 // LDS, double-buffered LDS, one barrier per chunk.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int PKC = 32, PLD = PKC + 4;
 
 template <int QT, int GT>
@@ -841,8 +833,7 @@ int seam_pair_scores_blockdiag_f32(const float* x, const int* seg, const int64_t
 
 int seam_match_scores_f32(const float* logits, float* score, int64_t n_pairs, void* stream) {
     if (n_pairs <= 0) return 0;
-    int grid = (int)((n_pairs + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(n_pairs);
     hipLaunchKernelGGL(match_scores_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, score, (size_t)n_pairs);
     return (int)hipGetLastError();
 }

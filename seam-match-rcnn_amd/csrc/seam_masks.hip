@@ -16,6 +16,7 @@
 // words of one row band lie along c, so the scan's and the expand's lanes read consecutive words.
 // RLE: one kernel; a pixel binary-searches its column-major index in the object's run starts, its value is the run index & 1.
 #include <hip/hip_runtime.h>
+#include "seam_launch.h"
 #include <stdint.h>
 
 #pragma STDC FP_CONTRACT OFF
@@ -225,8 +226,7 @@ int seam_poly_masks_u8(const int* pts, const int* part_off, const int* part_obj,
         hipError_t rc = hipMemsetAsync(ws, 0, (size_t)ws_bytes, s);
         if (rc != hipSuccess) return (int)rc;
         if (T > 0) {
-            int grid = (T + 255) / 256;
-            if (grid > 4096) grid = 4096;
+            const unsigned grid = seam_launch::grid256(T);
             hipLaunchKernelGGL(poly_toggle_kernel, dim3(grid), dim3(256), 0, s, pts, part_off, part_obj, edge_pt_off, part_ws_off,
                                obj_hw, (uint32_t*)ws, ws_words, P, V, T);
         }

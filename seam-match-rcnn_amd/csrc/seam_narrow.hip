@@ -8,13 +8,11 @@
 // 16-byte loads (a lane takes channels 16 j + 4 (l >> 4) + e of row l & 15; the same k permutation is baked into the
 // packed weights), so the kernel is a pure row stream: x is read once, nothing else moves.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
 constexpr int JMAX = 16;      // 16-channel blocks per row: C <= 256
 
 __global__ __launch_bounds__(256, 2) void linear_narrow_kernel(const float* __restrict__ x, const float* __restrict__ wpk,

@@ -35,11 +35,10 @@
 //     per ds_read_b128 pair keeps the non-MFMA share of the loop near 6 %.)
 //   * epilogue on the VALU beside the other wave's MFMAs: d' = acc + A_q + B_j, compare with tau_q, ballot + prefix count into LDS.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
 
 #include "seam_topk.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -68,15 +67,6 @@ __device__ __forceinline__ float key_to_float(unsigned key) {
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
 
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // ---------------------------------------------------------------------------------------------------------------- 1. prep
 __global__ __launch_bounds__(256) void pairmf_prep(const float* __restrict__ a, const float* __restrict__ w,
                                                    const float* __restrict__ bias, float* __restrict__ awm2,
@@ -93,8 +83,8 @@ __global__ __launch_bounds__(256) void pairmf_prep(const float* __restrict__ a, 
         const int wq = q >> 5, n = (q >> 4) & 1, jj = q & 15, hh = k >> 6, u = (k >> 2) & 15, e = k & 3;
         awm2[((((size_t)(wq * 2 + n) * 16 + u) * 64 + hh * 16 + jj) << 2) + e] = -2.f * wd * av;
     }
-    const float A = block_sum256(wd * av * av, red);
-    const float P = block_sum256(aw * av * av, red);
+    const float A = block_sum(wd * av * av, red);
+    const float P = block_sum(aw * av * av, red);
     if (k == 0) {
         qA[q] = A + (bias[1] - bias[0]);
         qP[q] = P;

@@ -25,30 +25,19 @@
 // Tiles are dealt XCD-aware: row tile t lives on XCD t mod 8, and the K / NS slab groups of one XCD walk the same row tiles at
 // about the same time, so an activation row is read from HBM once and from that XCD's L2 by the other slabs.
 #include <hip/hip_runtime.h>
-#include <atomic>
+#include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_fastdiv.h"
+#include "seam_launch.h"
 #include "seam_fpn_common.h"
-#include "seam_opts.h"
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// LDS access by 32-bit byte address (the K phase keeps its fragment pointers as plain integers: hipcc otherwise re-derives
-// "base + index" per access with a vector add, and every vector-ALU instruction between two fp32 MFMAs idles the matrix pipe)
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ f32x4 lds_read16(int addr) { return *reinterpret_cast<lds_f32x4*>((unsigned)addr); }
 
 constexpr int PW_WAVES = 8;
 constexpr int TBUF = 16 * 128;          // wave-private transpose buffer: 16 pixel rows x 32 channels (rows of 128 B: conflict-free
                                         // for the ds_write_b32 of the accumulator layout AND the ds_read_b128 of the row layout)
-constexpr unsigned kOob = 0x80000000u;
 
 struct PwArgs {
     const float* x;        // [M, C1]
@@ -302,6 +291,22 @@ inline int pw_config(int M, int C1, int C2, int K) {
     return 0;
 }
 
+struct PwLaunch { const PwArgs& a; dim3 grid; size_t lds; hipStream_t st; };
+
+template <int MT, int NT, bool DUAL, int RES>
+hipError_t pw_launch(const PwLaunch& L) {
+    const hipError_t e = seam_launch::prepare<pw_sw_kernel<MT, NT, DUAL, RES>>(163840);
+    if (e == hipSuccess) hipLaunchKernelGGL((pw_sw_kernel<MT, NT, DUAL, RES>), L.grid, dim3(64 * PW_WAVES), L.lds, L.st, L.a);
+    return e;
+}
+
+template <bool DUAL, int RES>
+hipError_t pw_cfg(int MT, int NT, const PwLaunch& L) {
+    if (MT == 1 && NT == 8) return pw_launch<1, 8, DUAL, RES>(L);
+    if (MT == 2 && NT == 4) return pw_launch<2, 4, DUAL, RES>(L);
+    return pw_launch<2, 2, DUAL, RES>(L);
+}
+
 }  // namespace
 
 extern "C" {
@@ -335,38 +340,17 @@ int seam_conv1x1_sw_f32(const float* x, const float* x2, const float* w, const f
     const size_t lds = (size_t)(32 * NT) * (Ct * 4 + 16) + PW_WAVES * TBUF;
     // one block per CU; fewer when the rows do not fill them (a block's first act is to copy its slab): blocks per slab = row
     // tiles / 8 waves, rounded up to the 8 XCDs.  The grid never changes a result (each output pixel is one wave's fixed fma chain).
-    const int max_blk = seam_opt::get(seam_opt::PW_BLOCKS);      // dev knob; a multiple of 64
-    if (max_blk < 64 || max_blk % 64 || max_blk < 8 * a.ns) return (int)hipErrorInvalidValue;
+    const int max_blk = 256;
+    if (max_blk < 8 * a.ns) return (int)hipErrorInvalidValue;
     const int tiles = (M + 32 * MT - 1) / (32 * MT);
     int per_slab = (((tiles + PW_WAVES - 1) / PW_WAVES + 7) / 8) * 8;
     if (per_slab > max_blk / a.ns) per_slab = (max_blk / a.ns) & ~7;      // a multiple of 8 (one row group per XCD), >= 8 by the check above
-    const int nblk = per_slab * a.ns;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-#define SEAM_PW_LAUNCH(mt, nt, dual, res)                                                                                         \
-    do {                                                                                                                         \
-        static std::atomic<unsigned> attr_done{0};      /* one bit per device: the ABI is thread-safe per stream */               \
-        int dev_ = 0;                                                                                                            \
-        (void)hipGetDevice(&dev_);                                                                                               \
-        if (!(attr_done.load(std::memory_order_acquire) & (1u << (dev_ & 31)))) {                                                \
-            e = hipFuncSetAttribute((const void*)pw_sw_kernel<mt, nt, dual, res>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                    163840);                                                                                     \
-            if (e == hipSuccess) attr_done.fetch_or(1u << (dev_ & 31), std::memory_order_release);                               \
-        }                                                                                                                        \
-        if (e == hipSuccess) hipLaunchKernelGGL((pw_sw_kernel<mt, nt, dual, res>), dim3(nblk), dim3(64 * PW_WAVES), lds, st, a); \
-    } while (0)
-#define SEAM_PW_CFG(dual, res)                                                                                                   \
-    do {                                                                                                                         \
-        if (MT == 1 && NT == 8) SEAM_PW_LAUNCH(1, 8, dual, res);                                                                 \
-        else if (MT == 2 && NT == 4) SEAM_PW_LAUNCH(2, 4, dual, res);                                                            \
-        else SEAM_PW_LAUNCH(2, 2, dual, res);                                                                                    \
-    } while (0)
-    if (C2 > 0) SEAM_PW_CFG(true, 0);
-    else if (res_mode == 0) SEAM_PW_CFG(false, 0);
-    else if (res_mode == 1) SEAM_PW_CFG(false, 1);
-    else SEAM_PW_CFG(false, 2);
-#undef SEAM_PW_CFG
-#undef SEAM_PW_LAUNCH
+    const PwLaunch L{a, dim3(per_slab * a.ns), lds, (hipStream_t)stream};
+    hipError_t e;
+    if (C2 > 0) e = pw_cfg<true, 0>(MT, NT, L);
+    else if (res_mode == 0) e = pw_cfg<false, 0>(MT, NT, L);
+    else if (res_mode == 1) e = pw_cfg<false, 1>(MT, NT, L);
+    else e = pw_cfg<false, 2>(MT, NT, L);
     if (e != hipSuccess) return (int)e;
     return (int)hipGetLastError();
 }

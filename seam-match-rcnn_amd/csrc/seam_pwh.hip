@@ -22,22 +22,14 @@
 // accumulated in a different order: results agree to fp32 rounding of the accumulation, not bit for bit; an output is one wave's
 // fixed fma chain, so results are deterministic and independent of M.
 #include <hip/hip_runtime.h>
-#include <atomic>
+#include "seam_device.h"
 #include <stdint.h>
 #include <type_traits>
 #include "seam_fastdiv.h"
+#include "seam_launch.h"
 #include "seam_fpn_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ f32x4 lds_read16(int addr) { return *reinterpret_cast<lds_f32x4*>((unsigned)addr); }
 
 constexpr int PWH_WAVES = 8;
 constexpr int TBUF = 16 * 128;          // wave-private transpose buffer: 16 pixel rows x 32 channels fp32
@@ -455,6 +447,22 @@ inline int pwh_config(long long M, int C1, int C2, int K) {
     return 0;
 }
 
+struct PwhLaunch { const PwhArgs& a; dim3 grid; size_t lds; hipStream_t st; };
+
+template <int MT, int NT, bool DUAL, int RES>
+hipError_t pwh_launch(const PwhLaunch& L) {
+    const hipError_t e = seam_launch::prepare<pw_swh_kernel<MT, NT, DUAL, RES>>(163840);
+    if (e == hipSuccess) hipLaunchKernelGGL((pw_swh_kernel<MT, NT, DUAL, RES>), L.grid, dim3(64 * PWH_WAVES), L.lds, L.st, L.a);
+    return e;
+}
+
+template <bool DUAL, int RES>
+hipError_t pwh_cfg(int MT, int NT, const PwhLaunch& L) {
+    if (MT == 1 && NT == 8) return pwh_launch<1, 8, DUAL, RES>(L);
+    if (MT == 2 && NT == 4) return pwh_launch<2, 4, DUAL, RES>(L);
+    return pwh_launch<4, 2, DUAL, RES>(L);
+}
+
 }  // namespace
 
 extern "C" {
@@ -489,37 +497,14 @@ int seam_conv1x1_swh_f16(const void* x, const void* x2, const void* w, const flo
     const int tiles = (int)((M + 32 * MT - 1) / (32 * MT));
     int per_slab = (((tiles + PWH_WAVES - 1) / PWH_WAVES + 7) / 8) * 8;
     if (per_slab > max_blk / a.ns) per_slab = (max_blk / a.ns) & ~7;      // a multiple of 8 (one row group per XCD), >= 8
-    const int nblk = per_slab * a.ns;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-#define SEAM_PWH_LAUNCH(mt, nt, dual, res)                                                                                        \
-    do {                                                                                                                         \
-        static std::atomic<unsigned> attr_done{0};      /* one bit per device: the ABI is thread-safe per stream */               \
-        int dev_ = 0;                                                                                                            \
-        (void)hipGetDevice(&dev_);                                                                                               \
-        if (!(attr_done.load(std::memory_order_acquire) & (1u << (dev_ & 31)))) {                                                \
-            e = hipFuncSetAttribute((const void*)pw_swh_kernel<mt, nt, dual, res>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                    163840);                                                                                     \
-            if (e == hipSuccess) attr_done.fetch_or(1u << (dev_ & 31), std::memory_order_release);                               \
-        }                                                                                                                        \
-        if (e == hipSuccess) hipLaunchKernelGGL((pw_swh_kernel<mt, nt, dual, res>), dim3(nblk), dim3(64 * PWH_WAVES), lds, st, a); \
-    } while (0)
-#define SEAM_PWH_CFG(dual, res)                                                                                                   \
-    do {                                                                                                                         \
-        if (MT == 1 && NT == 8) SEAM_PWH_LAUNCH(1, 8, dual, res);                                                                \
-        else if (MT == 2 && NT == 4) SEAM_PWH_LAUNCH(2, 4, dual, res);                                                           \
-        else SEAM_PWH_LAUNCH(4, 2, dual, res);                                                                                   \
-    } while (0)
+    const PwhLaunch L{a, dim3(per_slab * a.ns), lds, (hipStream_t)stream};
+    hipError_t e;
     if (C2 > 0) {
         if (res_mode == 2) return (int)hipErrorInvalidValue;
-        if (res_mode == 1) SEAM_PWH_CFG(true, 1); else SEAM_PWH_CFG(true, 0);
+        e = res_mode == 1 ? pwh_cfg<true, 1>(MT, NT, L) : pwh_cfg<true, 0>(MT, NT, L);
     } else {
-        if (res_mode == 2) SEAM_PWH_CFG(false, 2);
-        else if (res_mode == 1) SEAM_PWH_CFG(false, 1);
-        else SEAM_PWH_CFG(false, 0);
+        e = res_mode == 2 ? pwh_cfg<false, 2>(MT, NT, L) : res_mode == 1 ? pwh_cfg<false, 1>(MT, NT, L) : pwh_cfg<false, 0>(MT, NT, L);
     }
-#undef SEAM_PWH_CFG
-#undef SEAM_PWH_LAUNCH
     if (e != hipSuccess) return (int)e;
     return (int)hipGetLastError();
 }
@@ -544,14 +529,8 @@ int seam_stem_s2d_swh_f16(const void* xpad, const void* w, const float* scale, c
     const long long tiles = (a.Mp + 127) / 128;
     long long nblk = (tiles + PWH_WAVES - 1) / PWH_WAVES;
     if (nblk > 256) nblk = 256;
-    static std::atomic<unsigned> attr_done{0};
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    if (!(attr_done.load(std::memory_order_acquire) & (1u << (dev_ & 31)))) {
-        const hipError_t e = hipFuncSetAttribute((const void*)stem_swh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        if (e != hipSuccess) return (int)e;
-        attr_done.fetch_or(1u << (dev_ & 31), std::memory_order_release);
-    }
+    const hipError_t e = seam_launch::prepare<stem_swh_kernel>(163840);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(stem_swh_kernel, dim3((unsigned)nblk), dim3(64 * PWH_WAVES), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -22,20 +22,14 @@
 //     bottleneck reductions, the top FPN lateral -- have none; the C entry refuses one).
 // Arithmetic: the products of seam_conv2d_f16 (fp16 operands, fp32 accumulation in k order, fp32 scale / shift, one rounding).
 #include <hip/hip_runtime.h>
-#include <atomic>
+#include "seam_device.h"
 #include <stdint.h>
 #include <type_traits>
 #include "seam_fastdiv.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "seam_launch.h"
 
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
 constexpr int BM = 256;                     // pixels per tile
 constexpr int CK = 128;                     // channels per chunk
 constexpr int ROWB = CK * 2 + 16;           // LDS bytes per pixel and chunk: 17 slots of 16 bytes -- the 16 lanes of a ds_read_b128 cycle
@@ -52,9 +46,6 @@ constexpr int RB = 16;                      // B fragments in flight per consume
 #ifndef SEAM_PWHPC_ABL
 #define SEAM_PWHPC_ABL 0     // experiments: 1 no in-loop A reads, 2 no in-loop B loads, 4 no row staging
 #endif
-#define LDSQ __attribute__((address_space(3)))
-#define PH_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define SB() __builtin_amdgcn_sched_barrier(0)
 
 struct PwhpcArgs {
     const void* x;         // [M, C] fp16
@@ -67,9 +58,6 @@ struct PwhpcArgs {
     unsigned m_tiles_n;
 };
 
-// a tile index (< total_tiles + 2 * grid) / tiles_n: exact by pwhpc_plan()'s check (seam_fastdiv.h)
-__device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
-
 __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -77,17 +65,12 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
     const bool consumer = wave < 4;
     const int n = p.nchunks;
 
-    // ---- the block's tiles: XCD x (= blockIdx & 7) owns a contiguous range of the launch's tiles (tile = m-tile * tiles_n + n-tile:
-    // the n-tiles of a row block are neighbours -- the second one finds the rows in the L2); its blocks walk it interleaved ----
-    const int T = p.total_tiles, G = gridDim.x;
-    const int xcd = blockIdx.x & 7, sl0 = blockIdx.x >> 3;
-    const int q8 = T >> 3, rem8 = T & 7;
-    const int cnt = q8 + (xcd < rem8 ? 1 : 0);
-    const int start = xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8;
-    const int S = (G >> 3) + ((G & 7) > xcd ? 1 : 0);
-    const int ntiles = sl0 < cnt ? (cnt - sl0 + S - 1) / S : 0;
+    // ---- the block's tiles (tile = m-tile * tiles_n + n-tile: the n-tiles of a row block are neighbours -- the second one finds the
+    // rows in the L2) ----
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
-    const int tile0 = start + sl0;
+    const int tile0 = xt.tile0();
     const size_t row_bytes = (size_t)p.C * 2, out_row = (size_t)p.K * 2;
     LDSQ unsigned* const dcnt = reinterpret_cast<LDSQ unsigned*>((LDSQ char*)smem + DC);
 
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
         request(rq[1]);                         // chunk 1
         store_chunk(rq[0], 0);
         request(rq[0]);                         // chunk 2
-        PH_BAR();                               // P: chunk 0 visible
+        LDS_BAR();                              // P: chunk 0 visible
         for (int k = 0; k < ntiles; ++k) {
             for (int t = 0; t < n; t += 2) {    // two chunks per trip: the register sets' parity is a compile-time constant
                 if (t == n - 2 && ptid < 64) {  // the tile's epilogue vectors -> LDS (read by the consumers behind the last chunk's barrier)
@@ -149,13 +132,13 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
                 // chunk c (even position in the tile): chunk c + 1 registers (set 1) -> buffer 1; request chunk c + 3 into set 1
                 store_chunk(rq[1], 1);
                 request(rq[1]);
-                PH_BAR();
+                LDS_BAR();
                 store_chunk(rq[0], 0);
                 request(rq[0]);
-                PH_BAR();
+                LDS_BAR();
             }
             // the tile's epilogue: the consumers' finished fp16 tile -> memory, beside the next tile's first chunk
-            PH_BAR();                           // E: the tile is in LDS
+            LDS_BAR();                          // E: the tile is in LDS
             {
                 const int tl = tile0 + k * S;
                 const int tm = fdivu(tl, p.tiles_n, p.m_tiles_n);
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
         f32x4 af[8];
         f32x4 bf[RB];
         int tile = tile0;
-        PH_BAR();                               // P
+        LDS_BAR();                              // P
         __amdgpu_buffer_rsrc_t w_rsrc;
         auto load_b = [&](const int slot, const int step) {         // step = chunk * 8 + ks of the tile
             bf[slot] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, blane, step * 1024, 0));
@@ -254,7 +237,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
 #endif
                 }
                 SB();
-                PH_BAR();                       // chunk t + 1 is in the other buffer; this one may be overwritten
+                LDS_BAR();                      // chunk t + 1 is in the other buffer; this one may be overwritten
             };
             for (int t = 0; t < n; t += 2) {    // (n is even: the buffer and ring phases are compile-time constants)
                 chunk(t, 0);
@@ -295,7 +278,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_f16pc(const PwhpcArgs p) {
                 }
             };
             if (p.relu) finish_tile(std::true_type{}); else finish_tile(std::false_type{});
-            PH_BAR();                           // E: the producers take it from here
+            LDS_BAR();                          // E: the producers take it from here
         }
     }
 }
@@ -351,8 +334,7 @@ long long seam_conv1x1_f16pc_weight_halves(int K, int C) { return (long long)K *
 int seam_pack_conv1x1_weight_f16pc(const float* w, void* w_packed, int K, int C, void* stream) {
     if (K % 128 || C % 128) return (int)hipErrorInvalidValue;
     const size_t total = (size_t)(K / 32) * (C / 128) * 8 * 64;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(pwhpc_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)w_packed, K, C);
     return (int)hipGetLastError();
 }
@@ -363,20 +345,9 @@ int seam_conv1x1_f16pc(const void* x, const void* w_packed, const float* scale, 
     PwhpcArgs a;
     if (residual || pwhpc_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y; a.relu = relu;
-    static std::atomic<unsigned> attr_done{0};
-    static std::atomic<int> cus[32];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned bit = 1u << (dev & 31);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv1x1_f16pc, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        int ncu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        cus[dev & 31].store(ncu, std::memory_order_relaxed);
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const int ncu = cus[dev & 31].load(std::memory_order_relaxed);
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_f16pc>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
     hipLaunchKernelGGL(conv1x1_f16pc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
     return (int)hipGetLastError();

@@ -32,19 +32,16 @@
 // fourth channel in its last lanes (the store reads its data registers over several cycles; with an immediate offset hipcc adds
 // the wait state itself).
 #include <hip/hip_runtime.h>
-#include <atomic>
+#include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_fastdiv.h"
+#include "seam_launch.h"
 #include "seam_opts.h"
 #if defined(SEAM_PWPC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/pwpc_abl.sh)
 #endif
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -61,16 +58,12 @@ constexpr int LDS_BYTES = TR0 + 4 * 2 * TBUF;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS map");
 constexpr int BS = 3;                       // the chunk's barrier follows the MFMAs of this 8-k step
 constexpr int RB = 8;                       // B fragments in flight per consumer wave: one chunk (8 steps of 8 k) ahead
-constexpr unsigned kOob = 0x80000000u;
 
 #ifndef SEAM_PWPC_ABL
 #define SEAM_PWPC_ABL 0     // experiments: 1 producers idle (no loads / LDS stores), 2 no in-loop A fragment reads, 4 no in-loop B fragment loads
 #endif
-#define LDSQ __attribute__((address_space(3)))
-#define PWPC_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #ifdef SEAM_PWPC_TRACE
-#define PW_TR(tag) do { if (tr_on) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && tr_k < 1024) p.trace[wave * 1024 + tr_k] = tm_ | ((unsigned long long)(tag) << 56); ++tr_k; } } while (0)
+#define PW_TR(tag) SEAM_STAMP(1024, tag)
 #else
 #define PW_TR(tag) do { } while (0)
 #endif
@@ -88,9 +81,6 @@ struct PwpcArgs {
     unsigned long long* trace;   // SEAM_PWPC_TRACE builds only
 };
 
-// a tile index (< total_tiles + 2 * grid) / tiles_n: exact by pwpc_plan()'s check (seam_fastdiv.h)
-__device__ __forceinline__ int fdivu(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
-
 __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -98,17 +88,11 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
     const bool consumer = wave < 4;
     const int n = p.nchunks;
 
-    // ---- the block's tiles: XCD x (= blockIdx & 7) owns a contiguous range of the launch's tiles (tile = m-tile * tiles_n + n-tile:
-    // the n-tiles of an activation row block are neighbours); its blocks walk it interleaved ----
-    const int T = p.total_tiles, G = gridDim.x;
-    const int xcd = blockIdx.x & 7, sl0 = blockIdx.x >> 3;
-    const int q8 = T >> 3, rem8 = T & 7;
-    const int cnt = q8 + (xcd < rem8 ? 1 : 0);
-    const int start = xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8;
-    const int S = (G >> 3) + ((G & 7) > xcd ? 1 : 0);
-    const int ntiles = sl0 < cnt ? (cnt - sl0 + S - 1) / S : 0;
+    // ---- the block's tiles (tile = m-tile * tiles_n + n-tile: the n-tiles of an activation row block are neighbours) ----
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
-    const int tile0 = start + sl0;
+    const int tile0 = xt.tile0();
     const size_t row_bytes = (size_t)p.C * 4, out_row = (size_t)p.K * 4;
 #ifdef SEAM_PWPC_TRACE
     const bool tr_on = p.trace && blockIdx.x == SEAM_PWPC_TRACE && (wave & 3) == 0;
@@ -166,11 +150,11 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
         request(rq[0]);                                     // chunk 2
         store_chunk(rq[1], std::integral_constant<int, 1>{});
         request(rq[1]);                                     // chunk 3
-        PWPC_BAR();                                         // P: chunks 0 and 1 visible
+        LDS_BAR();                                          // P: chunks 0 and 1 visible
         auto step = [&](const int c, auto par_c, auto buf_c) {      // B_c, then chunk c + 2 -> buffer (c + 2) % 3, chunk c + 4 requested
             constexpr int PAR = decltype(par_c)::value;
             PW_TR(11);
-            PWPC_BAR();
+            LDS_BAR();
             PW_TR(12);
 #if !(SEAM_PWPC_ABL & 1)
             if (c + 2 < total_chunks) store_chunk(rq[PAR], buf_c);
@@ -218,7 +202,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
         const LDSQ char* const tr = (const LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane >> 3) * TROW + (lane & 7) * 16;
         int tile = tile0;
         ring_preload(tile);
-        PWPC_BAR();                             // P: chunks 0 and 1 are in LDS
+        LDS_BAR();                              // P: chunks 0 and 1 are in LDS
         int cbuf = 0;                           // LDS buffer of the current chunk (global chunk index % 3)
 #pragma unroll
         for (int m = 0; m < 4; ++m) af[m] = *reinterpret_cast<const f32x4 LDSQ*>(ab + m * (32 * ROWB));
@@ -390,8 +374,7 @@ long long seam_conv1x1_pc_weight_floats(int K, int C) { return (long long)K * C;
 int seam_pack_conv1x1_pc_f32(const float* w, float* w_packed, int K, int C, void* stream) {
     if (K % 128 || C % 128) return (int)hipErrorInvalidValue;
     const size_t total = (size_t)K * C / 4;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(pwpc_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, w_packed, K, C);
     return (int)hipGetLastError();
 }
@@ -401,20 +384,9 @@ int seam_conv1x1_pc_f32(const float* x, const float* w_packed, const float* scal
     PwpcArgs a;
     if (pwpc_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
-    static std::atomic<unsigned> attr_done{0};
-    static std::atomic<int> cus[32];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned bit = 1u << (dev & 31);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv1x1_pc, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        int ncu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        cus[dev & 31].store(ncu, std::memory_order_relaxed);
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const int ncu = cus[dev & 31].load(std::memory_order_relaxed);
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_pc>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
 #ifdef SEAM_PWPC_TRACE
     static seam_dev::TraceBuf tb;

@@ -13,7 +13,7 @@
 
 namespace {
 
-using namespace seam_train;       // wave_sum, block_sum256, ord_key, iou_gt_prop, box_area
+using namespace seam_train;       // block_sum256, ord_key, iou_gt_prop, box_area
 
 constexpr int SAMPLE_THREADS = 1024;
 constexpr int SAMPLE_MAX_CAND = 16384;     // == NMS_MAX_BOXES: rpn_post_nms_top_n_train (8000) + the GT boxes fit

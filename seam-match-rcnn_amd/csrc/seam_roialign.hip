@@ -17,13 +17,11 @@
 // roi_align_lds_kernel  row-staged tiles: per row of bins the <= 4 feature rows its two sample rows touch go through LDS with a
 //                       register-staged prefetch one bin row ahead.  Kept for the A/B: latency-bound (14 dependent stages), slower.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_opts.h"
 #include "seam_fpn_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -2,15 +2,12 @@
 // order-preserving float key of the samplers, and torchvision's box_iou element in its fp32 expression order.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 
 namespace seam_train {
 
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order sum over a 256-thread block (4 waves)
+// fixed-order sum over a 256-thread block (4 waves).  Deliberately not seam_device.h's block_sum: this one associates
+// (r0 + r1) + (r2 + r3) and ends in a barrier (`red` is free again on return); merging the two would change last bits.
 __device__ __forceinline__ float block_sum256(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();

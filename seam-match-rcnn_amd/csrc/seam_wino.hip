@@ -22,42 +22,14 @@
 //   Epilogue: the nu half of the output transform in registers, the xi half through a 32 KiB LDS exchange, then
 //     scale/shift (+ residual, ReLU) and 16-byte NHWC stores.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
+#include "seam_launch.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_opts.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
-
-// Packed-fp32 VALU ops for the input transform.  Written as asm because the DAG combiner scalarises a <4 x float> op
-// whose lanes are extracted one by one (each feeds its own MFMA): 32 v_fma/v_sub per transform instead of 16 packed ones.
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x4 fma4(f32x2 c, f32x4 b, f32x4 a) {        // a + c * b
-    const f32x2 lo = pk_fma(c, __builtin_shufflevector(b, b, 0, 1), __builtin_shufflevector(a, a, 0, 1));
-    const f32x2 hi = pk_fma(c, __builtin_shufflevector(b, b, 2, 3), __builtin_shufflevector(a, a, 2, 3));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
 __device__ __forceinline__ f32x4 add4(f32x4 a, f32x4 b) {
     const f32x2 lo = pk_add(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1));
     const f32x2 hi = pk_add(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3));
@@ -301,7 +273,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino(const WinoArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nu][mt][r] = 0.f;
 
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #define A1(x) do { if (!(SEAM_WINO_ABL & 1)) { x; } } while (0)
 #define A8(x) do { if (!(SEAM_WINO_ABL & 8)) { x; } } while (0)
 #define MF(v, bf, mt, kk, nu) acc[nu][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[nu][kk], bf[nu][kk], acc[nu][mt], 0, 0, 0)
@@ -401,7 +372,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino(const WinoArgs p) {
             if (t + 1 < p.nchunks) chunk(t + 1, 1, bf1, bf0, vb, va);
         }
     }
-#undef SB
 #undef A1
 #undef A8
 #undef MF
@@ -620,8 +590,7 @@ long long seam_wino_weight_floats(int K, int Cstore) { return (long long)K * Cst
 int seam_pack_conv_weight_wino_f32(const float* w, float* u_packed, int K, int Cin, int Cstore, int mode, void* stream) {
     if (!wino_ok(Cstore, K, 3, 3, 1) || Cin > Cstore) return (int)hipErrorInvalidValue;
     const size_t total = (size_t)(K / 32) * (Cstore / 8) * 64;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(wino_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, u_packed, K, Cin, Cstore, mode);
     return (int)hipGetLastError();
 }

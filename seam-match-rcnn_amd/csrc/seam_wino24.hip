@@ -25,40 +25,19 @@
 //   Epilogue: the nu half of the output transform (A4t: 6 -> 4) in registers, the xi half (A2t: 4 -> 2) through a
 //     32 KiB LDS exchange in two passes, scale / shift (+ residual, ReLU), 16-byte NHWC stores.
 #include <hip/hip_runtime.h>
+#include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_fastdiv.h"
+#include "seam_launch.h"
 #include "seam_opts.h"
 #if defined(SEAM_W24PC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/w24pc_abl.sh)
 #endif
-#include <atomic>
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr unsigned kOob = 0x80000000u;
-
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
 #ifndef SEAM_W24_PK
 #define SEAM_W24_PK 1       // 1 (default): the in-loop input transform on packed fp32 VALU ops; 0: scalar-lane v_fma_f32 / v_add_f32
 #endif
@@ -80,11 +59,6 @@ __device__ __forceinline__ float s_sub(float a, float b) {
     float d;
     asm("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
-}
-__device__ __forceinline__ f32x4 fma4(f32x2 c, f32x4 b, f32x4 a) {        // a + c * b
-    const f32x2 lo = pk_fma(c, __builtin_shufflevector(b, b, 0, 1), __builtin_shufflevector(a, a, 0, 1));
-    const f32x2 hi = pk_fma(c, __builtin_shufflevector(b, b, 2, 3), __builtin_shufflevector(a, a, 2, 3));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 // the same with a wave-uniform multiplier held in an SGPR pair (one scalar source per VOP3P): the constants of B4t cost no
 // VGPRs -- the register file is full (96 accumulators, two weight sets), and a VGPR temporary that aliases the
@@ -153,7 +127,7 @@ struct Wino24Args {
     int nt;               // n-tiles per block (kernel template NT)
     int tiles_n;          // K / (32 * NT)
     int nchunks;          // C / 8
-    // ceil(2^32 / d) of the divisors the block prologue needs (fdiv below): an integer division costs ~20 VALU instructions,
+    // ceil(2^32 / d) of the divisors the block prologue needs (fdivu, seam_fastdiv.h): an integer division costs ~20 VALU instructions,
     // and VALU instructions of either resident block delay the matrix pipe
     unsigned m_tiles_n, m_per_img, m_tys, m_pitch, m_bx[3], m_TX[3], m_PW[3];
     // n-tile split over XCD groups (see the kernel's tile decode): nsplit groups, tns = tiles_n / nsplit n-tiles per group, the
@@ -167,9 +141,6 @@ struct Wino24Args {
     unsigned long long* trace;   // SEAM_W24PC_TRACE builds only: s_memtime stamps of one block's waves 0 and 4 (else null)
 };
 
-// a / d with m = ceil(2^32 / d) (d >= 2) -- one v_mul_hi_u32 / s_mul_hi_u32; exact for the numerator bound wino24_plan() checks
-// for each divisor (seam_fastdiv.h)
-__device__ __forceinline__ int fdiv(int a, int d, unsigned m) { return d == 1 ? a : (int)__umulhi((unsigned)a, m); }
 
 constexpr int NPIXMAX = 384;                       // raw patch pixels per buffer (3 x 16-byte loads per thread per chunk)
 constexpr int NI = (2 * NPIXMAX + 255) / 256;
@@ -195,11 +166,11 @@ __device__ __forceinline__ void w24_block(const Wino24Args& p, char* smem, const
     const int lane = tid & 63;
     const int xi = tid >> 6;
     const int TX = p.TX[reg], TY = p.TY[reg];
-    const int byi = fdiv(rb, p.bx[reg], p.m_bx[reg]);
+    const int byi = fdivu(rb, p.bx[reg], p.m_bx[reg]);
     const int bxi = rb - byi * p.bx[reg];
     const int tys = p.tiles_y, pitch = 2 * tys + 2;
     const int R0 = tm * TY;                                // stacked mode: first tile row (global) of this block
-    const int n_img = p.stack ? fdiv(R0, tys, p.m_tys) : tm_img;   // first image of this block
+    const int n_img = p.stack ? fdivu(R0, tys, p.m_tys) : tm_img;   // first image of this block
     const int prow0 = p.stack ? 2 * (R0 - n_img * tys) : 0;
     const int n_here = min(p.G, p.N - n_img);
     const int ty0 = p.stack ? 0 : p.ry0[reg] + byi * TY, tx0 = p.stack ? 0 : p.rx0[reg] + bxi * TX;
@@ -219,11 +190,11 @@ __device__ __forceinline__ void w24_block(const Wino24Args& p, char* smem, const
                                                            // lanes) never share a bank group
     const int nslots = TX * TY;
     auto slot = [&](int id, int& g, int& ty, int& tx, int& prow) -> bool {
-        const int r = fdiv(id, TX, p.m_TX[reg]);
+        const int r = fdivu(id, TX, p.m_TX[reg]);
         tx = tx0 + (id - r * TX);
         if (p.stack) {
             const int R = R0 + r;
-            const int n = fdiv(R, tys, p.m_tys);
+            const int n = fdivu(R, tys, p.m_tys);
             g = n - n_img;
             ty = R - n * tys;
             prow = pitch * g + 2 * ty - prow0;
@@ -247,12 +218,12 @@ __device__ __forceinline__ void w24_block(const Wino24Args& p, char* smem, const
         const int half = idx & 1;
         const int pix = idx >> 1;
         const bool ok = pix < NPIX;
-        const int v = fdiv(pix, PW, p.m_PW[reg]);          // patch row
+        const int v = fdivu(pix, PW, p.m_PW[reg]);          // patch row
         const int px = pix - v * PW;
         int g = 0, gy = iy0 + v;
         if (p.stack) {
             const int vr = prow0 + v;
-            g = fdiv(vr, pitch, p.m_pitch);
+            g = fdivu(vr, pitch, p.m_pitch);
             gy = vr - g * pitch - p.pad;
         }
         const int gx = ix0 + px;
@@ -376,7 +347,6 @@ __device__ __forceinline__ void w24_block(const Wino24Args& p, char* smem, const
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nu][nt][r] = 0.f;
 
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #define MF(nu, kk) do { _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) { \
         acc[nu][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[nu][kk], bcur[nt][nu][kk], acc[nu][nt], 0, 0, 0); if (nt + 1 < NT) SB(); } } while (0)
 #define MG(frag, nu, kk) do { _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) { \
@@ -495,7 +465,6 @@ __device__ __forceinline__ void w24_block(const Wino24Args& p, char* smem, const
         chunk(t, 0, bfs[0], bfs[NBS - 1]);
         if (t + 1 < p.nchunks) chunk(t + 1, 1, bfs[NBS - 1], bfs[0]);
     }
-#undef SB
 #undef MF
 #undef MG
 #undef A1
@@ -623,7 +592,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino24(const Win
         // by nsplit XCDs: patch loads run 2+ chunks ahead and tolerate the miss).
         const int g = xcd % p.nsplit, pi = xcd / p.nsplit;
         const int j = b >> 3;
-        const int tml = fdiv(j, p.tns, p.m_tns);
+        const int tml = fdivu(j, p.tns, p.m_tns);
         tn = g * p.tns + (j - tml * p.tns);
         const int size = p.part_q + (pi < p.part_r ? 1 : 0);
         if (tml >= size) return;                           // padding blocks of the shorter partitions
@@ -631,11 +600,11 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino24(const Win
     } else {
         const int q8 = nblk >> 3, rem8 = nblk & 7;
         const int tile = (xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8) + (b >> 3);
-        tm = fdiv(tile, p.tiles_n, p.m_tiles_n);
+        tm = fdivu(tile, p.tiles_n, p.m_tiles_n);
         tn = tile - tm * p.tiles_n;
     }
     const int per_img = p.per_img;
-    const int tm_img = fdiv(tm, per_img, p.m_per_img);
+    const int tm_img = fdivu(tm, per_img, p.m_per_img);
     int rb = tm - tm_img * per_img;
     int reg = 0;
     if (p.nreg > 1 && rb >= p.bx[0] * p.by[0]) {
@@ -694,10 +663,8 @@ constexpr int PC_EXB = 4 * 4 * 32 * 32 * 4;
 constexpr int PC_LDS = PC_EX + PC_EXB;
 static_assert((2 * RAWB) % 16 == 0 && PC_LDS <= 160 * 1024, "LDS map");
 
-#define PC_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define LDSQ __attribute__((address_space(3)))
 #ifdef SEAM_W24PC_TRACE      // debug: stamp (tag << 56 | s_memtime) into p.trace[wave * 4096 + k++] from lane 0 of the traced block
-#define PC_TR(tag) do { if (tr_on) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && tr_k < 4096) p.trace[wave * 4096 + tr_k] = tm_ | ((unsigned long long)(tag) << 56); ++tr_k; } } while (0)
+#define PC_TR(tag) SEAM_STAMP(4096, tag)
 #else
 #define PC_TR(tag) do { } while (0)
 #endif
@@ -709,9 +676,9 @@ struct PcGeo {
 };
 __device__ __forceinline__ PcGeo pc_geo(const Wino24Args& p, const int tile) {
     PcGeo g;
-    const int tm = fdiv(tile, p.tiles_n, p.m_tiles_n);
+    const int tm = fdivu(tile, p.tiles_n, p.m_tiles_n);
     g.tn = tile - tm * p.tiles_n;
-    const int tm_img = fdiv(tm, p.per_img, p.m_per_img);
+    const int tm_img = fdivu(tm, p.per_img, p.m_per_img);
     int rb = tm - tm_img * p.per_img;
     int reg = 0;
     const int c0 = p.rg[0].bx * p.rg[0].by, c1 = p.rg[1].bx * p.rg[1].by;
@@ -723,10 +690,10 @@ __device__ __forceinline__ PcGeo pc_geo(const Wino24Args& p, const int tile) {
     g.reg = reg;
     const Wino24Args::Rg R = p.rg[reg];         // one 64-byte scalar load
     const int TX = R.TX, TY = R.TY;
-    const int byi = fdiv(rb, R.bx, R.m_bx);
+    const int byi = fdivu(rb, R.bx, R.m_bx);
     const int bxi = rb - byi * R.bx;
     g.R0 = tm * TY;
-    g.n_img = p.stack ? fdiv(g.R0, p.tiles_y, p.m_tys) : tm_img;
+    g.n_img = p.stack ? fdivu(g.R0, p.tiles_y, p.m_tys) : tm_img;
     g.prow0 = p.stack ? 2 * (g.R0 - g.n_img * p.tiles_y) : 0;
     g.n_here = min(p.G, p.N - g.n_img);
     g.ty0 = p.stack ? 0 : R.ry0 + byi * TY;
@@ -747,11 +714,11 @@ __device__ __forceinline__ PcGeo pc_geo(const Wino24Args& p, const int tile) {
 }
 // tile slot id (0..31) of a block patch -> image-in-group g, tile row / column, first patch row; false for idle slots
 __device__ __forceinline__ bool pc_slot(const Wino24Args& p, const PcGeo& q, int id, int& g, int& ty, int& tx, int& prow) {
-    const int r = fdiv(id, q.TX, q.m_TX);
+    const int r = fdivu(id, q.TX, q.m_TX);
     tx = q.tx0 + (id - __mul24(r, q.TX));
     if (p.stack) {
         const int R = q.R0 + r;
-        const int n = fdiv(R, p.tiles_y, p.m_tys);
+        const int n = fdivu(R, p.tiles_y, p.m_tys);
         g = n - q.n_img;
         ty = R - __mul24(n, p.tiles_y);
         prow = __mul24(2 * p.tiles_y + 2, g) + 2 * ty - q.prow0;
@@ -847,24 +814,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
     const int xi = wave & 3;
     const int n = p.nchunks;
 
-    // ---- the block's tiles: XCD x (= blockIdx & 7) owns a contiguous range of the launch's tiles; its blocks walk it interleaved ----
-    const int T = p.total_tiles;
-    const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, sl0 = blockIdx.x >> 3;
-    const int q8 = T >> 3, rem8 = T & 7;
-    const int cnt = q8 + (xcd < rem8 ? 1 : 0);
-    const int start = xcd < rem8 ? xcd * (q8 + 1) : rem8 * (q8 + 1) + (xcd - rem8) * q8;
-    const int S = (G >> 3) + ((G & 7) > xcd ? 1 : 0);
-    const int ntiles = sl0 < cnt ? (cnt - sl0 + S - 1) / S : 0;
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
-    const int tile0 = start + sl0;
+    const int tile0 = xt.tile0();
 
     const int vlane = PC_V + (xi * 6 * 64 + lane) * 16;        // this wave pair's row of V[0]: + buf * PC_VB + nu * 1024
 #ifdef SEAM_W24PC_TRACE
     const bool tr_on = p.trace && blockIdx.x == SEAM_W24PC_TRACE && (wave & 3) == 0;
     int tr_k = 0;
 #endif
-#define SB() __builtin_amdgcn_sched_barrier(0)
 
 #ifdef SEAM_W24PC_TRACE
     const unsigned long long blk_t0 = __builtin_amdgcn_s_memtime();
@@ -901,7 +860,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
                     for (int r = 0; r < NP; ++r) {
                         const int v = vp[r] & 0xffff, px = vp[r] >> 16;
                         const int vr = q.prow0 + v;                 // v = 0x7fff (no pixel): an image index far outside the group
-                        const int g = fdiv(vr, pitch, p.m_pitch);
+                        const int g = fdivu(vr, pitch, p.m_pitch);
                         const int gy = vr - __mul24(g, pitch) - p.pad, gx = q.ix0 + px;
                         const bool inb = g < q.n_here && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
                         goff[r] = inb ? (unsigned)((__mul24(__mul24(__mul24(g, p.H) + gy, p.W) + gx, p.C) + (ptid & 7) * 4) * 4) : kOob;
@@ -920,12 +879,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
 #pragma unroll
             for (int r = 0; r < NP; ++r) {
                 const int pix = (ptid >> 3) + 32 * r;
-                const int v = fdiv(pix, q.PW, q.m_PW);
+                const int v = fdivu(pix, q.PW, q.m_PW);
                 const int px = pix - __mul24(v, q.PW);
                 int g = 0, gy = q.iy0 + v;
                 if (p.stack) {
                     const int vr = q.prow0 + v;
-                    g = fdiv(vr, pitch, p.m_pitch);
+                    g = fdivu(vr, pitch, p.m_pitch);
                     gy = vr - __mul24(g, pitch) - p.pad;
                 }
                 const int gx = q.ix0 + px;
@@ -1056,16 +1015,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
         }
         store_chunk(rq[0], 0, 0);
         store_chunk(rq[0], 1, 1);
-        PC_BAR();                               // P1: raw(0), raw(1) visible (the patch is shared by the four producer waves)
+        LDS_BAR();                              // P1: raw(0), raw(1) visible (the patch is shared by the four producer waves)
         tr_read(0);
         tr_math();
         tr_write(0);
         tr_read(1);
-        PC_BAR();                               // P2: every wave has read raw[0] and raw[1]
+        LDS_BAR();                              // P2: every wave has read raw[0] and raw[1]
         tr_math();                              // va = V(1)
         PC_PIN_VA();
         store_chunk(rq[0], 2, 0);               // raw(2)
-        PC_BAR();                               // P3: V(0), raw(2) visible
+        LDS_BAR();                              // P3: V(0), raw(2) visible
 
         // ---- interval i of a tile (i = 0 .. n - 1), closed by the barrier inside the consumers' chunk i:
         //        fragments of chunk i + 1: registers -> V[(i + 1) & 1];   patch of chunk i + 3: registers -> raw[(i + 3) & 1];
@@ -1080,13 +1039,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
             PcEpi epi;
             pc_epi_vectors(p, qp, tid, epi);    // requested here, used behind the barrier
             PC_TR(30);
-            PC_BAR();                           // E1: ex holds n-tile 0
+            LDS_BAR();                          // E1: ex holds n-tile 0
             PC_TR(31);
             if (!(SEAM_W24PC_ABL & 16)) pc_finish(p, qp, ex, 0, tid, false, epi);
             PC_TR(32);
-            PC_BAR();                           // E2: ex is free again
+            LDS_BAR();                          // E2: ex is free again
             PC_TR(33);
-            PC_BAR();                           // E3: ex holds n-tile 1
+            LDS_BAR();                          // E3: ex holds n-tile 1
             PC_TR(34);
             if (!(SEAM_W24PC_ABL & 16)) pc_finish(p, qp, ex, 1, tid, false, epi);
             PC_TR(35);
@@ -1174,9 +1133,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
         f32x4 aq[AD + 1];                       // A fragments: position nu in aq[nu % (AD + 1)]
         static_assert(6 % (AD + 1) == 0 && AD >= 1 && AD <= 2, "the fragment ring's phase repeats every chunk");
         auto read_a = [&](int buf, int nu) -> f32x4 { return *reinterpret_cast<const f32x4*>(smem + vlane + buf * PC_VB + nu * 1024); };
-        PC_BAR();                               // P1
-        PC_BAR();                               // P2
-        PC_BAR();                               // P3
+        LDS_BAR();                              // P1
+        LDS_BAR();                              // P2
+        LDS_BAR();                              // P3
         int tile = tile0;
         auto u_desc = [&](const int tn) {
             return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.u + (size_t)tn * NT * ntile_bytes), 0, NT * ntile_bytes, 0x00020000);
@@ -1240,7 +1199,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
                     SB();
                     if (i == 5 - AD) {          // every fragment of this chunk is in registers (or on its way, waited for by the barrier
                         PC_TR(8);               // statement): the producers may overwrite V[c]
-                        PC_BAR();
+                        LDS_BAR();
                         PC_TR(9);
                     }
                 }
@@ -1261,7 +1220,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 PC_TR(20 + 4 * nt);
-                if (nt == 1) PC_BAR();          // E2: the finishers of n-tile 0 are done with ex
+                if (nt == 1) LDS_BAR();         // E2: the finishers of n-tile 0 are done with ex
                 PC_TR(21 + 4 * nt);
                 if (!(SEAM_W24PC_ABL & 16)) {
                     const f32x2 c2 = {2.f, 2.f}, c4 = {4.f, 4.f}, c8 = {8.f, 8.f};
@@ -1306,7 +1265,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
                     ring_preload();
                 }
                 PC_TR(22 + 4 * nt);
-                PC_BAR();                       // E1 / E3: ex holds this n-tile
+                LDS_BAR();                      // E1 / E3: ex holds this n-tile
                 PC_TR(23 + 4 * nt);
                 if (!(SEAM_W24PC_ABL & 16)) pc_finish(p, q, ex, nt, tid, true, epi);
             }
@@ -1319,7 +1278,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
         }
 #endif
     }
-#undef SB
 }
 
 // OIHW fp32 [K, Cin, 3, 3] -> U = G2 g G4t in MFMA fragment order: [K/32][Cstore/8][24][64][4]
@@ -1521,8 +1479,7 @@ int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, long&
     }
     blocks = pp.blocks * a.tiles_n;
     {
-        const int want = seam_opt::get(seam_opt::W24_NSPLIT);
-        int ns = want > 0 ? want : wino24_nsplit(C, K, pp.blocks);
+        int ns = wino24_nsplit(C, K, pp.blocks);
         while (ns > 1 && (a.tiles_n % ns || 8 % ns)) ns >>= 1;
         a.nsplit = ns < 1 ? 1 : ns;
         a.tns = a.tiles_n / a.nsplit;
@@ -1531,7 +1488,7 @@ int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, long&
         if (a.nsplit > 1) blocks = 8L * (a.part_q + (a.part_r ? 1 : 0)) * a.tns;
     }
     if (blocks >= (1L << 24)) return (int)hipErrorInvalidValue;
-    // fdiv numerator bounds: a tile index (< blocks + grid, grid < 2^16) by tiles_n, a block's j by tns; tm by per_img; rb < per_img
+    // fdivu numerator bounds: a tile index (< blocks + grid, grid < 2^16) by tiles_n, a block's j by tns; tm by per_img; rb < per_img
     // by bx; stacked: a tile row R < (tm + 1) * TY by tiles_y, a patch row (< 2^15 + pitch) by pitch; a slot id, patch pixel (< 2^16)
     // by TX, PW
     {
@@ -1559,8 +1516,7 @@ long long seam_wino24_weight_floats(int K, int Cstore) { return (long long)K * C
 int seam_pack_conv_weight_wino24_f32(const float* w, float* u_packed, int K, int Cin, int Cstore, int mode, void* stream) {
     if (!wino_ok(Cstore, K, 3, 3, 1) || Cin > Cstore) return (int)hipErrorInvalidValue;
     const size_t total = (size_t)(K / 32) * (Cstore / 8) * 64;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const unsigned grid = seam_launch::grid256(total);
     hipLaunchKernelGGL(wino24_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, u_packed, K, Cin, Cstore, mode);
     return (int)hipGetLastError();
 }
@@ -1602,22 +1558,10 @@ int seam_conv3x3_wino24_f32(const float* x, const float* u_packed, const float* 
     a.relu = relu;
     a.trace = nullptr;
     a.total_tiles = 0;
-    const int dyn = seam_opt::get(seam_opt::W24_DYNLDS);     // dev knob: occupancy experiments
     if (wino24_pc(a)) {
-        // > 64 KiB of dynamic LDS needs the attribute once per device (an atomic flag per device: the ABI is thread-safe per stream)
-        static std::atomic<unsigned> attr_done{0};
-        static std::atomic<int> cus[32];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned bit = 1u << (dev & 31);
-        if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-            const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino24pc<SEAM_W24PC_RING>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS);
-            if (e != hipSuccess) return (int)e;
-            int ncu = 0;
-            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-            cus[dev & 31].store(ncu, std::memory_order_relaxed);
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
+        int ncu;
+        const hipError_t e = seam_launch::prepare<conv3x3_wino24pc<SEAM_W24PC_RING>>(PC_LDS, &ncu);
+        if (e != hipSuccess) return (int)e;
         // persistent grid: one block per CU walks its XCD's tile range (SEAM_W24_PERSIST=0: one tile per block)
         const int persist = seam_opt::get(seam_opt::W24_PERSIST);
         a.total_tiles = (int)blocks;
@@ -1627,7 +1571,6 @@ int seam_conv3x3_wino24_f32(const float* x, const float* u_packed, const float* 
             a.rg[r].m_bx = a.m_bx[r]; a.rg[r].m_TX = a.m_TX[r]; a.rg[r].m_PW = a.m_PW[r];
             for (int e = 0; e < 5; ++e) a.rg[r].pad_[e] = 0;
         }
-        const int ncu = cus[dev & 31].load(std::memory_order_relaxed);
         const unsigned grid = (unsigned)(persist && blocks > ncu ? ncu : blocks);
 #ifdef SEAM_W24PC_TRACE
         static seam_dev::TraceBuf tb;
@@ -1639,8 +1582,8 @@ int seam_conv3x3_wino24_f32(const float* x, const float* u_packed, const float* 
 #endif
         return (int)hipGetLastError();
     }
-    if (a.nt == 2) hipLaunchKernelGGL(conv3x3_wino24<2>, dim3((unsigned)blocks), dim3(256), dyn, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(conv3x3_wino24<1>, dim3((unsigned)blocks), dim3(256), dyn, (hipStream_t)stream, a);
+    if (a.nt == 2) hipLaunchKernelGGL(conv3x3_wino24<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(conv3x3_wino24<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -45,6 +45,8 @@ def test_library_exports_every_declared_symbol(native):
 def test_host_helpers_no_gpu(native):
     lib = native.lib()
     assert lib.seam_version() >= 1000
+    # ten variant selectors; a retired one is an unknown name
+    assert lib.seam_option_count() == 10 and lib.seam_set_option(b"SEAM_W24_PC", 1) == 0 and lib.seam_set_option(b"SEAM_PW_BLOCKS", 256) != 0
     assert lib.seam_conv_kred(256, 3, 3) == 2304 and lib.seam_conv_kred(4, 7, 7) == 224
     assert lib.seam_conv_rows_padded(15) == 64 and lib.seam_conv_rows_padded(256) == 256
     assert lib.seam_nlb_workspace_floats(2, 10) >= 2 * 10 * 130
