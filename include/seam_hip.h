@@ -938,6 +938,54 @@ int seam_rle_positions_masks(const int* obj_hw_host, const int* obj_hw, const in
 int seam_rle_positions_paste(int D, int H, int W, const void* ws, int64_t ws_bytes, const int64_t* scan, int* positions,
                              int64_t capacity, seam_stream_t stream);
 
+/* ---- The optimizer step (ref stuffs/engine.py:62-64 optimizer.step(); train_matchrcnn.py:70-72 torch.optim.SGD) ----------------
+ * seam_sgd_step_f32: momentum SGD over every tensor of the table in one launch.  `tensors` and `chunks` are DEVICE tables,
+ * `groups` is HOST memory and travels by value in the kernel arguments (a changed lr costs no upload).
+ *   tensors[t]: p, g (and buf, or NULL without momentum) point at numel fp32 elements, 4-byte aligned; slot indexes groups->g.
+ *   chunks[c]:  count <= seam_sgd_chunk_elems() elements of tensor `tensor` from element `offset` (a multiple of that size); the
+ *               caller lists every element of every tensor in exactly one chunk and no chunk for an empty tensor.
+ *   groups->g[s], per element, every multiply and every add rounded on its own (torch.optim.SGD's arithmetic):
+ *       g = maximize ? -grad : grad;  if (weight_decay != 0) g = g + weight_decay * p;
+ *       if (momentum != 0) { buf = first ? g : momentum * buf + one_minus_dampening * g;  g = nesterov ? g + momentum * buf : buf; }
+ *       p = p - lr * g;
+ *     one_minus_dampening is the caller's (1 - dampening) rounded to fp32 once, as torch passes it; `first`: the slot's buffers
+ *     are not read, only written.
+ * fingerprint: NULL, or 2 * SEAM_SGD_FP_SLOTS uint64 on the device, cleared by the call and filled with partial sums: over the
+ *   even entries, the sum modulo 2^64 of (bit pattern x a position-dependent odd weight) of every parameter element as the kernel
+ *   READ it; over the odd entries, the same of every element as WRITTEN.  The weights depend on (table index, element index)
+ *   only, so with an unchanged parameter list this step's "read" sum equals the previous step's "written" sum unless something
+ *   else wrote a parameter in between -- the one kind of edit no version counter shows (`p.data` in torch).  No extra traffic.
+ * No byte outside the tensors is written.  Refused (non-zero, nothing launched): n_chunks < 0, groups NULL, groups->n outside
+ * 0..SEAM_SGD_MAX_SLOTS, a NULL table with n_chunks > 0.  n_chunks == 0: no-op. */
+#define SEAM_SGD_MAX_SLOTS 32
+#define SEAM_SGD_FP_SLOTS 64
+typedef struct { float* p; const float* g; float* buf; int64_t numel; int group; int reserved; } seam_sgd_tensor_t;
+typedef struct { int tensor; int count; int64_t offset; } seam_sgd_chunk_t;
+typedef struct { float lr, momentum, one_minus_dampening, weight_decay; int nesterov, maximize, first, reserved; } seam_sgd_group_t;
+typedef struct { int n; int reserved[3]; seam_sgd_group_t g[SEAM_SGD_MAX_SLOTS]; } seam_sgd_groups_t;
+int seam_sgd_chunk_elems(void);
+int seam_sgd_step_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* chunks, int n_chunks,
+                      const seam_sgd_groups_t* groups, unsigned long long* fingerprint, seam_stream_t stream);
+
+/* seam_repack_many_f32: the fp32 weight packs of a list of (layer, form) jobs in one launch, each job's bytes equal to its
+ * per-layer entry's: IGEMM = seam_pack_conv_weight_f32 (modes 0, 1, 2), SPLIT3 = seam_pack_conv_weight_sx (computed from the
+ * source, no scratch), WINO / WINO24 = seam_pack_conv_weight_wino_f32 / _wino24_f32, PC = seam_pack_conv1x1_pc_f32, NARROW =
+ * seam_pack_linear_narrow_f32, SW = the row-major [K, C] weights of seam_conv1x1_sw_f32 with scale[k] folded into row k
+ * (scale NULL: a copy).  1x1 forms (PC, SW, NARROW) take R = S = 1, Cstore = Cin = C, mode 0.
+ * seam_repack_layout (HOST table) checks every job by its per-layer entry's rules and fills kred, rows, items, first_block and
+ * n_blocks; it returns the launch's block count, or -(1 + k) when job k is refused.  The caller copies the table to the device
+ * and passes that copy, the job count and the block count to seam_repack_many_f32. */
+enum { SEAM_REPACK_IGEMM = 0, SEAM_REPACK_WINO = 1, SEAM_REPACK_WINO24 = 2, SEAM_REPACK_PC = 3, SEAM_REPACK_SW = 4,
+       SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6 };
+typedef struct {
+    const float* src; void* dst; const float* scale;
+    int64_t items;
+    int form, K, Cin, R, S, Cstore, mode;
+    int kred, rows, first_block, n_blocks, reserved;
+} seam_repack_job_t;
+long long seam_repack_layout(seam_repack_job_t* jobs, int n_jobs);
+int seam_repack_many_f32(const seam_repack_job_t* jobs, int n_jobs, long long total_blocks, seam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ Layout (only what the path needs):
   ops.py     thin launch wrappers (raw device pointers + current HIP stream)
   models/    host-side mirror of the reference's ``models/`` interface
   retrieval.py  clip sharding + RCCL all-gather of the product bank + match
+  optim.py   SGD: the optimizer step in one launch + the in-place refresh of the cached weight packs
   mask_utils.py  ground-truth masks from COCO-style annotations, rasterised on the device
   synth.py   deterministic synthetic weights / inputs
 """

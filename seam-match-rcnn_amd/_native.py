@@ -27,6 +27,41 @@ class TrunkLayer(C.Structure):
     _fields_ = [("w", C.c_void_p), ("u", C.c_void_p), ("u24", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p)]
 
 
+SGD_MAX_SLOTS = 32      # SEAM_SGD_MAX_SLOTS
+SGD_FP_SLOTS = 64       # SEAM_SGD_FP_SLOTS
+
+
+class SgdTensor(C.Structure):
+    """seam_sgd_tensor_t of include/seam_hip.h."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("numel", C.c_int64), ("group", C.c_int), ("reserved", C.c_int)]
+
+
+class SgdChunk(C.Structure):
+    """seam_sgd_chunk_t of include/seam_hip.h."""
+    _fields_ = [("tensor", C.c_int), ("count", C.c_int), ("offset", C.c_int64)]
+
+
+class SgdGroup(C.Structure):
+    """seam_sgd_group_t of include/seam_hip.h."""
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("one_minus_dampening", C.c_float), ("weight_decay", C.c_float),
+                ("nesterov", C.c_int), ("maximize", C.c_int), ("first", C.c_int), ("reserved", C.c_int)]
+
+
+class SgdGroups(C.Structure):
+    """seam_sgd_groups_t of include/seam_hip.h."""
+    _fields_ = [("n", C.c_int), ("reserved", C.c_int * 3), ("g", SgdGroup * SGD_MAX_SLOTS)]
+
+
+REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW = range(7)     # SEAM_REPACK_*
+
+
+class RepackJob(C.Structure):
+    """seam_repack_job_t of include/seam_hip.h."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("scale", C.c_void_p), ("items", C.c_int64),
+                ("form", C.c_int), ("K", C.c_int), ("Cin", C.c_int), ("R", C.c_int), ("S", C.c_int), ("Cstore", C.c_int), ("mode", C.c_int),
+                ("kred", C.c_int), ("rows", C.c_int), ("first_block", C.c_int), ("n_blocks", C.c_int), ("reserved", C.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/seam_hip.h one to one
 SIGNATURES = {
     "seam_version": (_i, []),
@@ -187,6 +222,10 @@ SIGNATURES = {
     "seam_rle_encode_paste_f32": (_i, [_p, _p, _i, _i, _i, _p, _i64, _p, _p]),
     "seam_rle_positions_masks": (_i, [_p, _p, _p, _p, _i64, _p, _p, _i64, _i, _p]),
     "seam_rle_positions_paste": (_i, [_i, _i, _i, _p, _i64, _p, _p, _i64, _p]),
+    "seam_sgd_chunk_elems": (_i, []),
+    "seam_sgd_step_f32": (_i, [_p, _p, _i, C.POINTER(SgdGroups), _p, _p]),
+    "seam_repack_layout": (C.c_longlong, [C.POINTER(RepackJob), _i]),
+    "seam_repack_many_f32": (_i, [_p, _i, C.c_longlong, _p]),
 }
 
 _lib = None

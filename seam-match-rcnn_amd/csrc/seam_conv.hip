@@ -35,6 +35,7 @@
 #include "seam_fastdiv.h"
 #include "seam_fpn_common.h"
 #include "seam_opts.h"
+#include "seam_pack_items.h"
 
 namespace {
 
@@ -1214,21 +1215,8 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 1 : 2) void conv_igemm_
 
 // fp32-packed weights [slab][chunk][row][32 floats] -> [slab][chunk][plane][row][32 bf16], the truncation split of split3_bf16
 __global__ void split3_weight_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, size_t total, int slab_bn) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const float x = in[i];
-        const unsigned x0 = __builtin_bit_cast(unsigned, x) & 0xffff0000u;
-        const float r = x - __builtin_bit_cast(float, x0);
-        const unsigned y0 = __builtin_bit_cast(unsigned, r) & 0xffff0000u;
-        const float s = r - __builtin_bit_cast(float, y0);
-        const size_t rowchunk = i >> 5;
-        const int col = (int)(i & 31);
-        const size_t slabchunk = rowchunk / (size_t)slab_bn;
-        const int row = (int)(rowchunk - slabchunk * slab_bn);
-        unsigned short* o = out + slabchunk * 3 * (size_t)slab_bn * 32 + (size_t)row * 32 + col;
-        o[0] = (unsigned short)(x0 >> 16);
-        o[(size_t)slab_bn * 32] = (unsigned short)(y0 >> 16);
-        o[(size_t)slab_bn * 64] = (unsigned short)(__builtin_bit_cast(unsigned, s) >> 16);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        seam_pack::split3_item(in[i], out, i, slab_bn);
 }
 
 // Re-layout of fp32-packed weights [..][row][32 floats] -> [..][row][32 hi bf16 | 32 lo bf16] (same 128 B per row-chunk)
@@ -1254,42 +1242,8 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ 
     constexpr int BKE = CHUNK_BYTES / (int)sizeof(T);
     const size_t total = (size_t)rows * kred;
     const int nk = kred / BKE;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int col = (int)(i % BKE);
-        size_t rest = i / BKE;
-        const int row_in = (int)(rest % bn);
-        rest /= bn;
-        const int q = (int)(rest % nk);
-        const int tn = (int)(rest / nk);
-        const int row = tn * bn + row_in;
-        int r, s2, c;
-        if (Cstore >= BKE) {
-            const int ccn = Cstore / BKE;
-            s2 = q % S;
-            c = ((q / S) % ccn) * BKE + col;
-            r = q / (S * ccn);
-        } else {
-            const int kk = q * BKE + col;
-            const int pos = kk / Cstore;
-            c = kk - pos * Cstore;
-            r = pos / S;
-            s2 = pos - r * S;
-        }
-        float v = 0.f;
-        if (row < K && c < Cin && r < R) {
-            if (mode == 0) {
-                v = w[(((size_t)row * Cin + c) * R + r) * S + s2];
-            } else if (mode == 2) {   // input-gradient weights of a Conv2d [Cin(out), K(in), R, S]: rotate 180, swap channels
-                v = w[(((size_t)c * K + row) * R + (R - 1 - r)) * S + (S - 1 - s2)];
-            } else {  // ConvTranspose2d weight [Cin, Cout, 2, 2]; row = (a*2+b)*Cout + co
-                const int cout = K / 4;
-                const int ab = row / cout;
-                const int co = row - ab * cout;
-                v = w[(((size_t)c * cout + co) * 2 + (ab >> 1)) * 2 + (ab & 1)];
-            }
-        }
-        out[i] = (T)v;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = (T)seam_pack::igemm_value<BKE>(w, i, K, Cin, R, S, Cstore, nk, bn, mode);
 }
 
 template <typename T>

@@ -9,6 +9,7 @@
 // packed weights), so the kernel is a pure row stream: x is read once, nothing else moves.
 #include <hip/hip_runtime.h>
 #include "seam_device.h"
+#include "seam_pack_items.h"
 #include <stdint.h>
 
 namespace {
@@ -81,11 +82,7 @@ __global__ __launch_bounds__(256, 2) void linear_narrow_kernel(const float* __re
 // [K, C] fp32 row-major -> [C/16][64 lanes][4]: lane (col = l & 15, kq = l >> 4), element e = w[col][16 j + 4 kq + e] (0 for col >= K)
 __global__ void narrow_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int K, int C) {
     const int total = (C >> 4) * 64 * 4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int e = i & 3, lane = (i >> 2) & 63, j = i >> 8;
-        const int col = lane & 15, kq = lane >> 4;
-        out[i] = col < K ? w[(size_t)col * C + 16 * j + 4 * kq + e] : 0.f;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) seam_pack::narrow_item(w, out, i, K, C);
 }
 
 }  // namespace

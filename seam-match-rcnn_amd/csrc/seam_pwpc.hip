@@ -38,6 +38,7 @@
 #include "seam_fastdiv.h"
 #include "seam_launch.h"
 #include "seam_opts.h"
+#include "seam_pack_items.h"
 #if defined(SEAM_PWPC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/pwpc_abl.sh)
 #endif
@@ -334,16 +335,8 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pc(const PwpcArgs p) {
 //   element (tn, w, step, lane, e) = W[n = 128 tn + 32 w + (lane & 31)][c = 8 step + 4 (lane >> 5) + e]
 __global__ void pwpc_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int K, int C) {
     const size_t total = (size_t)K * C / 4;
-    const int nsteps = C / 8;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        size_t rest = i >> 6;
-        const int step = (int)(rest % nsteps); rest /= nsteps;
-        const int nt = (int)rest;                // tn * 4 + w
-        const int nn = nt * 32 + (lane & 31);
-        const int c = 8 * step + 4 * (lane >> 5);
-        *reinterpret_cast<f32x4*>(out + i * 4) = *reinterpret_cast<const f32x4*>(w + (size_t)nn * C + c);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        seam_pack::pwpc_item(w, out, i, C);
 }
 
 int pwpc_plan(PwpcArgs& a, long long M, int C, int K) {

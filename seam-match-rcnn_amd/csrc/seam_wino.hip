@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "seam_opts.h"
+#include "seam_pack_items.h"
 
 namespace {
 
@@ -442,46 +443,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino(const WinoArgs p) {
 __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int K, int Cin, int Cstore, int mode) {
     const int nch = Cstore / 8;
     const size_t total = (size_t)(K / 32) * nch * 64;      // one thread per (tn, chunk, lane): 4 channels x 16 positions
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t rest = i >> 6;
-        const int chunk = (int)(rest % nch);
-        const int tn = (int)(rest / nch);
-        const int n = tn * 32 + (lane & 31);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = chunk * 8 + (lane >> 5) * 4 + e;
-            double g[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    float v = 0.f;
-                    if (c < Cin) v = mode == 2 ? w[(((size_t)c * K + n) * 3 + (2 - r)) * 3 + (2 - s)] : w[(((size_t)n * Cin + c) * 3 + r) * 3 + s];
-                    g[r][s] = (double)v;
-                }
-            double gg[4][3];
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                gg[0][s] = g[0][s];
-                gg[1][s] = 0.5 * (g[0][s] + g[1][s] + g[2][s]);
-                gg[2][s] = 0.5 * (g[0][s] - g[1][s] + g[2][s]);
-                gg[3][s] = g[2][s];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double u0 = gg[q][0];
-                const double u1 = 0.5 * (gg[q][0] + gg[q][1] + gg[q][2]);
-                const double u2 = 0.5 * (gg[q][0] - gg[q][1] + gg[q][2]);
-                const double u3 = gg[q][2];
-                const size_t base = ((((size_t)tn * nch + chunk) * 16 + q * 4) * 64 + lane) * 4 + e;
-                out[base] = (float)u0;
-                out[base + 256] = (float)u1;
-                out[base + 512] = (float)u2;
-                out[base + 768] = (float)u3;
-            }
-        }
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        seam_pack::wino_item(w, out, i, K, Cin, nch, mode);
 }
 
 // Block layout for one tile variant (32*MT tile slots per block).  Small maps: the whole tile grid of G images per block.

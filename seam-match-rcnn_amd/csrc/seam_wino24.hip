@@ -31,6 +31,7 @@
 #include "seam_fastdiv.h"
 #include "seam_launch.h"
 #include "seam_opts.h"
+#include "seam_pack_items.h"
 #if defined(SEAM_W24PC_TRACE)
 #include "dev/seam_trace_host.h"      // -DSEAM_DEV_BUILD experiment builds only (tools/experiments/w24pc_abl.sh)
 #endif
@@ -1287,48 +1288,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino24pc(const Wino24Args p) {
 __global__ void wino24_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int K, int Cin, int Cstore, int mode) {
     const int nch = Cstore / 8;
     const size_t total = (size_t)(K / 32) * nch * 64;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t rest = i >> 6;
-        const int chunk = (int)(rest % nch);
-        const int tn = (int)(rest / nch);
-        const int n = tn * 32 + (lane & 31);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = chunk * 8 + (lane >> 5) * 4 + e;
-            double g[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    float v = 0.f;
-                    if (c < Cin) v = mode == 2 ? w[(((size_t)c * K + n) * 3 + (2 - r)) * 3 + (2 - s)] : w[(((size_t)n * Cin + c) * 3 + r) * 3 + s];
-                    g[r][s] = (double)v;
-                }
-            double gg[4][3];
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                gg[0][s] = g[0][s];
-                gg[1][s] = 0.5 * (g[0][s] + g[1][s] + g[2][s]);
-                gg[2][s] = 0.5 * (g[0][s] - g[1][s] + g[2][s]);
-                gg[3][s] = g[2][s];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double a0 = gg[q][0], a1 = gg[q][1], a2 = gg[q][2];
-                double uu[6];
-                uu[0] = a0 / 4.0;
-                uu[1] = -(a0 + a1 + a2) / 6.0;
-                uu[2] = -(a0 - a1 + a2) / 6.0;
-                uu[3] = a0 / 24.0 + a1 / 12.0 + a2 / 6.0;
-                uu[4] = a0 / 24.0 - a1 / 12.0 + a2 / 6.0;
-                uu[5] = a2;
-                const size_t base = ((((size_t)tn * nch + chunk) * 24 + q * 6) * 64 + lane) * 4 + e;
-#pragma unroll
-                for (int nu = 0; nu < 6; ++nu) out[base + (size_t)nu * 256] = (float)uu[nu];
-            }
-        }
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        seam_pack::wino24_item(w, out, i, K, Cin, nch, mode);
 }
 
 // ---- block layout (32 tile slots of 2 x 4 outputs per block) --------------------------------------------------------

@@ -193,18 +193,28 @@ class ResNet50Body(nn.Module):
     def _all(self):
         return list(self.parameters()) + list(self.buffers())
 
+    def _pack_tensors(self):
+        return self._all()
+
+    def _pack_key(self):
+        """What ``packed()`` caches under: pointer and version of every parameter and buffer, the compute dtype, the split switch."""
+        dt = cdt(self)
+        return _key(self._all(), dt) + (dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True),)
+
     def packed(self):
         dt = cdt(self)
         sx = dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True)
-        key = _key(self._all(), dt) + (sx,)
+        key = self._pack_key()
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
                 pk = {"stem": ops.pack_conv(self.conv1.weight, None, self.bn1.tensors(), stride=2, pad=3,
                                             cstore=8 if dt == torch.float16 else 4, bn_eps=self.bn1.eps, dtype=dt)}
                 if dt in (torch.float32, torch.float16):
                     # w'[k, (dy*2+dx)*3 + c, r', s'] = w[k, c, 2r'+dy-1, 2s'+dx-1]  (zero where the 7x7 kernel has no tap)
-                    w8 = F.pad(self.conv1.weight.detach().to(torch.float32), (1, 0, 1, 0))          # [64,3,8,8], index 0 = tap -1
-                    ws = w8.view(64, 3, 4, 2, 4, 2).permute(0, 3, 5, 1, 2, 4).reshape(64, 12, 4, 4).contiguous()
+                    def s2d_weight():
+                        w8 = F.pad(self.conv1.weight.detach().to(torch.float32), (1, 0, 1, 0))      # [64,3,8,8], index 0 = tap -1
+                        return w8.view(64, 3, 4, 2, 4, 2).permute(0, 3, 5, 1, 2, 4).reshape(64, 12, 4, 4).contiguous()
+                    ws = ops.derived_source(s2d_weight, (self.conv1.weight,))
                     pk["stem_s2d"] = ops.pack_conv(ws, None, self.bn1.tensors(), stride=1, pad=2, cstore=12 if dt == torch.float32 else 16,
                                                    bn_eps=self.bn1.eps, wino=False, dtype=dt)
                     if dt == torch.float16 and STEM_SWH:
@@ -408,9 +418,15 @@ class FeaturePyramidNetwork(nn.Module):
                 state_dict[prefix + ".".join((parts[0], parts[1], parts[3]))] = state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
+    def _pack_tensors(self):
+        return list(self.parameters())
+
+    def _pack_key(self):
+        return _key(self.parameters(), cdt(self))
+
     def packed(self):
         dt = cdt(self)
-        key = _key(self.parameters(), dt)
+        key = self._pack_key()
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
                 self._pk = ([ops.pack_conv(m.weight, m.bias, dtype=dt) for m in self.inner_blocks],
@@ -528,13 +544,22 @@ class RPNHead(nn.Module):
                 state_dict[prefix + "conv." + s] = state_dict.pop(old + s)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
+    def _pack_tensors(self):
+        return list(self.parameters())
+
+    def _pack_key(self):
+        return _key(self.parameters(), cdt(self))
+
     def packed(self):
         dt = cdt(self)
-        key = _key(self.parameters(), dt)
+        key = self._pack_key()
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
-                w = torch.cat([self.cls_logits.weight, self.bbox_pred.weight], 0)       # A + 4A rows, one launch
-                b = torch.cat([self.cls_logits.bias, self.bbox_pred.bias], 0)
+                # A + 4A rows, one launch
+                w = ops.derived_source(lambda: torch.cat([self.cls_logits.weight, self.bbox_pred.weight], 0).detach(),
+                                       (self.cls_logits.weight, self.bbox_pred.weight))
+                b = ops.derived_source(lambda: torch.cat([self.cls_logits.bias, self.bbox_pred.bias], 0).detach(),
+                                       (self.cls_logits.bias, self.bbox_pred.bias))
                 self._pk = (ops.pack_conv(self.conv.weight, self.conv.bias, pad=1, dtype=dt), ops.pack_conv(w, b, dtype=dt))
             self._pk_key = key
         return self._pk

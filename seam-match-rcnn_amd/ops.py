@@ -285,7 +285,10 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         wph = torch.empty((int(lib.seam_conv1x1_f16pc_weight_halves(K, cs)),), dtype=F16, device=weight.device)
         _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wph), K, cs, _stream()),
                       "seam_pack_conv1x1_weight_f16pc")
-    return PackedConv(wp, scale, shift, K, cs, R, S, stride, pad, cin, dtype, u, u24, wn, ws, shift_sw, wq, wh, wsh, wph)
+    pc = PackedConv(wp, scale, shift, K, cs, R, S, stride, pad, cin, dtype, u, u24, wn, ws, shift_sw, wq, wh, wsh, wph)
+    if _PACK_RECORDER is not None:
+        _PACK_RECORDER.records.append((weight, bias, bn, mode, pc))
+    return pc
 
 
 def pack_conv_dgrad(weight: torch.Tensor, pad_fwd: int = 0, wino: bool = True) -> PackedConv:
@@ -689,10 +692,9 @@ def pack_conv_dual(w1: torch.Tensor, bn1, w2: torch.Tensor, bn2, bn_eps: float =
         bw, bb, rm, rv = (t.detach().to(F32) for t in bn)
         sc = bw * torch.rsqrt(rv + bn_eps)
         return w.detach().to(F32).reshape(w.shape[0], -1) * sc[:, None], bb - rm * sc
-    wa, ta = fold(w1, bn1)
-    wb, tb = fold(w2, bn2)
-    w = torch.cat([wa, wb], 1).contiguous()
-    return pack_conv(w[:, :, None, None], (ta + tb).contiguous(), wino=False, dtype=dtype)
+    w = derived_source(lambda: torch.cat([fold(w1, bn1)[0], fold(w2, bn2)[0]], 1).contiguous(), (w1, w2))
+    shift = derived_source(lambda: (fold(w1, bn1)[1] + fold(w2, bn2)[1]).contiguous(), ())      # the two BN shifts: no parameter in it
+    return pack_conv(w[:, :, None, None], shift, wino=False, dtype=dtype)
 
 
 def conv2d_dual(x1: torch.Tensor, x2: torch.Tensor, pc: PackedConv, stride2: int = 1, relu: bool = False) -> torch.Tensor:
@@ -2038,3 +2040,213 @@ def rle_encode_paste(probs: torch.Tensor, boxes: torch.Tensor, hw) -> list:
 
         last = torch.arange(1, d + 1, device=probs.device, dtype=torch.int64) * per - 1
         return _rle_finish(counts, last, [(h, w)] * d, positions)
+
+
+# ------------------------------------------------------------------------------ optimizer step + in-place pack refresh
+def sgd_chunk_table(numels: Sequence[int], chunk: int):
+    """Host logic of ``seam_sgd_step_f32``'s chunk table: (tensor, count, offset) rows that put every element of every tensor into
+    exactly one chunk of at most ``chunk`` elements, offsets multiples of ``chunk``, no row for an empty tensor."""
+    rows = []
+    for t, n in enumerate(numels):
+        n = int(n)
+        if n < 0:
+            raise ValueError("sgd_chunk_table: negative element count")
+        for off in range(0, n, chunk):
+            rows.append((t, min(chunk, n - off), off))
+    return rows
+
+
+def _upload(ctypes_array, device) -> torch.Tensor:
+    """A ctypes table as a uint8 device tensor (the caller keeps it alive while kernels read it)."""
+    host = torch.frombuffer(bytearray(bytes(ctypes_array)), dtype=torch.uint8)
+    return host.to(device)
+
+
+_PACK_RECORDER = None
+
+
+class _PackRecorder:
+    def __init__(self):
+        self.records = []      # (weight handed to the pack kernels, bias argument, bn argument, mode, PackedConv)
+        self.derived = []      # (tensor, fn, deps): pack sources / shifts computed from parameters by ``derived_source``
+
+
+class record_packs:
+    """While active, ``pack_conv`` / ``pack_conv_dual`` / ``derived_source`` note what they packed from what (``PackPlan``)."""
+
+    def __enter__(self):
+        global _PACK_RECORDER
+        self._prev, _PACK_RECORDER = _PACK_RECORDER, _PackRecorder()
+        return _PACK_RECORDER
+
+    def __exit__(self, *exc):
+        global _PACK_RECORDER
+        _PACK_RECORDER = self._prev
+        return False
+
+
+def derived_source(fn, deps: Sequence[torch.Tensor]) -> torch.Tensor:
+    """``fn()``: a tensor a module computes from the parameters ``deps`` and hands to ``pack_conv`` as weight or bias (the stem's
+    space-to-depth weight, the RPN head's stacked logits / deltas rows, the folded shortcut pair).  Under ``record_packs`` the
+    recipe is noted, so that ``PackPlan.refresh`` can recompute the tensor in place when a dependency moved."""
+    t = fn()
+    if _PACK_RECORDER is not None:
+        _PACK_RECORDER.derived.append((t, fn, tuple(deps)))
+    return t
+
+
+class PackPlan:
+    """The in-place refresh of the cached packs of ``backbone.body``, ``backbone.fpn`` and ``rpn.head`` after an optimizer step.
+
+    Built once: every covered module repacks by its own ``packed()`` under ``record_packs``, which yields, per pack, the source (a
+    parameter, or a ``derived_source``) and the destination buffers.  ``rebuilds`` counts every later build.  ``refresh(updated)``
+      * checks on the host that the plan still describes the model (the same ``_pk`` objects, the same parameter / buffer pointers,
+        versions that moved by exactly the optimizer's one bump and only on updated parameters, the same compute dtype / split
+        switch); otherwise it drops everything and rebuilds by the modules' own route -- it never writes through a stale pointer;
+      * recomputes the derived sources whose parameters moved (torch; counted in ``fallback_calls``);
+      * rewrites every weight-dependent buffer of every pack whose source moved in ONE ``seam_repack_many_f32`` launch on the
+        current stream (``launches_per_refresh``); epilogue vectors of a frozen BN and packs of frozen layers are not touched;
+      * sets each module's ``_pk_key`` to what ``packed()`` now computes: the next ``packed()`` is a hit on the same tensors.
+    fp32 compute only (the exact packs and their split-bf16 twins)."""
+
+    COVERED = ("backbone.body", "backbone.fpn", "rpn.head")
+
+    def __init__(self, model):
+        self.modules = []
+        for path in self.COVERED:
+            m = model
+            for part in path.split("."):
+                m = getattr(m, part, None)
+                if m is None:
+                    break
+            if m is not None and hasattr(m, "packed") and hasattr(m, "_pack_key"):
+                self.modules.append((path, m))
+        if not self.modules:
+            raise ValueError("PackPlan: the model has none of " + ", ".join(self.COVERED))
+        self.refreshes = self.rebuilds = self.table_uploads = 0
+        self.launches_per_refresh = self.fallback_calls = 0
+        self._built = self._ever_built = False
+
+    # -- build
+    def build(self):
+        """Build the plan now (``optim.SGD`` does, when it is given the model): every covered module repacks once by its own route."""
+        if not self._built:
+            self._build()
+        return self
+
+    def rebuild_after_edit(self):
+        """The last in-place refresh followed an edit of a parameter that no version counter showed (``optim.SGD`` found the
+        parameters changed under it): treat it like any other edit -- drop the plan and rebuild by the modules' own route."""
+        self.refreshes -= 1
+        self._build()
+
+    def _build(self):
+        self._built = False
+        self._pk, self._keys, self._entries, self._derived = [], [], [], []
+        self._table_for, self._table = None, None
+        for path, m in self.modules:
+            m._pk_key = None
+            with record_packs() as rec:
+                pk = m.packed()
+            params = {p.data_ptr(): p for p in m.parameters() if p.numel()}
+            derived = {t.data_ptr(): (t, fn, deps) for t, fn, deps in rec.derived}
+            self._derived += [d for d in rec.derived if d[2]]
+
+            def deps_of(t, what):
+                if t.data_ptr() in params:
+                    return (params[t.data_ptr()],)
+                if t.data_ptr() in derived:
+                    return derived[t.data_ptr()][2]
+                raise NotImplementedError(f"PackPlan: {path}: the {what} of a pack is neither a parameter nor a derived_source")
+
+            for weight, bias, bn, mode, pc in rec.records:
+                wdeps = deps_of(weight, "weight")
+                if bias is not None:
+                    if bn is not None or pc.shift is None or pc.shift.data_ptr() != bias.data_ptr():
+                        raise NotImplementedError(f"PackPlan: {path}: a pack whose shift is computed from its bias is not covered")
+                    deps_of(bias, "bias")           # a parameter (the shift aliases it) or a derived_source (refreshed with it)
+                self._entries.append((wdeps, self._jobs_of(path, weight, mode, pc)))
+            self._pk.append(pk)
+            self._keys.append(m._pack_key())
+        self.rebuilds += self._ever_built
+        self._built = self._ever_built = True
+
+    @staticmethod
+    def _jobs_of(path, weight, mode, pc):
+        N = _native
+
+        def job(form, dst, R=1, S=1, cs=pc.Cstore, cin=pc.Cin, md=0, scale=None):
+            return N.RepackJob(src=weight.data_ptr(), dst=dst.data_ptr(), scale=None if scale is None else scale.data_ptr(), form=form,
+                               K=pc.K, Cin=cin, R=R, S=S, Cstore=cs, mode=md)
+
+        if pc.dtype in _SX_TERMS:
+            return [job(N.REPACK_SPLIT3, pc.w, pc.R, pc.S, md=mode)]
+        if pc.dtype != F32 or pc.wh is not None or pc.wsh is not None or pc.wph is not None:
+            raise NotImplementedError(f"PackPlan: {path}: only fp32 packs are refreshed in place (pass refresh_packs=False)")
+        jobs = [job(N.REPACK_IGEMM, pc.w, pc.R, pc.S, md=mode)]
+        if pc.u is not None:
+            jobs.append(job(N.REPACK_WINO, pc.u, 3, 3, md=mode))
+        if pc.u24 is not None:
+            jobs.append(job(N.REPACK_WINO24, pc.u24, 3, 3, md=mode))
+        if (pc.wn is not None or pc.ws is not None or pc.wq is not None) and mode != 0:
+            raise NotImplementedError(f"PackPlan: {path}: the pointwise forms of a transposed conv are not covered")
+        if pc.wn is not None:
+            jobs.append(job(N.REPACK_NARROW, pc.wn))
+        if pc.ws is not None and pc.ws.data_ptr() != weight.data_ptr():      # (without a scale the rows ARE the weight: nothing to do)
+            jobs.append(job(N.REPACK_SW, pc.ws, scale=pc.scale))
+        if pc.wq is not None:
+            jobs.append(job(N.REPACK_PC, pc.wq))
+        return jobs
+
+    # -- the host checks
+    def _valid(self, updated) -> bool:
+        for (path, m), pk, old in zip(self.modules, self._pk, self._keys):
+            if m._pk is not pk:
+                return False
+            new = m._pack_key()
+            if len(new) != len(old):
+                return False
+            tensors = m._pack_tensors()
+            for i, (a, b) in enumerate(zip(old, new)):
+                if i >= len(tensors):
+                    if a != b:              # compute dtype, split switch
+                        return False
+                    continue
+                bump = 1 if id(tensors[i]) in updated else 0
+                if a[0] != b[0] or a[1] + bump != b[1]:
+                    return False
+        return True
+
+    @torch.no_grad()
+    def refresh(self, updated: Sequence[torch.Tensor]) -> bool:
+        """``updated``: the parameters the optimizer just changed, their versions bumped once.  True: refreshed in place; False:
+        the plan was (re)built by the modules' own route."""
+        ids = frozenset(id(p) for p in updated)
+        if not self._built or not self._valid(ids):
+            self._build()
+            return False
+        lib = _native.lib()
+        calls = 0
+        for t, fn, deps in self._derived:
+            if any(id(d) in ids for d in deps):
+                t.copy_(fn())
+                calls += 1
+        if self._table_for != ids:
+            jobs = [j for deps, js in self._entries if any(id(d) in ids for d in deps) for j in js]
+            arr = (_native.RepackJob * max(1, len(jobs)))(*jobs)
+            blocks = int(lib.seam_repack_layout(arr, len(jobs)))
+            if blocks < 0:
+                raise _native.SeamNativeError(f"seam_repack_layout refused job {-1 - blocks}")
+            dev = self.modules[0][1]._pack_tensors()[0].device
+            self._table = (_upload(arr, dev) if jobs else None, len(jobs), blocks)
+            self._table_for = ids
+            self.table_uploads += 1
+        table, n, blocks = self._table
+        if n:
+            _native.check(lib.seam_repack_many_f32(_ptr(table), n, blocks, _stream()), "seam_repack_many_f32")
+        for i, (path, m) in enumerate(self.modules):
+            m._pk_key = self._keys[i] = m._pack_key()
+        self.refreshes += 1
+        self.launches_per_refresh = 1 if n else 0
+        self.fallback_calls = calls
+        return True
