@@ -150,6 +150,21 @@ int seam_pack_conv1x1_weight_f16pc(const float* w, void* w_packed, int K, int C,
 int seam_conv1x1_f16pc(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
                        long long M, int C, int K, int relu, seam_stream_t stream);
 
+/* conv1x1_sxpc (csrc/seam_pwsx.hip): the fp32 1x1 / stride-1 / pad-0 layers with a long reduction as six-term split-bf16 products
+ * (the arithmetic of seam_conv2d_sx with terms = 6, bit for bit) on a producer / consumer block -- the split twin of
+ * seam_conv1x1_pc_f32.  Serves torchvision's Bottleneck.conv1 / conv3 + FrozenBatchNorm2d (+ residual) + ReLU on the fp32 path.
+ *   _supported: 1 when the shape is served (C >= 256 and a multiple of 64, K a multiple of 128, M >= 1), else 0;
+ *   _weight_bytes: bytes of the packed weights (three bf16 planes: 6 K C);
+ *   seam_pack_conv1x1_weight_sxpc: w [K, C] fp32 row-major -> [K/128][4][C/16][3 planes][64 lanes][8 bf16] (no padding: the
+ *   supported shapes have none);
+ *   seam_conv1x1_sxpc: y[M, K] = act(scale * (x[M, C] . w^T) + shift + residual), fp32 in / out; relu 0 | 1; a shape that is not
+ *   supported returns hipErrorInvalidValue and launches nothing. */
+int seam_conv1x1_sxpc_supported(long long M, int C, int K);
+long long seam_conv1x1_sxpc_weight_bytes(int K, int C);
+int seam_pack_conv1x1_weight_sxpc(const float* w, void* w_packed, int K, int C, seam_stream_t stream);
+int seam_conv1x1_sxpc(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                      long long M, int C, int K, int relu, seam_stream_t stream);
+
 /* fp16 twin of seam_conv1x1_sw_f32 (csrc/seam_pwh.hip, round 6): the config-5 path's 1x1 layers [TV Bottleneck conv1 / conv3 /
  * stride-1 projection shortcut, FeaturePyramidNetwork.inner_blocks; behind models/video_matchrcnn.py:337] as a STREAMING kernel --
  * weights stationary in LDS, independent waves, 16-byte NHWC pieces in and out -- with the contract of seam_conv2d_f16 /
@@ -970,13 +985,13 @@ int seam_sgd_step_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* 
 /* seam_repack_many_f32: the fp32 weight packs of a list of (layer, form) jobs in one launch, each job's bytes equal to its
  * per-layer entry's: IGEMM = seam_pack_conv_weight_f32 (modes 0, 1, 2), SPLIT3 = seam_pack_conv_weight_sx (computed from the
  * source, no scratch), WINO / WINO24 = seam_pack_conv_weight_wino_f32 / _wino24_f32, PC = seam_pack_conv1x1_pc_f32, NARROW =
- * seam_pack_linear_narrow_f32, SW = the row-major [K, C] weights of seam_conv1x1_sw_f32 with scale[k] folded into row k
- * (scale NULL: a copy).  1x1 forms (PC, SW, NARROW) take R = S = 1, Cstore = Cin = C, mode 0.
+ * seam_pack_linear_narrow_f32, SXPC = seam_pack_conv1x1_weight_sxpc, SW = the row-major [K, C] weights of seam_conv1x1_sw_f32 with scale[k] folded into row k
+ * (scale NULL: a copy).  1x1 forms (PC, SXPC, SW, NARROW) take R = S = 1, Cstore = Cin = C, mode 0.
  * seam_repack_layout (HOST table) checks every job by its per-layer entry's rules and fills kred, rows, items, first_block and
  * n_blocks; it returns the launch's block count, or -(1 + k) when job k is refused.  The caller copies the table to the device
  * and passes that copy, the job count and the block count to seam_repack_many_f32. */
 enum { SEAM_REPACK_IGEMM = 0, SEAM_REPACK_WINO = 1, SEAM_REPACK_WINO24 = 2, SEAM_REPACK_PC = 3, SEAM_REPACK_SW = 4,
-       SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6 };
+       SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6, SEAM_REPACK_SXPC = 7 };
 typedef struct {
     const float* src; void* dst; const float* scale;
     int64_t items;

@@ -52,7 +52,7 @@ class SgdGroups(C.Structure):
     _fields_ = [("n", C.c_int), ("reserved", C.c_int * 3), ("g", SgdGroup * SGD_MAX_SLOTS)]
 
 
-REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW = range(7)     # SEAM_REPACK_*
+REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC = range(8)     # SEAM_REPACK_*
 
 
 class RepackJob(C.Structure):
@@ -98,6 +98,10 @@ SIGNATURES = {
     "seam_conv1x1_f16pc_weight_halves": (C.c_longlong, [_i, _i]),
     "seam_pack_conv1x1_weight_f16pc": (_i, [_p, _p, _i, _i, _p]),
     "seam_conv1x1_f16pc": (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _p]),
+    "seam_conv1x1_sxpc_supported": (_i, [C.c_longlong, _i, _i]),
+    "seam_conv1x1_sxpc_weight_bytes": (C.c_longlong, [_i, _i]),
+    "seam_pack_conv1x1_weight_sxpc": (_i, [_p, _p, _i, _i, _p]),
+    "seam_conv1x1_sxpc": (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _p]),
     "seam_conv1x1_swh_f16": (_i, [_p, _p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_stem_s2d_swh_f16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "seam_conv2d_dual_f16": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -877,28 +877,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm_bx3(const
 // Everything else is conv_igemm_bx3's: the fp32 gather, the chunk walk, the register ring, the XOR-swizzled 64-byte LDS
 // rows (three planes per operand: 96 KiB at 128 x 128, one block per CU), plus the fp32 kernel's 16-byte epilogue.
 // Weights (seam_pack_conv_weight_sx): [n_slab][chunk][plane 0..2][slab_bn rows][32 bf16] -- 192 B per row-chunk.
-// top 16 bits of x as a float.  The opaque asm keeps each value its own register: without it hipcc (7.x) folds the four
-// masked words of a vector into ONE operand of its v_pk_add_f32 (op_sel_hi:[1,0]) and every element loses the top piece of
-// element 0 instead of its own -- found by the identity test, visible in the ISA.
-__device__ __forceinline__ float top16(float x) {
-    unsigned t = __builtin_bit_cast(unsigned, x) & 0xffff0000u;
-    asm volatile("" : "+v"(t));
-    return __builtin_bit_cast(float, t);
-}
-
-__device__ __forceinline__ void split3_bf16(const f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const float a0 = top16(v[2 * p]), b0 = top16(v[2 * p + 1]);
-        const float ra = v[2 * p] - a0, rb = v[2 * p + 1] - b0;          // exact: <= 16 significand bits left
-        const float a1 = top16(ra), b1 = top16(rb);
-        const float sa = ra - a1, sb = rb - b1;                          // exact: <= 8 bits left, a bf16 as it stands
-        p0[p] = (__builtin_bit_cast(unsigned, a0) >> 16) | __builtin_bit_cast(unsigned, b0);
-        p1[p] = (__builtin_bit_cast(unsigned, a1) >> 16) | __builtin_bit_cast(unsigned, b1);
-        p2[p] = (__builtin_bit_cast(unsigned, sa) >> 16) | (__builtin_bit_cast(unsigned, sb) & 0xffff0000u);
-    }
-}
-
+// The split itself (top16, split3_bf16) lives in seam_split.h, shared with conv1x1_sxpc (seam_pwsx.hip).
 template <int BM, int BN, int TERMS>
 __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 1 : 2) void conv_igemm_sx(const ConvArgs p) {
     static_assert(TERMS == 6 || TERMS == 9, "six or nine piece products");

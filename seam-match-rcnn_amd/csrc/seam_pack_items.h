@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "seam_device.h"
+#include "seam_split.h"
 
 namespace seam_pack {
 
@@ -152,6 +153,30 @@ __device__ __forceinline__ void pwpc_item(const float* __restrict__ w, float* __
     const int nn = nt * 32 + (lane & 31);
     const int c = 8 * step + 4 * (lane >> 5);
     *reinterpret_cast<f32x4*>(out + i * 4) = *reinterpret_cast<const f32x4*>(w + (size_t)nn * C + c);
+}
+
+// producer / consumer split 1x1 form (conv1x1_sxpc): item i = (n-tile of 32, k-step, lane) of [K/32][C/16][3 planes][64 lanes][8 bf16]
+// from row-major [K, C]: the lane's eight weights W[32 nt + (lane & 31)][16 step + 8 (lane >> 5) + e] cut into their three bf16
+// pieces (the truncation split of split3_bf16; top16 keeps every value its own register, see seam_split.h)
+__device__ __forceinline__ void sxpc_item(const float* __restrict__ w, unsigned short* __restrict__ out, size_t i, int C) {
+    const int nsteps = C / 16;
+    const int lane = (int)(i & 63);
+    const size_t rest = i >> 6;
+    const int step = (int)(rest % nsteps);
+    const size_t nt = rest / nsteps;
+    const float* src = w + (nt * 32 + (lane & 31)) * (size_t)C + 16 * step + 8 * (lane >> 5);
+    unsigned short* o = out + (nt * nsteps + step) * 1536 + lane * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float x = src[e];
+        const float x0 = top16(x);
+        const float r = x - x0;
+        const float y0 = top16(r);
+        const float s = r - y0;
+        o[e] = (unsigned short)(__builtin_bit_cast(unsigned, x0) >> 16);
+        o[512 + e] = (unsigned short)(__builtin_bit_cast(unsigned, y0) >> 16);
+        o[1024 + e] = (unsigned short)(__builtin_bit_cast(unsigned, s) >> 16);
+    }
 }
 
 // narrow (<= 16 outputs) form: item i of [C/16][64 lanes][4] from row-major [K, C]

@@ -1,0 +1,397 @@
+// seam_pwsx.hip -- pointwise (1x1, stride 1, pad 0) convolution, fp32 in / fp32 out, as six-term three-plane split-bf16 products
+// (the arithmetic of conv_igemm_sx<.., 6>, seam_conv.hip) on a PRODUCER / CONSUMER block persistent over its XCD's tiles: the
+// structure of conv1x1_f16pc (seam_pwhpc.hip) with the fp32 16-byte epilogue of conv1x1_pc (seam_pwpc.hip).  It serves the long
+// 1x1 layers of the fp32 path's split classes: the bottleneck reductions (512 / 1024 / 2048 -> 128 / 256 / 512) and the plain
+// expansions with their residual (256 -> 1024, 512 -> 2048).
+//
+// Why.  conv_igemm_sx is bound by exposed load latency (profiles/split_f32_tile_and_ablation.txt: 333-389 us shipped, 229 us without
+// global loads, 162 us MFMAs + epilogue on 40 x 50^2, 1024 -> 256): all four waves of its block gather, split, store to LDS, meet at
+// a barrier and multiply in turn, one wave per SIMD.  Here
+//   * a block owns 128 pixels (consecutive rows of the [M, C] activation matrix) x 128 output channels per tile;
+//   * waves 4..7 (producers) copy the tile's rows, 64 channels (one 256-byte run per pixel, 16 adjacent lanes per run) per chunk,
+//     global -> registers -> split3_bf16 -> LDS (two LDS buffers, two more chunks in registers), across tile boundaries; their
+//     per-lane offsets are launch invariants, a tile changes one descriptor; every interval issues the same 8 loads (without a chunk:
+//     an empty descriptor), so hipcc's vmcnt bookkeeping is exact;
+//   * waves 0..3 (consumers, one per SIMD) only multiply: wave w owns channels 32 w .. 32 w + 31 of the tile for all 128 pixels (4
+//     accumulator tiles).  Per k-step of 16: twelve `ds_read_b128` (three planes x four 32-pixel groups: lane = pixel, 16 bytes = 8
+//     consecutive k, the upper lanes 8 k further) and three 1-KiB global loads (the wave's three weight planes in fragment order, a
+//     register ring four k-steps deep) feed 24 MFMAs; addresses are per-lane bases + immediates: no VALU in the k-steps (the chunk
+//     loop swaps its two buffer pointers, three v_mov per 96 MFMAs).  One barrier
+//     per chunk (96 MFMAs per wave), inside the chunk's LAST k-step: that step's fragments were read a step earlier, so behind the
+//     barrier the consumers read the next chunk's first fragments under their own MFMAs and run from chunk to chunk -- and from a
+//     tile's epilogue into the next tile -- without a stop, while the producers put chunk c + 2 over chunk c;
+//   * the MFMA's operand roles are swapped (rows = channels, columns = pixels), so a lane ends with four consecutive channels of one
+//     pixel per register quad; the epilogue is conv1x1_pc's: a wave-private LDS transpose into rows (8 lanes per pixel), scale /
+//     shift, plain residual, ReLU, 16-byte stores of full 128-byte lines, no barrier.  The epilogue vectors and the residual pieces of three
+//     of the four pixel groups are requested before the tile's last chunk, the fourth group's at the epilogue's start (all four
+//     ahead spill registers).  Store offsets stay in the vector register (the SGPR-offset hazard).
+// Arithmetic: bit for bit conv_igemm_sx<.., 6>: the same 16 k-values per MFMA in the same element positions, k-steps ascending,
+// within a k-step the six piece products of an accumulator tile in its order (activation piece, weight piece) = (2,0) (1,1) (0,2)
+// (1,0) (0,1) (0,0), every accumulator tile starts from zero; the products are exact, so which operand is the MFMA's A is immaterial.
+//
+// LDS map (139264 bytes, one block per CU):
+//   [0, 102400)        two chunk buffers of 128 pixel rows x 400 bytes: plane 0 | plane 1 | plane 2 (64 bf16 = 128 bytes each) | 16
+//                      bytes of padding -- 25 slots of 16 bytes, odd, so the 16 lanes of a ds_read_b128 cycle (16 consecutive
+//                      pixels) meet 16 different bank groups
+//   [102400, 139264)   per consumer wave two transpose buffers of 32 pixels x (32 channels + 16 bytes)
+#include <hip/hip_runtime.h>
+#include "seam_device.h"
+#include <stdint.h>
+#include <type_traits>
+#include "seam_fastdiv.h"
+#include "seam_launch.h"
+#include "seam_pack_items.h"
+#include "seam_split.h"
+
+namespace {
+
+constexpr int BM = 128;                     // pixels per tile
+constexpr int CK = 64;                      // channels per chunk
+constexpr int KS = CK / 16;                 // k-steps (one MFMA depth) per chunk
+constexpr int PLB = CK * 2;                 // bytes of one plane of a pixel's chunk
+constexpr int ROWB = 3 * PLB + 16;          // LDS bytes per pixel and chunk: 25 slots
+constexpr int ABUF = BM * ROWB;             // 51200
+constexpr int NP = BM * (CK / 4) / 256;     // 16-byte fp32 pieces per producer thread and chunk: 8
+constexpr int TROW = 128 + 16;              // wave-private transpose rows: 32 pixels x (32 channels + 16 bytes)
+constexpr int TBUF = 32 * TROW;             // 4608 bytes
+constexpr int TR0 = 2 * ABUF;
+constexpr int LDS_BYTES = TR0 + 4 * 2 * TBUF;
+static_assert(LDS_BYTES <= 160 * 1024 && ABUF + 3 * PLB < 65536 && 4 * 32 * ROWB < 65536, "LDS map / ds immediates");
+constexpr int RB = 4;                       // k-steps of weight fragments in flight per consumer wave (= KS: the ring slot of a k-step is its index in the chunk)
+static_assert(RB == KS, "ring slot = k-step of the chunk");
+constexpr int RVA = 3;                      // pixel groups whose residual pieces are requested before the tile's last chunk (the fourth: at the
+                                            // epilogue's start; 4 spills 6 registers, 3 leaves 242 VGPRs and no scratch)
+
+#ifndef SEAM_SXPC_ABL
+#define SEAM_SXPC_ABL 0     // timing-only experiments: 1 no row staging, 2 no in-loop weight loads, 4 no split VALU, 8 no in-loop A reads
+#endif
+
+struct SxpcArgs {
+    const float* x;        // [M, C]
+    const void* w;         // packed: [K/128][4 n-tiles][C/16 k-steps][3 planes][64 lanes][8 bf16]
+    const float* scale;    // [K] or null
+    const float* shift;    // [K] or null
+    const float* res;      // [M, K] or null
+    float* y;              // [M, K]
+    int M, C, K, relu;
+    int tiles_n, nchunks, total_tiles;
+    unsigned m_tiles_n;
+};
+
+__global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool consumer = wave < 4;
+    const int n = p.nchunks;
+
+    // ---- the block's tiles (tile = m-tile * tiles_n + n-tile: the n-tiles of a row block are neighbours -- the second one finds the
+    // rows in the L2) ----
+    const XcdTiles xt = xcd_tiles(p.total_tiles);
+    const int ntiles = xt.ntiles, S = xt.stride;
+    if (ntiles == 0) return;
+    const int tile0 = xt.tile0();
+    const size_t row_bytes = (size_t)p.C * 4, out_row = (size_t)p.K * 4;
+    const int total_chunks = ntiles * n;
+
+    if (!consumer) {
+        // =================================================== producer ===================================================
+        const int ptid = tid - 256;
+        unsigned goff[NP];                      // byte offset of piece (ptid & 15) of tile row (ptid >> 4) + 16 r: launch invariants
+        LDSQ char* lp[NP];                      // LDS address of the piece's plane 0 in chunk buffer 0
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int row = (ptid >> 4) + 16 * r;
+            goff[r] = (unsigned)(row * p.C * 4 + (ptid & 15) * 16);
+            lp[r] = (LDSQ char*)smem + row * ROWB + (ptid & 15) * 8;
+        }
+        f32x4 rq[2][NP];                        // two chunks in registers (chunk parity)
+        // the REQUEST stage: chunk ck of tile `tile`; rows past M have no records in the tile's descriptor and read as zeros; past the
+        // block's last tile the descriptor is empty (the loads are issued all the same: see the header)
+        int tile = tile0, ck = 0, tiles_left = ntiles;
+        auto x_desc = [&](const int tl) {
+            const int tm = fdivu(tl, p.tiles_n, p.m_tiles_n);
+            const int row0 = tm * BM;
+            const int rows = tiles_left > 0 ? min(BM, p.M - row0) : 0;
+            return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.x + (size_t)(tiles_left > 0 ? row0 : 0) * row_bytes), 0,
+                                                     (int)(rows * row_bytes), 0x00020000);
+        };
+        __amdgpu_buffer_rsrc_t rs = x_desc(tile);
+        auto request = [&](f32x4 (&dst)[NP]) {
+#pragma unroll
+            for (int r = 0; r < NP; ++r)
+                dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (SEAM_SXPC_ABL & 1) ? kOob : goff[r], ck * (CK * 4), 0));
+            if (++ck == n) {                    // the next request belongs to the next tile
+                ck = 0;
+                tile += S;
+                --tiles_left;
+                rs = x_desc(tile);
+            }
+        };
+        auto store_chunk = [&](const f32x4 (&src)[NP], const int buf) {
+            if (SEAM_SXPC_ABL & 1) return;
+#pragma unroll
+            for (int r = 0; r < NP; ++r) {
+                u32x2 q0, q1, q2;
+                if (SEAM_SXPC_ABL & 4) {
+                    q0[0] = __builtin_bit_cast(unsigned, src[r][0]); q0[1] = __builtin_bit_cast(unsigned, src[r][1]);
+                    q1[0] = __builtin_bit_cast(unsigned, src[r][2]); q1[1] = __builtin_bit_cast(unsigned, src[r][3]); q2 = q0;
+                } else {
+                    split3_bf16(src[r], q0, q1, q2);
+                }
+                *reinterpret_cast<u32x2 LDSQ*>(lp[r] + buf * ABUF) = q0;
+                *reinterpret_cast<u32x2 LDSQ*>(lp[r] + buf * ABUF + PLB) = q1;
+                *reinterpret_cast<u32x2 LDSQ*>(lp[r] + buf * ABUF + 2 * PLB) = q2;
+            }
+        };
+        // chunk c (counted over the block's tiles) lives in LDS buffer c & 1 and travels through register set c & 1.  The consumers
+        // pass the barrier of chunk c (B_c) in its last k-step: before it the producers have stored chunk c + 1, behind it nobody
+        // reads chunk c's buffer any more and it takes chunk c + 2.
+        request(rq[0]);                         // chunk 0
+        request(rq[1]);                         // chunk 1
+        store_chunk(rq[0], 0);
+        request(rq[0]);                         // chunk 2
+        LDS_BAR();                              // P: chunk 0 visible
+        for (int c = 0; c < total_chunks; c += 2) {
+            store_chunk(rq[1], 1);              // chunk c + 1
+            request(rq[1]);                     // chunk c + 3
+            LDS_BAR();                          // B_c
+            if (c + 1 >= total_chunks) break;
+            store_chunk(rq[0], 0);              // chunk c + 2
+            request(rq[0]);                     // chunk c + 4
+            LDS_BAR();                          // B_{c+1}
+        }
+    } else {
+        // =================================================== consumer ===================================================
+        const int wn = wave;                    // this wave's 32-channel n-tile of the block's 128
+        f32x16 acc[4];
+        f32x4 af[3][4];                         // [plane][pixel group]: the A fragments of the current k-step
+        f32x4 bf[RB][3];                        // [ring slot][plane]: the wave's weight fragments
+        // the lane's pixel (group 0) at k-half lane >> 5, plane 0, in the chunk buffer ...; groups, planes and k-steps are immediates
+        const LDSQ char* ac = (const LDSQ char*)smem + (lane & 31) * ROWB + (lane >> 5) * 16;      // ... of the current chunk
+        const LDSQ char* an = ac + ABUF;                                                            // ... of the next one
+        const int nsteps = p.C >> 4;
+        const int wtile_bytes = nsteps * 3072;  // one n-tile's weights: C / 16 k-steps x three 1-KiB planes
+        const int blane = lane * 16;
+        __amdgpu_buffer_rsrc_t w_rsrc;
+        int tm_n = 0, tn_n = 0;                 // m-tile / n-tile of the tile whose weights are in the ring
+        auto load_b = [&](const int slot, const int step) {
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                bf[slot][pl] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, blane, (step * 3 + pl) * 1024, 0));
+        };
+        auto ring_preload = [&](const int tl) {
+            tm_n = fdivu(tl, p.tiles_n, p.m_tiles_n);
+            tn_n = __builtin_amdgcn_readfirstlane(tl - tm_n * p.tiles_n);
+            tm_n = __builtin_amdgcn_readfirstlane(tm_n);
+            w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w + (size_t)(tn_n * 4 + wn) * wtile_bytes), 0, wtile_bytes, 0x00020000);
+#pragma unroll
+            for (int s = 0; s < RB; ++s) { SB(); load_b(s, s); }
+            SB();
+        };
+        // The epilogue's row layout (after the wave-private transpose): lane -> pixel (lane >> 3) + 8 i of a 32-pixel group, 16-byte piece
+        // (lane & 7) of the wave's 32 channels: eight lanes write one pixel's 128 bytes -- a full line per pixel.
+        const unsigned ooff = (unsigned)((lane >> 3) * p.K * 4 + (32 * wn + 4 * (lane & 7)) * 4);
+        LDSQ char* const tw = (LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane & 31) * TROW + (lane >> 5) * 16;   // accumulator layout: piece 2 qd + h
+        const LDSQ char* const tr = (const LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane >> 3) * TROW + (lane & 7) * 16;
+        const int K32 = 32 * p.K * 4, K8 = 8 * p.K * 4;        // byte steps of a 32-pixel group / of 8 pixels
+        int tile = tile0;
+        ring_preload(tile);
+        f32x4 rv[4][4], sc, sh;
+        LDS_BAR();                              // P: chunk 0 is in LDS
+        for (int k = 0; k < ntiles; ++k) {
+            const int tm_k = tm_n, tn_k = tn_n;             // (wave-uniform by construction)
+            const int rows = min(BM, p.M - tm_k * BM);
+            const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)((char*)p.y + (size_t)tm_k * BM * out_row), 0, (int)(rows * out_row), 0x00020000);
+            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)((const char*)(p.res ? p.res : p.y) + (size_t)tm_k * BM * out_row), 0, (int)(rows * out_row), 0x00020000);
+            const unsigned ocol = ooff + (unsigned)(tn_k * 512);
+            // the tile's first fragments (a tile's last chunk reads them ahead like every chunk, but they are not kept across the
+            // epilogue, which needs the registers)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) af[pl][m] = *reinterpret_cast<const f32x4 LDSQ*>(ac + m * (32 * ROWB) + pl * PLB);
+            for (int t = 0; t < n; ++t) {
+                const bool last = t == n - 1;
+                if (last) {
+                    // the tile's epilogue vectors (this lane's four channels in the row layout) without a branch of their own (a
+                    // missing vector reads the weights instead and is replaced by 1 / 0), and the residual pieces of the first RVA
+                    // pixel groups (row layout): in flight under the tile's last chunk
+                    const int ch = tn_k * 128 + 32 * wn + 4 * (lane & 7);
+                    const f32x4 a = *reinterpret_cast<const f32x4*>((p.scale ? p.scale : (const float*)p.w) + ch);
+                    const f32x4 b = *reinterpret_cast<const f32x4*>((p.shift ? p.shift : (const float*)p.w) + ch);
+                    sc = a;                     // (replaced in the epilogue: a select here would wait for the loads at once)
+                    sh = b;
+                    if (p.res) {
+#pragma unroll
+                        for (int m = 0; m < RVA; ++m)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, ocol + m * K32 + i * K8, 0, 0));
+                    }
+                }
+                auto read_a = [&](const int pl, const int m, const int ks) -> f32x4 {       // ks = KS: the next chunk's first fragments
+                    return *reinterpret_cast<const f32x4 LDSQ*>((ks == KS ? an : ac + ks * 32) + m * (32 * ROWB) + pl * PLB);
+                };
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    // (activation piece, weight piece) by descending i + j: entries 3..8 of conv_igemm_sx's T9
+                    constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};
+                    constexpr int LAST[3] = {5, 3, 0};      // the term after which plane pa's fragments of this k-step are history
+#pragma unroll
+                    for (int tq = 0; tq < 6; ++tq) {
+                        const int pa = TA[tq], pb = TB[tq];
+                        if (ks == KS - 1 && tq == 1) {
+                            // B_c: the next chunk is in the other buffer; this one (read to its end a k-step ago) may be overwritten
+                            SB();
+                            LDS_BAR();
+                            SB();
+#if !(SEAM_SXPC_ABL & 8)
+#pragma unroll
+                            for (int m = 0; m < 4; ++m) af[2][m] = read_a(2, m, KS);
+#endif
+                        }
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) {
+                            SB();
+                            // roles swapped: rows = output channels (the weight fragment), columns = pixels (the activation fragment)
+                            if (ks == 0 && tq == 0 && t == 0) {     // the tile's first step multiplies into a constant zero: no accumulator clears
+                                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf[ks][pb]), __builtin_bit_cast(bf16x8, af[pa][m]), z, 0, 0, 0);
+                            } else {
+                                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf[ks][pb]), __builtin_bit_cast(bf16x8, af[pa][m]), acc[m], 0, 0, 0);
+                            }
+                            SB();
+#if !(SEAM_SXPC_ABL & 8)
+                            // the next k-step's fragment of this plane and group, behind the plane's last product of this k-step
+                            if (tq == LAST[pa] && !(ks == KS - 1 && tq == 0)) af[pa][m] = read_a(pa, m, ks + 1);
+#endif
+                        }
+                    }
+                    SB();
+#if !(SEAM_SXPC_ABL & 2)
+                    load_b(ks, min(t * KS + ks + RB, nsteps - 1));      // (past the tile's end: its last step again, never used)
+#endif
+                }
+                SB();
+                // the buffers change roles (three v_mov per chunk of 96 MFMAs; the k-steps themselves have no vector-ALU instruction)
+                const LDSQ char* const sw = ac;
+                ac = an;
+                an = sw;
+            }
+            // ---- epilogue, in registers ----
+            tile += S;
+            ring_preload(tile);                 // the next tile's first weight fragments: in flight under the arithmetic (past the
+                                                // block's last tile: a tile that is never multiplied -- inside the pack, or dropped)
+            if (!p.scale) sc = f32x4{1.f, 1.f, 1.f, 1.f};
+            if (!p.shift) sh = f32x4{0.f, 0.f, 0.f, 0.f};
+            auto finish_tile = [&](auto res_c, auto relu_c) {    // flags as compile-time constants: four straight-line copies
+                constexpr bool RES = decltype(res_c)::value, RELU = decltype(relu_c)::value;
+                if (RES) {
+#pragma unroll
+                    for (int m = RVA; m < 4; ++m)   // the pixel groups the last chunk had no registers for
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, ocol + m * K32 + i * K8, 0, 0));
+                    // (one wait for everything that came from memory, before the first store)
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) asm volatile("" :: "v"(rv[m][0]), "v"(rv[m][1]), "v"(rv[m][2]), "v"(rv[m][3]));
+                }
+                // accumulator layout (lane = pixel, register quad = 4 consecutive channels) -> this wave's private [32 pixels][32 channels]
+                // rows (two buffers: group m + 1 is written before group m is read back) -> row layout: 8 lanes per pixel
+                auto put = [&](const int m) {
+#pragma unroll
+                    for (int qd = 0; qd < 4; ++qd)
+                        *reinterpret_cast<f32x4 LDSQ*>(tw + (m & 1) * TBUF + qd * 32) =
+                            f32x4{acc[m][4 * qd], acc[m][4 * qd + 1], acc[m][4 * qd + 2], acc[m][4 * qd + 3]};
+                };
+                put(0);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    if (m + 1 < 4) put(m + 1);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        f32x4 v = *reinterpret_cast<const f32x4 LDSQ*>(tr + (m & 1) * TBUF + i * (8 * TROW));
+                        v = v * sc + sh;                    // (no scale: sc = 1 -- the same value as v + sh)
+                        if (RES) v += rv[m][i];
+                        if (RELU) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                        }
+                        // (vector offset + immediate only: with a SCALAR offset hipcc puts the next piece's arithmetic right behind a
+                        // 16-byte store without the wait state its data registers need)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, ocol + m * K32 + i * K8, 0, 0);
+                    }
+                }
+            };
+            if (p.res) {
+                if (p.relu) finish_tile(std::true_type{}, std::true_type{}); else finish_tile(std::true_type{}, std::false_type{});
+            } else {
+                if (p.relu) finish_tile(std::false_type{}, std::true_type{}); else finish_tile(std::false_type{}, std::false_type{});
+            }
+        }
+    }
+}
+
+// [K, C] fp32 (row-major) -> three bf16 planes in fragment order [K/128][4][C/16][3][64][8]
+__global__ void sxpc_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int K, int C) {
+    const size_t total = (size_t)K * C / 8;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        seam_pack::sxpc_item(w, out, i, C);
+}
+
+int sxpc_plan(SxpcArgs& a, long long M, int C, int K) {
+    if (M <= 0 || C < 256 || (C % CK) || K < 128 || (K % 128)) return 1;
+    if ((unsigned long long)BM * C * 4 >= kOob || (unsigned long long)BM * K * 4 >= kOob) return 1;
+    if ((unsigned long long)(C / 16) * 3072 >= kOob) return 1;
+    const long long tiles_m = (M + BM - 1) / BM;
+    const long long total = tiles_m * (K / 128);
+    if (total >= (1LL << 24) || M >= (1LL << 31)) return 1;
+    a.M = (int)M; a.C = C; a.K = K;
+    a.tiles_n = K / 128; a.nchunks = C / CK; a.total_tiles = (int)total;
+    // (the producers and the ring preload run one grid stride past the block's last tile: numerators below 2 * total + 2^16)
+    if (!seam_fastdiv::exact(a.tiles_n, 2ull * total + (1ull << 16))) return 1;
+    a.m_tiles_n = seam_fastdiv::magic(a.tiles_n);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* 1 when seam_conv1x1_sxpc takes this layer (1x1 / stride 1 / pad 0; C >= 256 and a multiple of 64; K a multiple of 128; M >= 1), else 0 */
+int seam_conv1x1_sxpc_supported(long long M, int C, int K) {
+    SxpcArgs a;
+    return sxpc_plan(a, M, C, K) == 0 ? 1 : 0;
+}
+
+long long seam_conv1x1_sxpc_weight_bytes(int K, int C) { return (long long)K * C * 6; }
+
+/* w: [K, C] fp32 row-major (a 1x1 OIHW weight) -> the kernel's three bf16 planes in fragment order */
+int seam_pack_conv1x1_weight_sxpc(const float* w, void* w_packed, int K, int C, void* stream) {
+    SxpcArgs a;
+    if (sxpc_plan(a, 1, C, K)) return (int)hipErrorInvalidValue;      // the kernel's own rule for (C, K)
+    const size_t total = (size_t)K * C / 8;
+    const unsigned grid = seam_launch::grid256(total);
+    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
+    return (int)hipGetLastError();
+}
+
+/* y[M, K] = act(scale * (x[M, C] . w^T) + shift + residual), fp32 in / out, six-term split-bf16 products: the bits of seam_conv2d_sx
+ * with terms = 6 on the same 1x1 layer; relu 0 | 1 */
+int seam_conv1x1_sxpc(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                      long long M, int C, int K, int relu, void* stream) {
+    SxpcArgs a;
+    if ((relu != 0 && relu != 1) || sxpc_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
+    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

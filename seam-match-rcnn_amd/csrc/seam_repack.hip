@@ -3,7 +3,8 @@
 // form needs and the job's block range.  A block finds its job by binary search over the first blocks and grid-strides over the
 // job's items with the item functions of seam_pack_items.h -- the functions the per-layer pack kernels run, so the bytes written
 // are those of the per-layer ABI calls.  The three-plane split twin (SEAM_REPACK_SPLIT3) computes each value of the exact pack
-// from the source and splits it, so it does not wait for another job of the same launch.
+// from the source and splits it, so it does not wait for another job of the same launch; the fragment-order split form of
+// conv1x1_sxpc (SEAM_REPACK_SXPC) reads the row-major source itself.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "seam_device.h"
@@ -48,6 +49,9 @@ __global__ __launch_bounds__(256) void repack_many_kernel(const seam_repack_job_
     case SEAM_REPACK_PC:
         for (size_t i = i0; i < total; i += step) seam_pack::pwpc_item(src, (float*)j.dst, i, j.Cstore);
         break;
+    case SEAM_REPACK_SXPC:
+        for (size_t i = i0; i < total; i += step) seam_pack::sxpc_item(src, (unsigned short*)j.dst, i, j.Cstore);
+        break;
     case SEAM_REPACK_SW:
         for (size_t i = i0; i < total; i += step) seam_pack::sw_item(src, j.scale, (float*)j.dst, i, j.Cstore);
         break;
@@ -81,6 +85,9 @@ long long job_items(seam_repack_job_t& j) {
     case SEAM_REPACK_PC:
         if (!plain || (j.K % 128) || (j.Cstore % 128) || (((uintptr_t)j.src | (uintptr_t)j.dst) & 15)) return 0;
         return (long long)j.K * j.Cstore / 4;
+    case SEAM_REPACK_SXPC:
+        if (!plain || !seam_conv1x1_sxpc_supported(1, j.Cstore, j.K)) return 0;
+        return (long long)j.K * j.Cstore / 8;
     case SEAM_REPACK_SW:
         if (!plain) return 0;
         return (long long)j.K * j.Cstore;

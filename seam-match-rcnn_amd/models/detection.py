@@ -58,6 +58,8 @@ def adt(module) -> torch.dtype:
 # model with ``set_split_f32``; SEAM_SPLIT_F32=0 for the process) switches it off and restores the exact-fp32 kernels bit for bit.
 # Classes: c1 = bottleneck 1x1 reductions, c3 = 1x1 expansions with their residual (C >= SPLIT_C3_MIN_C), c2s2 = the three
 # stride-2 3x3s.  The two-source shortcut GEMMs and the FPN laterals keep their fused fp32 kernels (the split kernel has neither form).
+# The long 1x1 layers of c1 / c3 (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel conv1x1_sxpc (ops.SXPC;
+# the same bits as conv_igemm_sx), the others on conv_igemm_sx.
 SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
 SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
 SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; the short reductions of layer1 / layer2 (C = 64, 128) are faster on conv1x1_sw

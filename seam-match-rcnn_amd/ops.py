@@ -66,6 +66,7 @@ class PackedConv:
     wh: Optional[torch.Tensor] = None   # fp16 stride-1 3x3 layers (C, K multiples of 128, or C = K = 64): fragment-order weights of seam_conv3x3_f16pc
     wsh: Optional[torch.Tensor] = None  # fp16 1x1 / stride-1 layers (C multiple of 64, <= 512): row-major fp16 [K, C] weights of seam_conv1x1_swh_f16
     wph: Optional[torch.Tensor] = None  # fp16 1x1 / stride-1 layers with C >= 512 (a multiple of 256), K a multiple of 128: fragment-order weights of seam_conv1x1_f16pc
+    wx: Optional[torch.Tensor] = None   # SX6 1x1 / stride-1 layers with C >= 256 (a multiple of 64), K a multiple of 128: three bf16 planes in fragment order (seam_conv1x1_sxpc)
 
 
 BX3 = "bf16x3"      # fp32 activations, split-bf16 operands (3 bf16 MFMAs per product, fp32 accumulate)
@@ -93,6 +94,14 @@ PWPC = _os.environ.get("SEAM_PWPC", "1") != "0"
 SWH = _os.environ.get("SEAM_PWH", "1") != "0"
 PWHPC = _os.environ.get("SEAM_PWHPC", "1") != "0"       # conv1x1_f16pc: the long-reduction fp16 1x1 layers (csrc/seam_pwhpc.hip)
 PWHPC_MIN_C = int(_os.environ.get("SEAM_PWHPC_MIN_C", "1024"))  # reductions from this length on take it (C = 512 stays on conv1x1_swh: 1.04-1.2x alone, nothing in the step)
+# split-bf16 path (SX6): the long 1x1 / stride-1 layers through the producer / consumer kernel (csrc/seam_pwsx.hip); SEAM_SXPC=0 keeps
+# them on conv_igemm_sx.  The two kernels give the same bits, so the choice may depend on the batch: launches of at least
+# SXPC_MIN_TILES tiles of 128 pixels x 128 channels take it -- every shape of a step does (1.05-1.26x); with fewer tiles than CUs the
+# persistent blocks' long tiles lose to the implicit GEMM's smaller ones (196 tiles: 1.16x, 100 tiles: 0.87x, 40 tiles: 0.66x;
+# profiles/sxpc_layer_ab.txt).  SXPC_RULE = False: every supported shape (tests, tools/sxpc_ab.py).
+SXPC = _os.environ.get("SEAM_SXPC", "1") != "0"
+SXPC_MIN_TILES = int(_os.environ.get("SEAM_SXPC_MIN_TILES", "196"))
+SXPC_RULE = True
 F16PC_RULE = True      # dispatch by seam_conv3x3_f16pc_pays (False: every supported shape -- tests, tools/f16pc_ab.py)
 
 
@@ -212,7 +221,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
     epv = 8 if dtype == F16 else 4
     cs = cstore if cstore is not None else ((cin + epv - 1) // epv) * epv
     rows = lib.seam_conv_rows_padded(K)
-    u = u24 = wh = None
+    u = u24 = wh = wx = None
     if dtype == F32:
         kred = lib.seam_conv_kred(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F32, device=weight.device)
@@ -233,6 +242,11 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         tmp = torch.empty((rows, kred), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_conv_weight_sx(_ptr(weight), _ptr(wp), _ptr(tmp), K, cin, R, S, cs, mode, _stream()),
                       "seam_pack_conv_weight_sx")
+        if (SXPC and dtype == SX6 and mode == 0 and not is_linear and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin
+                and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K)):
+            wx = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
+            _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wx), K, cs, _stream()),
+                          "seam_pack_conv1x1_weight_sxpc")
     else:
         kred = lib.seam_conv_kred_f16(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F16, device=weight.device)
@@ -285,7 +299,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         wph = torch.empty((int(lib.seam_conv1x1_f16pc_weight_halves(K, cs)),), dtype=F16, device=weight.device)
         _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wph), K, cs, _stream()),
                       "seam_pack_conv1x1_weight_f16pc")
-    pc = PackedConv(wp, scale, shift, K, cs, R, S, stride, pad, cin, dtype, u, u24, wn, ws, shift_sw, wq, wh, wsh, wph)
+    pc = PackedConv(wp, scale, shift, K, cs, R, S, stride, pad, cin, dtype, u, u24, wn, ws, shift_sw, wq, wh, wsh, wph, wx)
     if _PACK_RECORDER is not None:
         _PACK_RECORDER.records.append((weight, bias, bn, mode, pc))
     return pc
@@ -519,7 +533,12 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
              and lib.seam_conv1x1_f16pc_supported(n * h * w, c, pc.K) == 1)
     swh = (not pwhpc and pc.dtype == F16 and pc.wsh is not None and SWH and out_hw is None and not out_f32 and h * w >= SW_MIN_HW
            and relu in (0, 1, False, True))
-    if pwhpc:
+    sxpc = (pc.dtype == SX6 and pc.wx is not None and SXPC and out_hw is None and relu in (0, 1, False, True)
+            and (-(-(n * h * w) // 128) * (pc.K // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_supported(n * h * w, c, pc.K) == 1)
+    if sxpc:
+        _native.check(lib.seam_conv1x1_sxpc(_ptr(x), _ptr(pc.wx), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y), n * h * w, c, pc.K,
+                                            1 if relu else 0, _stream()), "seam_conv1x1_sxpc")
+    elif pwhpc:
         _native.check(lib.seam_conv1x1_f16pc(_ptr(x), _ptr(pc.wph), _ptr(pc.scale), _ptr(pc.shift), None, _ptr(y), n * h * w, c, pc.K,
                                              1 if relu else 0, _stream()), "seam_conv1x1_f16pc")
     elif swh:
@@ -567,7 +586,9 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
         e1.record()
         tile = lib.seam_conv_tile_taps(3 if pc.dtype in _SX_TERMS else 2 if pc.dtype == BX3 else 1 if pc.dtype == F16 else 0,
                                        n * ho * wo, pc.K, pc.R * pc.S)
-        if pwhpc:
+        if sxpc:
+            variant = "conv1x1_sxpc"
+        elif pwhpc:
             variant = "conv1x1_f16pc"
         elif swh:
             variant = _swh_variant(lib, n * h * w, c, pc.K)
@@ -2180,7 +2201,10 @@ class PackPlan:
                                K=pc.K, Cin=cin, R=R, S=S, Cstore=cs, mode=md)
 
         if pc.dtype in _SX_TERMS:
-            return [job(N.REPACK_SPLIT3, pc.w, pc.R, pc.S, md=mode)]
+            jobs = [job(N.REPACK_SPLIT3, pc.w, pc.R, pc.S, md=mode)]
+            if pc.wx is not None:
+                jobs.append(job(N.REPACK_SXPC, pc.wx))
+            return jobs
         if pc.dtype != F32 or pc.wh is not None or pc.wsh is not None or pc.wph is not None:
             raise NotImplementedError(f"PackPlan: {path}: only fp32 packs are refreshed in place (pass refresh_packs=False)")
         jobs = [job(N.REPACK_IGEMM, pc.w, pc.R, pc.S, md=mode)]
