@@ -7,6 +7,7 @@ fp32 contiguous tensors and raises otherwise: there is no CPU / eager fallback.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -105,22 +106,17 @@ SXPC_RULE = True
 F16PC_RULE = True      # dispatch by seam_conv3x3_f16pc_pays (False: every supported shape -- tests, tools/f16pc_ab.py)
 
 
-def _pack_wino(lib, weight: torch.Tensor, K: int, cin: int, cs: int, mode: int) -> Optional[torch.Tensor]:
+def _pack_wino(lib, weight: torch.Tensor, K: int, cin: int, cs: int, mode: int):
+    """Winograd weights of a stride-1 3x3 fp32 layer -> (u of F(2x2,3x3), u24 of F(2x4,3x3)); (None, None) where unsupported."""
     if not lib.seam_wino_supported(cs, K, 3, 3, 1):
-        return None
+        return None, None
     u = torch.empty((int(lib.seam_wino_weight_floats(K, cs)),), dtype=F32, device=weight.device)
     _native.check(lib.seam_pack_conv_weight_wino_f32(_ptr(weight), _ptr(u), K, cin, cs, mode, _stream()),
                   "seam_pack_conv_weight_wino_f32")
-    return u
-
-
-def _pack_wino24(lib, weight: torch.Tensor, K: int, cin: int, cs: int, mode: int) -> Optional[torch.Tensor]:
-    if not lib.seam_wino_supported(cs, K, 3, 3, 1):
-        return None
-    u = torch.empty((int(lib.seam_wino24_weight_floats(K, cs)),), dtype=F32, device=weight.device)
-    _native.check(lib.seam_pack_conv_weight_wino24_f32(_ptr(weight), _ptr(u), K, cin, cs, mode, _stream()),
+    u24 = torch.empty((int(lib.seam_wino24_weight_floats(K, cs)),), dtype=F32, device=weight.device)
+    _native.check(lib.seam_pack_conv_weight_wino24_f32(_ptr(weight), _ptr(u24), K, cin, cs, mode, _stream()),
                   "seam_pack_conv_weight_wino24_f32")
-    return u
+    return u, u24
 
 
 # F(2x4,3x3) (csrc/seam_wino24.hip): 0 = never, 1 = where it issues fewer MFMAs than F(2x2,3x3) (x WINO24_MARGIN), 2 = always
@@ -173,24 +169,108 @@ def _sw_ok(pc: "PackedConv", h: int, w: int) -> bool:
     return SW and pc.ws is not None and h * w >= SW_MIN_HW
 
 
+def _swh_ok(pc: "PackedConv", h: int, w: int) -> bool:
+    return SWH and pc.wsh is not None and h * w >= SW_MIN_HW
+
+
+def _wino_form(lib, pc: "PackedConv", n, h, w, c, pad) -> int:
+    """Winograd form of a stride-1 3x3 fp32 layer on an h x w map: 0 = none (implicit GEMM), 1 = F(2x2,3x3), 2 = F(2x4,3x3)."""
+    if pc.u is None or not WINOGRAD or not _wino_pays(lib, n, h, w, c, pc.K, pad):
+        return 0
+    return 2 if pc.u24 is not None and WINOGRAD24 and _wino24_pays(lib, n, h, w, c, pc.K, pad) else 1
+
+
+def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out_f32) -> str:
+    """The kernel one ``conv2d`` launch takes.  First match wins; this order IS the precedence.  Integers, bools, which pack fields
+    exist, the knobs above (read now: tests and tools assign them) and the library's host predicates -- no tensor data, no stream."""
+    c, k, dt = pc.Cstore, pc.K, pc.dtype
+    if (dt == SX6 and pc.wx is not None and SXPC and not cropped and relu in (0, 1, False, True)
+            and (-(-(n * h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_supported(n * h * w, c, k) == 1):
+        return "sxpc"
+    f16k = dt == F16 and not out_f32 and relu in (0, 1, False, True)      # what the fp16 routes below need: fp16 out, ReLU a flag
+    if f16k and not cropped:
+        if (pc.wph is not None and PWHPC and not has_residual and c >= PWHPC_MIN_C and h * w >= SW_MIN_HW
+                and lib.seam_conv1x1_f16pc_supported(n * h * w, c, k) == 1):
+            return "pwhpc"
+        if _swh_ok(pc, h, w):
+            return "swh"
+    if pc.wn is not None and NARROW and not has_residual and not cropped:
+        return "narrow"
+    if dt == F32 and not cropped:
+        if _sw_ok(pc, h, w):
+            return "sw"
+        if pc.wq is not None and PWPC and h * w >= PWPC_MIN_HW and lib.seam_conv1x1_pc_supported(n * h * w, c, k) == 1:
+            return "pwpc"
+        form = _wino_form(lib, pc, n, h, w, c, pc.pad)
+        if form:
+            return "wino24" if form == 2 else "wino"
+    if cropped:            # (fp32 or fp16: conv2d has checked)
+        return "crop"
+    if (f16k and pc.wh is not None and F16PC and not has_residual
+            and (lib.seam_conv3x3_f16pc_pays if F16PC_RULE else lib.seam_conv3x3_f16pc_supported)(n, h, w, c, k, pc.pad) == 1):
+        return "f16pc"
+    return "igemm"          # (like "crop": the instantiation is the pack's dtype)
+
+
+# routes of one instantiation: their CONV_TRACE labels
+_ROUTE_LABEL = {"sxpc": "conv1x1_sxpc", "pwhpc": "conv1x1_f16pc", "narrow": "linear_narrow", "pwpc": "conv1x1_pc", "f16pc": "conv3x3_f16pc"}
+
+
+def _conv_variant(lib, route: str, pc: "PackedConv", n, h, w, ho, wo) -> str:
+    """The kernel's name for ``CONV_TRACE``, template arguments included, from the route ``_conv_route`` chose."""
+    c, k = pc.Cstore, pc.K
+    if route in _ROUTE_LABEL:
+        return _ROUTE_LABEL[route]
+    if route in ("sw", "swh"):
+        return _sw_variant(lib, route, n * h * w, c, k)
+    if route == "wino24":
+        return ("conv3x3_wino24pc" if lib.seam_wino24_form(n, h, w, c, k, pc.pad) == 1
+                else f"conv3x3_wino24<{lib.seam_wino24_variant(n, h, w, c, k, pc.pad)}>")
+    if route == "wino":
+        return f"conv3x3_wino<{lib.seam_wino_tile_variant(n, h, w, c, k, pc.pad)}>"
+    return _igemm_variant(lib, pc.dtype, n * ho * wo, k, pc.R * pc.S)      # "igemm" and "crop" (the crop kernels are its instantiations)
+
+
 def _sw_launch(lib, x, x2, pc, residual, y, m, c1, c2, relu, res_mode=0, ho=0, wo=0, rh=0, rw=0):
     _native.check(lib.seam_conv1x1_sw_f32(_ptr(x), _ptr(x2), _ptr(pc.ws), _ptr(pc.shift_sw), _ptr(residual), _ptr(y), m, c1, c2, pc.K,
                                           int(relu), res_mode, ho, wo, rh, rw, _stream()), "seam_conv1x1_sw_f32")
 
 
-def _swh_variant(lib, m, c, k) -> str:
-    cfg = int(lib.seam_conv1x1_swh_config(m, c, 0, k))
-    return f"conv1x1_swh<{cfg // 100},{cfg % 100}>"
+def _sw_variant(lib, route: str, m, c, k) -> str:
+    """Label of the weights-stationary pointwise kernel of route "sw" (fp32) / "swh" (fp16)."""
+    cfg = int((lib.seam_conv1x1_sw_config if route == "sw" else lib.seam_conv1x1_swh_config)(m, c, 0, k))
+    return f"conv1x1_{route}<{cfg // 100},{cfg % 100}>"
 
 
-def _sw_variant(lib, m, c, k) -> str:
-    cfg = int(lib.seam_conv1x1_sw_config(m, c, 0, k))
-    return f"conv1x1_sw<{cfg // 100},{cfg % 100}>"
+def _igemm_variant(lib, dt, m, k, taps: int = 1, dual: bool = False) -> str:
+    """Label of the implicit GEMM of precision ``dt`` (``dual``: ``conv2d_dual`` lists 128 x 128 where the tile table says 256 rows)."""
+    tile = lib.seam_conv_tile_taps(3 if dt in _SX_TERMS else 2 if dt == BX3 else 1 if dt == F16 else 0, m, k, taps)
+    if dual and tile // 1000 == 256:
+        tile = 128128
+    if dt in _SX_TERMS:
+        return f"conv_igemm_sx<{tile // 1000},{tile % 1000},{_SX_TERMS[dt]}>"
+    if dt == BX3:
+        return f"conv_igemm_bx3<{tile // 1000},{tile % 1000}>"
+    return f"conv_igemm<{'float' if dt == F32 else '_Float16'},{tile // 1000},{tile % 1000}>"
 
 
 # When set to a list, every conv launch is bracketed by HIP events on the launch stream and
-# (variant, algorithmic_flops, start_event, end_event) is appended (bench.py's roofline leg).
+# (variant, algorithmic_flops, start_event, end_event, (n, h, w, c, k, r, stride), bytes_moved) is appended (bench.py's roofline leg).
 CONV_TRACE = None
+
+
+def _trace_begin(variant: str, flops: float, shape: tuple, nbytes: float):
+    """Open the event bracket of one traced launch.  A launch site calls this only when ``CONV_TRACE`` is set --
+    ``tr = CONV_TRACE is not None and _trace_begin(...)`` -- so an untraced launch pays one global read and one comparison."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    tr = (CONV_TRACE, (variant, flops, e0, e1, shape, nbytes))
+    e0.record()
+    return tr
+
+
+def _trace_end(tr) -> None:
+    tr[1][3].record()
+    tr[0].append(tr[1])
 
 
 def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None, *, stride: int = 1,
@@ -205,13 +285,12 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
             pass of the heads (autograd.py) packs per step and keeps the bit-exact fp32 fma chain of the implicit GEMM."""
     lib = _native.lib()
     weight = _req(weight.detach(), name="weight")
-    is_linear = False
+    is_linear = not transposed2x2 and weight.dim() == 2      # a Linear runs on 1x1 maps: no weight form of the map-sized pointwise kernels
     if transposed2x2:
         cin, cout = weight.shape[0], weight.shape[1]
         K, R, S, mode = 4 * cout, 1, 1, 1
     else:
-        is_linear = weight.dim() == 2      # a Linear runs on 1x1 maps: no weight form of the map-sized pointwise kernels
-        if weight.dim() == 2:
+        if is_linear:
             weight = weight[:, :, None, None]
         if weight.dim() == 3:
             weight = weight[:, :, :, None]
@@ -221,15 +300,18 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
     epv = 8 if dtype == F16 else 4
     cs = cstore if cstore is not None else ((cin + epv - 1) // epv) * epv
     rows = lib.seam_conv_rows_padded(K)
-    u = u24 = wh = wx = None
+    plain = R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin      # a plain 1x1 layer: what every pointwise form below needs
+    conv1x1 = plain and mode == 0 and not is_linear
+    # the weight as a row-major fp32 [K, Cin] matrix, made on first use; of a Conv2d / Linear weight it is a view: the SAME storage
+    rows_kc = functools.cache(lambda: (weight.permute(2, 3, 1, 0).reshape(K, cin) if transposed2x2 else weight.reshape(K, cin)).to(F32).contiguous())
+    u = u24 = wh = wx = wn = ws = shift_sw = wq = wsh = wph = None      # the optional forms: each set below where the layer is eligible
     if dtype == F32:
         kred = lib.seam_conv_kred(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_conv_weight_f32(_ptr(weight), _ptr(wp), K, cin, R, S, cs, mode, _stream()),
                       "seam_pack_conv_weight_f32")
         if wino and mode == 0 and R == 3 and S == 3 and stride == 1:
-            u = _pack_wino(lib, weight, K, cin, cs, 0)
-            u24 = _pack_wino24(lib, weight, K, cin, cs, 0) if u is not None else None
+            u, u24 = _pack_wino(lib, weight, K, cin, cs, 0)
     elif dtype == BX3:
         kred = lib.seam_conv_kred(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F32, device=weight.device)      # opaque: [32 hi | 32 lo] bf16 per 128-byte row-chunk
@@ -242,11 +324,9 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         tmp = torch.empty((rows, kred), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_conv_weight_sx(_ptr(weight), _ptr(wp), _ptr(tmp), K, cin, R, S, cs, mode, _stream()),
                       "seam_pack_conv_weight_sx")
-        if (SXPC and dtype == SX6 and mode == 0 and not is_linear and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin
-                and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K)):
+        if SXPC and dtype == SX6 and conv1x1 and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K):
             wx = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
-            _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wx), K, cs, _stream()),
-                          "seam_pack_conv1x1_weight_sxpc")
+            _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(rows_kc()), _ptr(wx), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc")
     else:
         kred = lib.seam_conv_kred_f16(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F16, device=weight.device)
@@ -269,37 +349,25 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         shift = shift.contiguous()
     elif bias is not None:
         shift = bias.contiguous()
-    wn = None
     # (fp32 only: the same kernel on fp16 rows -- 8-byte loads, widened -- measured 1.7 % SLOWER end to end than the 128x64 fp16 tile)
-    if (dtype == F32 and mode == 0 and R == 1 and S == 1 and stride == 1 and pad == 0 and scale is None and cs == cin
-            and lib.seam_linear_narrow_supported(cs, K)):
+    if dtype == F32 and mode == 0 and plain and scale is None and lib.seam_linear_narrow_supported(cs, K):
         wn = torch.empty((64 * cs,), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_linear_narrow_f32(_ptr(weight), _ptr(wn), K, cs, _stream()), "seam_pack_linear_narrow_f32")
-    ws = shift_sw = None
-    if (dtype == F32 and mode in (0, 1) and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin
-            and lib.seam_conv1x1_sw_config(1 << 20, cs, 0, K)):
+    if dtype == F32 and mode in (0, 1) and plain and lib.seam_conv1x1_sw_config(1 << 20, cs, 0, K):
         # weights-stationary pointwise kernel (csrc/seam_pw.hip): plain row-major [K, C], the per-channel scale folded in
-        wm = (weight.permute(2, 3, 1, 0).reshape(K, cin) if transposed2x2 else weight.reshape(K, cin)).to(F32)
-        ws = (wm * scale[:, None] if scale is not None else wm).contiguous()
+        # (without a scale ``ws`` IS the weight's storage: PackPlan skips its job by comparing the two pointers)
+        ws = (rows_kc() * scale[:, None]).contiguous() if scale is not None else rows_kc()
         shift_sw = shift if shift is not None else torch.zeros((K,), dtype=F32, device=weight.device)
-    wq = None
-    if (PWPC and dtype == F32 and mode == 0 and not is_linear and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin and ws is None
-            and lib.seam_conv1x1_pc_supported(1 << 20, cs, K)):
+    if PWPC and dtype == F32 and conv1x1 and ws is None and lib.seam_conv1x1_pc_supported(1 << 20, cs, K):
         wq = torch.empty((int(lib.seam_conv1x1_pc_weight_floats(K, cs)),), dtype=F32, device=weight.device)
-        _native.check(lib.seam_pack_conv1x1_pc_f32(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wq), K, cs, _stream()),
-                      "seam_pack_conv1x1_pc_f32")
-    wsh = None
-    if (SWH and dtype == F16 and mode in (0, 1) and not is_linear and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin
-            and lib.seam_conv1x1_swh_config(1 << 20, cs, 0, K)):
-        wm = weight.permute(2, 3, 1, 0).reshape(K, cin) if transposed2x2 else weight.reshape(K, cin)
-        wsh = wm.to(F16).contiguous()
-    wph = None
-    if (PWHPC and dtype == F16 and mode == 0 and not is_linear and R == 1 and S == 1 and stride == 1 and pad == 0 and cs == cin
-            and lib.seam_conv1x1_f16pc_supported(1 << 20, cs, K)):
+        _native.check(lib.seam_pack_conv1x1_pc_f32(_ptr(rows_kc()), _ptr(wq), K, cs, _stream()), "seam_pack_conv1x1_pc_f32")
+    if SWH and dtype == F16 and mode in (0, 1) and plain and not is_linear and lib.seam_conv1x1_swh_config(1 << 20, cs, 0, K):
+        wsh = rows_kc().to(F16).contiguous()
+    if PWHPC and dtype == F16 and conv1x1 and lib.seam_conv1x1_f16pc_supported(1 << 20, cs, K):
         wph = torch.empty((int(lib.seam_conv1x1_f16pc_weight_halves(K, cs)),), dtype=F16, device=weight.device)
-        _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(weight.reshape(K, cin).to(F32).contiguous()), _ptr(wph), K, cs, _stream()),
-                      "seam_pack_conv1x1_weight_f16pc")
-    pc = PackedConv(wp, scale, shift, K, cs, R, S, stride, pad, cin, dtype, u, u24, wn, ws, shift_sw, wq, wh, wsh, wph, wx)
+        _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(rows_kc()), _ptr(wph), K, cs, _stream()), "seam_pack_conv1x1_weight_f16pc")
+    pc = PackedConv(wp, scale, shift, K, cs, R, S, stride=stride, pad=pad, Cin=cin, dtype=dtype, u=u, u24=u24, wn=wn, ws=ws,
+                    shift_sw=shift_sw, wq=wq, wh=wh, wsh=wsh, wph=wph, wx=wx)
     if _PACK_RECORDER is not None:
         _PACK_RECORDER.records.append((weight, bias, bn, mode, pc))
     return pc
@@ -321,9 +389,8 @@ def pack_conv_dgrad(weight: torch.Tensor, pad_fwd: int = 0, wino: bool = True) -
     wp = torch.empty((rows, kred), dtype=F32, device=weight.device)
     _native.check(lib.seam_pack_conv_weight_f32(_ptr(weight), _ptr(wp), cin, cout, R, S, cout, 2, _stream()),
                   "seam_pack_conv_weight_f32")
-    u = _pack_wino(lib, weight, cin, cout, cout, 2) if (wino and R == 3) else None
-    u24 = _pack_wino24(lib, weight, cin, cout, cout, 2) if u is not None else None
-    return PackedConv(wp, None, None, cin, cout, R, S, 1, R - 1 - pad_fwd, cout, F32, u, u24)
+    u, u24 = _pack_wino(lib, weight, cin, cout, cout, 2) if (wino and R == 3) else (None, None)
+    return PackedConv(wp, None, None, cin, cout, R, S, stride=1, pad=R - 1 - pad_fwd, Cin=cout, dtype=F32, u=u, u24=u24)
 
 
 def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, R: int, S: int, stride: int = 1, pad: int = 0,
@@ -505,7 +572,6 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
         if pc.dtype not in (F32, F16) or out_f32 or residual is not None or out_hw[0] > ho or out_hw[1] > wo:
             raise ValueError("conv2d: out_hw needs fp32 or fp16 weights, no residual and a size inside the full output")
         ho, wo = int(out_hw[0]), int(out_hw[1])
-    narrow = pc.wn is not None and NARROW and residual is None and out_hw is None
     ydt = F32 if (pc.dtype != F16 or out_f32) else F16
     if out is not None:
         if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != x.device or tuple(out.shape) != (n, ho, wo, pc.K)
@@ -516,53 +582,43 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
         residual = _req(residual, F16 if pc.dtype == F16 else F32, "residual")
         if residual.shape != y.shape:
             raise ValueError("conv2d: residual shape mismatch")
-    trace = CONV_TRACE
-    if trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     lib = _native.lib()
-    wino = pc.dtype == F32 and pc.u is not None and WINOGRAD and out_hw is None and _wino_pays(lib, n, h, w, c, pc.K, pc.pad)
-    wino24 = wino and pc.u24 is not None and WINOGRAD24 and _wino24_pays(lib, n, h, w, c, pc.K, pc.pad)
-    sw = not narrow and pc.dtype == F32 and out_hw is None and _sw_ok(pc, h, w)
-    pwpc = (not narrow and not sw and pc.dtype == F32 and pc.wq is not None and PWPC and out_hw is None and h * w >= PWPC_MIN_HW
-            and lib.seam_conv1x1_pc_supported(n * h * w, c, pc.K) == 1)
-    f16pc = (pc.dtype == F16 and pc.wh is not None and F16PC and residual is None and out_hw is None and not out_f32 and relu in (0, 1, False, True)
-             and (lib.seam_conv3x3_f16pc_pays if F16PC_RULE else lib.seam_conv3x3_f16pc_supported)(n, h, w, c, pc.K, pc.pad) == 1)
-    pwhpc = (pc.dtype == F16 and pc.wph is not None and PWHPC and residual is None and out_hw is None and not out_f32
-             and relu in (0, 1, False, True) and c >= PWHPC_MIN_C and h * w >= SW_MIN_HW
-             and lib.seam_conv1x1_f16pc_supported(n * h * w, c, pc.K) == 1)
-    swh = (not pwhpc and pc.dtype == F16 and pc.wsh is not None and SWH and out_hw is None and not out_f32 and h * w >= SW_MIN_HW
-           and relu in (0, 1, False, True))
-    sxpc = (pc.dtype == SX6 and pc.wx is not None and SXPC and out_hw is None and relu in (0, 1, False, True)
-            and (-(-(n * h * w) // 128) * (pc.K // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_supported(n * h * w, c, pc.K) == 1)
-    if sxpc:
+    route = _conv_route(lib, pc, n, h, w, relu, residual is not None, out_hw is not None, out_f32)
+    tr = CONV_TRACE is not None and _trace_begin(
+        _conv_variant(lib, route, pc, n, h, w, ho, wo), 2.0 * n * ho * wo * pc.K * pc.R * pc.S * (pc.Cin or pc.Cstore), (n, h, w, c, pc.K, pc.R, pc.stride),
+        float(x.element_size() * (x.numel() + pc.w.numel()) + y.element_size() * y.numel()
+              + (x.element_size() * y.numel() if residual is not None else 0)))
+    if route == "sxpc":
         _native.check(lib.seam_conv1x1_sxpc(_ptr(x), _ptr(pc.wx), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y), n * h * w, c, pc.K,
                                             1 if relu else 0, _stream()), "seam_conv1x1_sxpc")
-    elif pwhpc:
+    elif route == "pwhpc":
         _native.check(lib.seam_conv1x1_f16pc(_ptr(x), _ptr(pc.wph), _ptr(pc.scale), _ptr(pc.shift), None, _ptr(y), n * h * w, c, pc.K,
                                              1 if relu else 0, _stream()), "seam_conv1x1_f16pc")
-    elif swh:
+    elif route == "swh":
         _native.check(lib.seam_conv1x1_swh_f16(_ptr(x), None, _ptr(pc.wsh), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                                n * h * w, c, 0, pc.K, 1 if relu else 0, 1 if residual is not None else 0, 0, 0, 0, 0,
                                                _stream()), "seam_conv1x1_swh_f16")
-    elif narrow:
+    elif route == "narrow":
         _native.check(lib.seam_linear_narrow_f32(_ptr(x), _ptr(pc.wn), _ptr(pc.shift), _ptr(y), n * h * w, c, pc.K, int(relu), _stream()),
                       "seam_linear_narrow_f32")
-    elif sw:
+    elif route == "sw":
         _sw_launch(lib, x, None, pc, residual, y, n * h * w, c, 0, relu, 1 if residual is not None else 0)
-    elif pwpc:
+    elif route == "pwpc":
         _native.check(lib.seam_conv1x1_pc_f32(_ptr(x), _ptr(pc.wq), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                               n * h * w, c, pc.K, int(relu), _stream()), "seam_conv1x1_pc_f32")
-    elif wino24:
+    elif route == "wino24":
         _native.check(lib.seam_conv3x3_wino24_f32(_ptr(x), _ptr(pc.u24), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                                   n, h, w, c, pc.K, pc.pad, int(relu), _stream()), "seam_conv3x3_wino24_f32")
-    elif wino:
+    elif route == "wino":
         _native.check(lib.seam_conv3x3_wino_f32(_ptr(x), _ptr(pc.u), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                                 n, h, w, c, pc.K, pc.pad, int(relu), _stream()), "seam_conv3x3_wino_f32")
-    elif out_hw is not None:            # (fp32 or fp16: checked above)
+    elif route == "crop":             # (fp32 or fp16: checked above)
         crop = lib.seam_conv2d_crop_f16 if pc.dtype == F16 else lib.seam_conv2d_crop_f32
         _native.check(crop(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(y), n, h, w, c, pc.K,
                            pc.R, pc.S, pc.stride, pc.pad, ho, wo, int(relu), _stream()), "seam_conv2d_crop")
+    elif route == "f16pc":
+        _native.check(lib.seam_conv3x3_f16pc(_ptr(x), _ptr(pc.wh), _ptr(pc.scale), _ptr(pc.shift), None, _ptr(y),
+                                             n, h, w, c, pc.K, pc.pad, 1 if relu else 0, _stream()), "seam_conv3x3_f16pc")
     elif pc.dtype == F32:
         _native.check(lib.seam_conv2d_f32(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                           n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, int(relu), _stream()),
@@ -575,47 +631,12 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
         _native.check(lib.seam_conv2d_bx3(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                           n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, int(relu), _stream()),
                       "seam_conv2d_bx3")
-    elif f16pc:
-        _native.check(lib.seam_conv3x3_f16pc(_ptr(x), _ptr(pc.wh), _ptr(pc.scale), _ptr(pc.shift), None, _ptr(y),
-                                             n, h, w, c, pc.K, pc.pad, 1 if relu else 0, _stream()), "seam_conv3x3_f16pc")
     else:
         _native.check(lib.seam_conv2d_f16(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                           n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, 1 if relu else 0,
                                           1 if out_f32 else 0, _stream()), "seam_conv2d_f16")
-    if trace is not None:
-        e1.record()
-        tile = lib.seam_conv_tile_taps(3 if pc.dtype in _SX_TERMS else 2 if pc.dtype == BX3 else 1 if pc.dtype == F16 else 0,
-                                       n * ho * wo, pc.K, pc.R * pc.S)
-        if sxpc:
-            variant = "conv1x1_sxpc"
-        elif pwhpc:
-            variant = "conv1x1_f16pc"
-        elif swh:
-            variant = _swh_variant(lib, n * h * w, c, pc.K)
-        elif narrow:
-            variant = "linear_narrow"
-        elif sw:
-            variant = _sw_variant(lib, n * h * w, c, pc.K)
-        elif pwpc:
-            variant = "conv1x1_pc"
-        elif wino24:
-            variant = ("conv3x3_wino24pc" if lib.seam_wino24_form(n, h, w, c, pc.K, pc.pad) == 1
-                       else f"conv3x3_wino24<{lib.seam_wino24_variant(n, h, w, c, pc.K, pc.pad)}>")
-        elif wino:
-            variant = f"conv3x3_wino<{lib.seam_wino_tile_variant(n, h, w, c, pc.K, pc.pad)}>"
-        elif f16pc:
-            variant = "conv3x3_f16pc"
-        elif pc.dtype in _SX_TERMS:
-            variant = f"conv_igemm_sx<{tile // 1000},{tile % 1000},{_SX_TERMS[pc.dtype]}>"
-        elif pc.dtype == BX3:
-            variant = f"conv_igemm_bx3<{tile // 1000},{tile % 1000}>"
-        else:
-            variant = f"conv_igemm<{'float' if pc.dtype == F32 else '_Float16'},{tile // 1000},{tile % 1000}>"
-        es = x.element_size()
-        trace.append((variant, 2.0 * n * ho * wo * pc.K * pc.R * pc.S * (pc.Cin or pc.Cstore), e0, e1,
-                      (n, h, w, c, pc.K, pc.R, pc.stride),
-                      float(es * (x.numel() + pc.w.numel()) + y.element_size() * y.numel()
-                            + (es * y.numel() if residual is not None else 0))))
+    if tr:
+        _trace_end(tr)
     return y
 
 
@@ -633,16 +654,12 @@ def stem_s2d_f16(x: torch.Tensor, w_rows: torch.Tensor, scale: Optional[torch.Te
         raise ValueError("stem_s2d_f16: x must be [N,H2,W2,16] fp16 (padded: +3 cells per direction) and w_rows [64,256] fp16")
     xp = x if padded else torch.nn.functional.pad(x, (0, 0, 2, 1, 2, 1))
     y = torch.empty((n, h2, w2, 64), dtype=F16, device=x.device)
-    trace = CONV_TRACE
-    if trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    tr = CONV_TRACE is not None and _trace_begin("stem_swh<4,2>", 2.0 * n * h2 * w2 * 64 * 16 * 12, (n, h2, w2, 16, 64, 4, 1),
+                                                 float(2 * (xp.numel() + w_rows.numel() + y.numel())))
     _native.check(_native.lib().seam_stem_s2d_swh_f16(_ptr(xp), _ptr(w_rows), _ptr(scale), _ptr(shift), _ptr(y), n, h2, w2,
                                                       1 if relu else 0, _stream()), "seam_stem_s2d_swh_f16")
-    if trace is not None:
-        e1.record()
-        trace.append(("stem_swh<4,2>", 2.0 * n * h2 * w2 * 64 * 16 * 12, e0, e1, (n, h2, w2, 16, 64, 4, 1),
-                      float(2 * (xp.numel() + w_rows.numel() + y.numel()))))
+    if tr:
+        _trace_end(tr)
     return y
 
 
@@ -650,26 +667,23 @@ def conv2d_topdown(x: torch.Tensor, pc: PackedConv, top: torch.Tensor) -> torch.
     """FPN top-down merge [TV]: conv(x) + nearest-upsample(top) -> NHWC.  Exact-fp32 weights: ONE launch (the coarse map is
     added in the conv epilogue, ``seam_conv2d_upres_f32``); other precisions: conv + ``upsample_add_``.  Both forms round
     identically."""
-    if (pc.dtype == F16 and pc.wsh is not None and SWH and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4
-            and x.shape[1] * x.shape[2] >= max(SW_MIN_HW, 128) and top.dim() == 4 and top.shape[0] == x.shape[0] and top.shape[3] == pc.K):
+    if (pc.dtype == F16 and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and _swh_ok(pc, x.shape[1], x.shape[2])
+            and x.shape[1] * x.shape[2] >= 128 and top.dim() == 4 and top.shape[0] == x.shape[0] and top.shape[3] == pc.K):
         # fp16 path (round 6): the merge in the streaming pointwise kernel's epilogue -- the lateral is never written and re-read
         x, top = _req(x, F16, "x"), _req(top, F16, "top")
         n, h, w, c = x.shape
         if c != pc.Cstore:
             raise ValueError(f"conv2d_topdown: input has {c} channels, weights packed for {pc.Cstore}")
         y = torch.empty((n, h, w, pc.K), dtype=F16, device=x.device)
-        trace = CONV_TRACE
-        if trace is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
         lib = _native.lib()
+        tr = CONV_TRACE is not None and _trace_begin(
+            _sw_variant(lib, "swh", n * h * w, c, pc.K), 2.0 * n * h * w * pc.K * (pc.Cin or pc.Cstore), (n, h, w, c, pc.K, 1, 1),
+            float(2 * (x.numel() + pc.w.numel() + y.numel() + top.numel())))
         _native.check(lib.seam_conv1x1_swh_f16(_ptr(x), None, _ptr(pc.wsh), _ptr(pc.scale), _ptr(pc.shift), _ptr(top), _ptr(y),
                                                n * h * w, c, 0, pc.K, 0, 2, h, w, top.shape[1], top.shape[2], _stream()),
                       "seam_conv1x1_swh_f16")
-        if trace is not None:
-            e1.record()
-            trace.append((_swh_variant(lib, n * h * w, c, pc.K), 2.0 * n * h * w * pc.K * (pc.Cin or pc.Cstore), e0, e1,
-                          (n, h, w, c, pc.K, 1, 1), float(2 * (x.numel() + pc.w.numel() + y.numel() + top.numel()))))
+        if tr:
+            _trace_end(tr)
         return y
     if pc.dtype != F32 or pc.K % 4:
         return upsample_add_(conv2d(x, pc), top)
@@ -683,25 +697,20 @@ def conv2d_topdown(x: torch.Tensor, pc: PackedConv, top: torch.Tensor) -> torch.
     if top.dim() != 4 or top.shape[0] != n or top.shape[3] != pc.K:
         raise ValueError("conv2d_topdown: top must be NHWC [N,Ht,Wt,K]")
     y = torch.empty((n, ho, wo, pc.K), dtype=F32, device=x.device)
-    trace = CONV_TRACE
-    if trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     lib = _native.lib()
     sw = _sw_ok(pc, h, w) and h * w >= 64
+    tr = CONV_TRACE is not None and _trace_begin(
+        _sw_variant(lib, "sw", n * h * w, c, pc.K) if sw else _igemm_variant(lib, F32, n * ho * wo, pc.K),
+        2.0 * n * ho * wo * pc.K * pc.R * pc.S * (pc.Cin or pc.Cstore), (n, h, w, c, pc.K, pc.R, pc.stride),
+        float(4 * (x.numel() + pc.w.numel() + y.numel() + top.numel())))
     if sw:
         _sw_launch(lib, x, None, pc, top, y, n * h * w, c, 0, False, 2, ho, wo, top.shape[1], top.shape[2])
     else:
         _native.check(lib.seam_conv2d_upres_f32(_ptr(x), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(top), _ptr(y),
                                                 n, h, w, c, pc.K, pc.R, pc.S, pc.stride, pc.pad, top.shape[1], top.shape[2], 0,
                                                 _stream()), "seam_conv2d_upres_f32")
-    if trace is not None:
-        e1.record()
-        tile = lib.seam_conv_tile_prec(0, n * ho * wo, pc.K)
-        trace.append((_sw_variant(lib, n * h * w, c, pc.K) if sw else f"conv_igemm<float,{tile // 1000},{tile % 1000}>",
-                      2.0 * n * ho * wo * pc.K * pc.R * pc.S * (pc.Cin or pc.Cstore), e0, e1,
-                      (n, h, w, c, pc.K, pc.R, pc.stride),
-                      float(4 * (x.numel() + pc.w.numel() + y.numel() + top.numel()))))
+    if tr:
+        _trace_end(tr)
     return y
 
 
@@ -735,16 +744,14 @@ def conv2d_dual(x1: torch.Tensor, x2: torch.Tensor, pc: PackedConv, stride2: int
     if (ho - 1) * stride2 >= h2 or (wo - 1) * stride2 >= w2:
         raise ValueError("conv2d_dual: x2 too small for the output grid")
     y = torch.empty((n, ho, wo, pc.K), dtype=dt, device=x1.device)
-    trace = CONV_TRACE
-    if trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     lib = _native.lib()
-    sw = dt == F32 and stride2 == 1 and (h2, w2) == (ho, wo) and _sw_ok(pc, ho, wo)
-    swh = (dt == F16 and stride2 == 1 and (h2, w2) == (ho, wo) and SWH and ho * wo >= SW_MIN_HW
-           and lib.seam_conv1x1_swh_config(n * ho * wo, c1, c2, pc.K) != 0)
-    if swh and pc.wsh is None:            # (the dual weights are packed as ONE [K, C1 + C2] matrix: take the fp16 rows from it once)
-        swh = False
+    same = stride2 == 1 and (h2, w2) == (ho, wo)      # the pointwise kernels read both inputs on the output grid
+    sw = dt == F32 and same and _sw_ok(pc, ho, wo)
+    swh = dt == F16 and same and _swh_ok(pc, ho, wo) and lib.seam_conv1x1_swh_config(n * ho * wo, c1, c2, pc.K) != 0
+    tr = CONV_TRACE is not None and _trace_begin(
+        _sw_variant(lib, "sw" if sw else "swh", n * ho * wo, c1 + c2, pc.K) if sw or swh else _igemm_variant(lib, dt, n * ho * wo, pc.K, dual=True),
+        2.0 * n * ho * wo * pc.K * (c1 + c2), (n, ho, wo, c1 + c2, pc.K, 1, 1),
+        float(x1.element_size() * (x1.numel() + n * ho * wo * c2 + pc.w.numel() + y.numel())))
     if sw:
         _sw_launch(lib, x1, x2, pc, None, y, n * ho * wo, c1, c2, relu)
     elif swh:
@@ -754,15 +761,8 @@ def conv2d_dual(x1: torch.Tensor, x2: torch.Tensor, pc: PackedConv, stride2: int
         fn = lib.seam_conv2d_dual_f32 if dt == F32 else lib.seam_conv2d_dual_f16
         _native.check(fn(_ptr(x1), _ptr(x2), _ptr(pc.w), _ptr(pc.scale), _ptr(pc.shift), _ptr(y), n, ho, wo, c1,
                          h2, w2, c2, stride2, pc.K, int(relu), _stream()), "seam_conv2d_dual")
-    if trace is not None:
-        e1.record()
-        tile = lib.seam_conv_tile_prec(0 if dt == F32 else 1, n * ho * wo, pc.K)
-        if tile // 1000 == 256:
-            tile = 128128
-        es = x1.element_size()
-        trace.append((_sw_variant(lib, n * ho * wo, c1 + c2, pc.K) if sw else _swh_variant(lib, n * ho * wo, c1 + c2, pc.K) if swh else f"conv_igemm<{'float' if dt == F32 else '_Float16'},{tile // 1000},{tile % 1000}>", 2.0 * n * ho * wo * pc.K * (c1 + c2), e0, e1,
-                      (n, ho, wo, c1 + c2, pc.K, 1, 1),
-                      float(es * (x1.numel() + n * ho * wo * c2 + pc.w.numel() + y.numel()))))
+    if tr:
+        _trace_end(tr)
     return y
 
 
@@ -790,8 +790,7 @@ def match_trunk(x: torch.Tensor, convs: Sequence[PackedConv], lin: PackedConv) -
     layers = (_native.TrunkLayer * 4)(*[layer(pc) for pc in convs])
     form = (C.c_int * 4)()
     for i, (pc, h) in enumerate(zip(convs, (14, 12, 10, 8))):
-        wino = pc.u is not None and WINOGRAD and _wino_pays(lib, k, h, h, 256, pc.K, 0)
-        form[i] = 2 if (wino and pc.u24 is not None and WINOGRAD24 and _wino24_pays(lib, k, h, h, 256, pc.K, 0)) else (1 if wino else 0)
+        form[i] = _wino_form(lib, pc, k, h, h, 256, 0)
     ws = torch.empty((int(lib.seam_match_trunk_workspace_floats(k)),), dtype=F32, device=x.device)
     _native.check(lib.seam_match_trunk_f32(_ptr(x), layers, C.byref(layer(lin)), _ptr(out), k, _ptr(ws), form, _stream()),
                   "seam_match_trunk_f32")

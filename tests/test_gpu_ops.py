@@ -799,3 +799,45 @@ def test_pointwise_pc_kernel(ops, case):
         assert torch.equal(ig, got), "conv1x1_pc and the implicit GEMM accumulate in the same k order: the same bits (seam_pwpc.hip header)"
     finally:
         ops.PWPC, ops.CONV_TRACE, ops.PWPC_MIN_HW = saved
+
+
+def test_every_traced_entry_point_appends_one_record_and_tracing_changes_no_bit(ops):
+    """The five launch sites that bracket themselves for ``CONV_TRACE`` (conv2d, conv2d_dual, conv2d_topdown in fp32 and fp16,
+    stem_s2d_f16), at the smallest shapes that reach them: one call under ``CONV_TRACE = []`` appends exactly one record
+    (variant, flops, start event, end event, 7-tuple shape, bytes) -- what bench.py's roofline leg and the tools unpack -- and the
+    same call untraced returns the same bits.  (The stem runs on 8 x 9 cells, not 8 x 8: seam_stem_s2d_swh_f16 takes frames whose padded
+    image, (H2 + 3) x (W2 + 3) cells, holds at least one 128-position tile, and 11 x 11 = 121 does not.)"""
+    d = dev()
+    bnp = tuple(t.to(d) for t in (torch.from_numpy(synth.uniform(synth.stream_id(901, "bw"), (64,), 0.5, 1.5)), rnd(902, (64,), "bb") * 0.1,
+                                  rnd(903, (64,), "rm") * 0.1, torch.from_numpy(synth.uniform(synth.stream_id(904, "rv"), (64,), 0.5, 1.5))))
+    w1, w2 = (rnd(s, (64, 64, 1, 1), "w").to(d) / 8 for s in (905, 906))
+    x1, x2 = (rnd(s, (1, 14, 14, 64)).to(d) for s in (907, 908))
+    top = rnd(909, (1, 7, 7, 64)).to(d)
+    pc32, pc16 = ops.pack_conv(w1, None, bnp), ops.pack_conv(w1, None, bnp, dtype=torch.float16)
+    ws = rnd(910, (64, 12, 4, 4), "w") / math.sqrt(12 * 16)
+    rows = F.pad(ws, (0, 0, 0, 0, 0, 4)).permute(0, 2, 3, 1).reshape(64, 256).half().contiguous().to(d)
+    xs = rnd(911, (1, 8, 9, 16)).half().to(d)
+    calls = {
+        "conv2d": lambda: ops.conv2d(x1, pc32, relu=True),
+        "conv2d_dual": lambda: ops.conv2d_dual(x1, x2, ops.pack_conv_dual(w1, bnp, w2, bnp), 1, relu=True),
+        "conv2d_topdown fp32": lambda: ops.conv2d_topdown(x1, pc32, top),
+        "conv2d_topdown fp16": lambda: ops.conv2d_topdown(x1.half(), pc16, top.half()),
+        "stem_s2d_f16": lambda: ops.stem_s2d_f16(xs, rows, pc16.scale, pc16.shift, relu=True),
+    }
+    assert ops.CONV_TRACE is None
+    for name, call in calls.items():
+        try:
+            ops.CONV_TRACE = trace = []
+            traced = call()
+        finally:
+            ops.CONV_TRACE = None
+        plain = call()
+        assert len(trace) == 1, (name, [t[0] for t in trace])
+        assert torch.equal(traced, plain), name
+        variant, flops, e0, e1, shape, nbytes = trace[0]
+        assert isinstance(variant, str) and variant and type(flops) is float and flops > 0 and type(nbytes) is float and nbytes > 0, (name, trace[0])
+        assert isinstance(shape, tuple) and len(shape) == 7 and all(type(v) is int for v in shape), (name, shape)
+        assert isinstance(e0, torch.cuda.Event) and isinstance(e1, torch.cuda.Event)
+        torch.cuda.synchronize()
+        assert e0.elapsed_time(e1) >= 0.0, name
+    assert ops.CONV_TRACE is None
