@@ -66,6 +66,9 @@ int seam_get_option(const char* name, int* value);
  * relu     0 none | 1 ReLU | 2 (backward passes) `residual` is NOT added: the result is zeroed where
  *          residual <= 0 -- the ReLU mask of the forward activation fused into the input-gradient conv
  * kred     padded reduction length = seam_conv_kred(C,R,S)
+ * Refused (hipErrorInvalidValue, nothing launched), here and in every seam_conv2d_* form below: N <= 0, K <= 0, a C outside
+ *          the rule above, stride < 1, and a kernel larger than the padded input (H + 2*pad < R or W + 2*pad < S:
+ *          there is no output pixel, whatever the stride).  Any R, S, stride and pad inside that are served.
  */
 int seam_conv_kred(int C, int R, int S);           /* host helper: ceil(R*S*C / 32) * 32 */
 int seam_conv_rows_padded(int K);                  /* host helper: ceil(K / 64) * 64      */

@@ -177,7 +177,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm(const Con
         b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)((const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * ES + (size_t)n_in_slab * CHUNK_BYTES), 0,
             (int)((unsigned)nk * (unsigned)slab_stride), 0x00020000);
-        const bool pointwise = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;       // input pixel = output pixel: no split at all
+        // input pixel = output pixel: no split at all (not under a crop: the output grid is then smaller than the input's)
+        const bool pointwise = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.Ho == p.H && p.Wo == p.W;
 #pragma unroll
         for (int i = 0; i < AI; ++i) {
             const int m = m0 + lrow + RP * i;
@@ -1306,6 +1307,8 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
            int rH = 0, int rW = 0, const DualSrc* dual = nullptr, int ho_crop = 0, int wo_crop = 0) {
     constexpr int BKE = CHUNK_BYTES / (int)sizeof(T), EPV = 16 / (int)sizeof(T);
     if ((C % EPV) || (C >= BKE && C % BKE) || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    // a kernel larger than the padded input has no output (under a stride the division below would round the negative extent to 0)
+    if (stride < 1 || R < 1 || S < 1 || H + 2 * pad < R || W + 2 * pad < S) return (int)hipErrorInvalidValue;
     ConvArgs a;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
     a.N = N; a.H = H; a.W = W; a.C = C;
@@ -1377,6 +1380,7 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
 int conv2d_bx3(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
                int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream, int terms = 3) {
     if ((C % 4) || (C >= 32 && C % 32) || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
+    if (stride < 1 || R < 1 || S < 1 || H + 2 * pad < R || W + 2 * pad < S) return (int)hipErrorInvalidValue;
     ConvArgs a;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
     a.N = N; a.H = H; a.W = W; a.C = C;
