@@ -956,6 +956,42 @@ int seam_rle_positions_masks(const int* obj_hw_host, const int* obj_hw, const in
 int seam_rle_positions_paste(int D, int H, int W, const void* ws, int64_t ws_bytes, const int64_t* scan, int* positions,
                              int64_t capacity, seam_stream_t stream);
 
+/* ---- The bitmap as the common form of the RLE operations (rleMerge, rleIou, rleArea at one bit per pixel) ------------------
+ * The workspace layout above ([ceil(h/32)][w] words per object, object o at word obj_cell_off[o]) filled from run lists, combined
+ * word by word, counted pair-wise; seam_rle_count_bits + the caller's scan + seam_rle_positions_masks turn any such bitmap back
+ * into an RLE.  obj_hw int32 [n][2], obj_cell_off int64 [n] are DEVICE tables (any mix of sizes, the cells of one call's objects
+ * need not be adjacent); obj_hw_host is obj_hw in HOST memory, read by the launcher.  Bits of rows at or past h are zero in
+ * everything these calls write and are ignored in what they read.  Integer arithmetic only, no atomics: two calls give identical
+ * bytes.  Nothing is allocated, nothing synchronises.
+ *
+ * seam_rle_bits_from_runs: run_start / obj_run_off exactly as seam_rle_masks_u8 takes them, n_runs = obj_run_off[n] entries in
+ *   run_start.  One thread per word: a binary search for the run holding the word's first position c*h + 32*band, then a walk
+ *   over the runs that start inside its rows.  Every word of every object is written; no other word of ws is.
+ * seam_rle_bits_combine: destination object g <- the OR (intersect != 0: the AND) of the source objects group_obj[group_off[g]
+ *   .. group_off[g+1]) (int32 DEVICE tables, CSR over n_entries entries, indices into the n_src source objects of src_hw /
+ *   src_cell_off / src).  A group's sources have its destination's shape; a source that has not, or an index outside 0..n_src-1,
+ *   is left out; a group with no source left gives zeros; a group of one is a copy.  dst and src must not overlap.
+ * seam_rle_count_bits: the count stage of seam_rle_encode_* for a bitmap that did not come from there: counts int32, laid out as
+ *   ws, <- transitions per cell; only the objects' cells are written (size counts as the objects' cells exactly before a scan).
+ * seam_rle_bits_inter: pairs int32 [P][2] (DEVICE), object indices (a, b) of one shape: inter[p] int64 <- sum over the cells of
+ *   popcount(a & b), one block per pair, the partial sums joined in a fixed tree.  One launch serves the pairs of many images.
+ *   A pair that names an index outside 0..n-1 or two shapes gives -1.
+ * seam_rle_bits_area: area[o] int64 <- object o's own popcount (the pair (o, o)).
+ * Refused with a non-zero return, nothing launched or written: a NULL table (source tables may be NULL when n_entries == 0), a
+ * negative count, h or w outside 1..16384, h*w >= 2^31, ws_bytes % 4 or smaller than the objects need.  n == 0 (n_dst == 0,
+ * P == 0): no-op, returns 0. */
+int seam_rle_bits_from_runs(const int* run_start, const int* obj_run_off, int n_runs, const int* obj_hw_host, const int* obj_hw,
+                            const int64_t* obj_cell_off, void* ws, int64_t ws_bytes, int n, seam_stream_t stream);
+int seam_rle_bits_combine(const int* group_off, const int* group_obj, int n_entries, const int* src_hw, const int64_t* src_cell_off,
+                          const void* src, int64_t src_bytes, int n_src, const int* dst_hw_host, const int* dst_hw,
+                          const int64_t* dst_cell_off, void* dst, int64_t dst_bytes, int n_dst, int intersect, seam_stream_t stream);
+int seam_rle_count_bits(const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off, const void* ws, int64_t ws_bytes,
+                        int* counts, int n, seam_stream_t stream);
+int seam_rle_bits_inter(const int* pairs, int P, const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off,
+                        const void* ws, int64_t ws_bytes, int n, int64_t* inter, seam_stream_t stream);
+int seam_rle_bits_area(const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off, const void* ws, int64_t ws_bytes,
+                       int n, int64_t* area, seam_stream_t stream);
+
 /* ---- The optimizer step (ref stuffs/engine.py:62-64 optimizer.step(); train_matchrcnn.py:70-72 torch.optim.SGD) ----------------
  * seam_sgd_step_f32: momentum SGD over every tensor of the table in one launch.  `tensors` and `chunks` are DEVICE tables,
  * `groups` is HOST memory and travels by value in the kernel arguments (a changed lr costs no upload).

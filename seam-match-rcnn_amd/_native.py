@@ -226,6 +226,11 @@ SIGNATURES = {
     "seam_rle_encode_paste_f32": (_i, [_p, _p, _i, _i, _i, _p, _i64, _p, _p]),
     "seam_rle_positions_masks": (_i, [_p, _p, _p, _p, _i64, _p, _p, _i64, _i, _p]),
     "seam_rle_positions_paste": (_i, [_i, _i, _i, _p, _i64, _p, _p, _i64, _p]),
+    "seam_rle_bits_from_runs": (_i, [_p, _p, _i, _p, _p, _p, _p, _i64, _i, _p]),
+    "seam_rle_bits_combine": (_i, [_p, _p, _i, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _i64, _i, _i, _p]),
+    "seam_rle_count_bits": (_i, [_p, _p, _p, _p, _i64, _p, _i, _p]),
+    "seam_rle_bits_inter": (_i, [_p, _i, _p, _p, _p, _p, _i64, _i, _p, _p]),
+    "seam_rle_bits_area": (_i, [_p, _p, _p, _p, _i64, _i, _p, _p]),
     "seam_sgd_chunk_elems": (_i, []),
     "seam_sgd_step_f32": (_i, [_p, _p, _i, C.POINTER(SgdGroups), _p, _p]),
     "seam_repack_layout": (C.c_longlong, [C.POINTER(RepackJob), _i]),

@@ -143,6 +143,114 @@ __global__ __launch_bounds__(256) void rle_positions_kernel(Objs t, const uint32
     }
 }
 
+// ---- the bitmap as the common form of every RLE operation: runs -> bits, bits (op) bits, popcount(bits & bits) ----------------
+// last i in [lo, hi) with tab[i] <= key (lo when none is), as seam_masks.hip's
+__device__ __forceinline__ int last_run_le(const int* __restrict__ tab, int lo, int hi, int key) {
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (tab[mid] <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// One thread per (band, column) word: binary search for the run that holds the word's first position p = c*h + 32*band, then a
+// walk over the runs that start inside its rows.  A zero-length run repeats a start and sets nothing.
+__global__ __launch_bounds__(256) void rle_values_runs_kernel(const int* __restrict__ run_start, const int* __restrict__ obj_run_off,
+                                                              Objs t, uint32_t* __restrict__ ws, int64_t ws_words, int n_runs,
+                                                              int n) {
+    for (int o = blockIdx.y; o < n; o += gridDim.y) {
+        const Obj b = obj_get(t, o, ws_words);
+        if (!b.ok) continue;
+        const int r0 = max(obj_run_off[o], 0), r1 = min(obj_run_off[o + 1], n_runs);     // never read outside the run table
+        const int cells = b.bands * b.w;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < cells; i += gridDim.x * 256) {
+            const int k = i / b.w, c = i - k * b.w;
+            const int nr = min(32, b.h - (k << 5));
+            const int p = c * b.h + (k << 5), end = p + nr;            // < 2^31: h*w is
+            uint32_t v = 0;
+            if (r1 > r0) {
+                int j = last_run_le(run_start, r0, r1, p), pos = p;
+                while (pos < end) {
+                    const int e = j + 1 < r1 ? min(max(run_start[j + 1], pos), end) : end;
+                    if ((j - r0) & 1) {
+                        const uint32_t upto = e - p == 32 ? ~0u : (1u << (e - p)) - 1u;
+                        v |= upto & ~((1u << (pos - p)) - 1u);
+                    }
+                    pos = e;
+                    ++j;
+                }
+            }
+            ws[b.base + i] = v;
+        }
+    }
+}
+
+// dst object g <- OR (AND with `intersect`) over the source objects group_obj[group_off[g] .. group_off[g+1]); a source that is
+// not a valid object of g's shape is left out, a group without a valid source gives zeros.
+__global__ __launch_bounds__(256) void rle_bits_combine_kernel(const int* __restrict__ group_off, const int* __restrict__ group_obj,
+                                                               int n_entries, Objs st, const uint32_t* __restrict__ src,
+                                                               int64_t src_words, int n_src, Objs dt, uint32_t* __restrict__ dst,
+                                                               int64_t dst_words, int n_dst, int intersect) {
+    for (int g = blockIdx.y; g < n_dst; g += gridDim.y) {
+        const Obj b = obj_get(dt, g, dst_words);
+        if (!b.ok) continue;
+        const int e0 = max(group_off[g], 0), e1 = min(group_off[g + 1], n_entries);
+        const int cells = b.bands * b.w;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < cells; i += gridDim.x * 256) {
+            uint32_t acc = 0;
+            bool any = false;
+            for (int e = e0; e < e1; ++e) {
+                const int s = group_obj[e];
+                if (s < 0 || s >= n_src) continue;
+                const Obj a = obj_get(st, s, src_words);
+                if (!a.ok || a.h != b.h || a.w != b.w) continue;
+                const uint32_t v = src[a.base + i];
+                acc = !any ? v : (intersect ? acc & v : acc | v);
+                any = true;
+            }
+            const int nr = b.h - ((i / b.w) << 5);
+            if (nr < 32) acc &= (1u << nr) - 1u;                      // rows past h stay zero whatever the sources hold
+            dst[b.base + i] = acc;
+        }
+    }
+}
+
+// One block per pair (a, b): out[p] = sum over the cells of popcount(a & b), rows past h masked off; pairs == NULL: pair p is
+// (p, p), the object's own popcount.  A pair that names no two valid objects of one shape gives -1.  Integer sums: the lanes'
+// partial sums meet in a fixed tree, and any order gives the same number.
+__global__ __launch_bounds__(256) void rle_bits_inter_kernel(const int* __restrict__ pairs, Objs t, const uint32_t* __restrict__ ws,
+                                                             int64_t ws_words, int n, int64_t* __restrict__ out, int P) {
+    __shared__ int part[4];
+    for (int p = blockIdx.x; p < P; p += gridDim.x) {
+        const int ia = pairs ? pairs[2 * p] : p, ib = pairs ? pairs[2 * p + 1] : p;
+        bool ok = ia >= 0 && ia < n && ib >= 0 && ib < n;              // block-uniform
+        Obj a{}, b{};
+        if (ok) {
+            a = obj_get(t, ia, ws_words);
+            b = obj_get(t, ib, ws_words);
+            ok = a.ok && b.ok && a.h == b.h && a.w == b.w;
+        }
+        if (!ok) {
+            if (threadIdx.x == 0) out[p] = -1;
+            continue;
+        }
+        const int cells = a.bands * a.w, full = (a.h & 31) ? (a.bands - 1) * a.w : cells;
+        const uint32_t tail = (1u << (a.h & 31)) - 1u;
+        const uint32_t* __restrict__ wa = ws + a.base;
+        const uint32_t* __restrict__ wb = ws + b.base;
+        int sum = 0;                                                   // <= h*w < 2^31
+        for (int i = threadIdx.x; i < cells; i += 256) {
+            const uint32_t v = wa[i] & wb[i];
+            sum += __popc(i < full ? v : v & tail);
+        }
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+        __syncthreads();                                              // the previous pair's reader is done with part
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) out[p] = (int64_t)part[0] + part[1] + part[2] + part[3];
+    }
+}
+
 inline dim3 cell_grid(int64_t max_cells, int n) {
     return dim3((unsigned)std::min<int64_t>((max_cells + 255) / 256, 256), (unsigned)std::min(n, 65535));
 }
@@ -157,6 +265,16 @@ inline bool scan_shapes(const int* hw, int n, int64_t* total, int64_t* largest) 
         *largest = std::max(*largest, c);
     }
     return true;
+}
+
+inline int bits_inter_launch(const int* pairs, int P, const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off,
+                      const void* ws, int64_t ws_bytes, int n, int64_t* out, void* stream) {
+    int64_t total, largest;
+    if (!scan_shapes(obj_hw_host, n, &total, &largest) || total * 4 > ws_bytes) return (int)hipErrorInvalidValue;
+    const Objs t{obj_hw, obj_cell_off, 0, 0};
+    hipLaunchKernelGGL(rle_bits_inter_kernel, dim3((unsigned)std::min(P, 65535)), dim3(256), 0, (hipStream_t)stream, pairs, t,
+                       (const uint32_t*)ws, ws_bytes >> 2, n, out, P);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -232,6 +350,65 @@ int seam_rle_positions_paste(int D, int H, int W, const void* ws, int64_t ws_byt
     hipLaunchKernelGGL(rle_positions_kernel, cell_grid(cells, D), dim3(256), 0, (hipStream_t)stream, t, (const uint32_t*)ws,
                        ws_bytes >> 2, scan, positions, capacity, D);
     return (int)hipGetLastError();
+}
+
+int seam_rle_bits_from_runs(const int* run_start, const int* obj_run_off, int n_runs, const int* obj_hw_host, const int* obj_hw,
+                            const int64_t* obj_cell_off, void* ws, int64_t ws_bytes, int n, void* stream) {
+    if (n < 0 || n_runs < 0 || ws_bytes < 0 || (ws_bytes & 3)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!run_start || !obj_run_off || !obj_hw_host || !obj_hw || !obj_cell_off || !ws) return (int)hipErrorInvalidValue;
+    int64_t total, largest;
+    if (!scan_shapes(obj_hw_host, n, &total, &largest) || total * 4 > ws_bytes) return (int)hipErrorInvalidValue;
+    const Objs t{obj_hw, obj_cell_off, 0, 0};
+    hipLaunchKernelGGL(rle_values_runs_kernel, cell_grid(largest, n), dim3(256), 0, (hipStream_t)stream, run_start, obj_run_off, t,
+                       (uint32_t*)ws, ws_bytes >> 2, n_runs, n);
+    return (int)hipGetLastError();
+}
+
+int seam_rle_bits_combine(const int* group_off, const int* group_obj, int n_entries, const int* src_hw, const int64_t* src_cell_off,
+                          const void* src, int64_t src_bytes, int n_src, const int* dst_hw_host, const int* dst_hw,
+                          const int64_t* dst_cell_off, void* dst, int64_t dst_bytes, int n_dst, int intersect, void* stream) {
+    if (n_dst < 0 || n_src < 0 || n_entries < 0 || src_bytes < 0 || dst_bytes < 0 || ((src_bytes | dst_bytes) & 3))
+        return (int)hipErrorInvalidValue;
+    if (n_dst == 0) return 0;
+    if (!group_off || !dst_hw_host || !dst_hw || !dst_cell_off || !dst) return (int)hipErrorInvalidValue;
+    if (n_entries > 0 && (!group_obj || !src_hw || !src_cell_off || !src || n_src == 0)) return (int)hipErrorInvalidValue;
+    int64_t total, largest;
+    if (!scan_shapes(dst_hw_host, n_dst, &total, &largest) || total * 4 > dst_bytes) return (int)hipErrorInvalidValue;
+    const Objs st{src_hw, src_cell_off, 0, 0}, dt{dst_hw, dst_cell_off, 0, 0};
+    hipLaunchKernelGGL(rle_bits_combine_kernel, cell_grid(largest, n_dst), dim3(256), 0, (hipStream_t)stream, group_off, group_obj,
+                       n_entries, st, (const uint32_t*)src, src_bytes >> 2, n_src, dt, (uint32_t*)dst, dst_bytes >> 2, n_dst,
+                       intersect);
+    return (int)hipGetLastError();
+}
+
+int seam_rle_count_bits(const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off, const void* ws, int64_t ws_bytes,
+                        int* counts, int n, void* stream) {
+    if (n < 0 || ws_bytes < 0 || (ws_bytes & 3)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!obj_hw_host || !obj_hw || !obj_cell_off || !ws || !counts) return (int)hipErrorInvalidValue;
+    int64_t total, largest;
+    if (!scan_shapes(obj_hw_host, n, &total, &largest) || total * 4 > ws_bytes) return (int)hipErrorInvalidValue;
+    const Objs t{obj_hw, obj_cell_off, 0, 0};
+    hipLaunchKernelGGL(rle_count_kernel, cell_grid(largest, n), dim3(256), 0, (hipStream_t)stream, t, (const uint32_t*)ws,
+                       ws_bytes >> 2, counts, n);
+    return (int)hipGetLastError();
+}
+
+int seam_rle_bits_inter(const int* pairs, int P, const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off,
+                        const void* ws, int64_t ws_bytes, int n, int64_t* inter, void* stream) {
+    if (P < 0 || n < 0 || ws_bytes < 0 || (ws_bytes & 3)) return (int)hipErrorInvalidValue;
+    if (P == 0) return 0;
+    if (n == 0 || !pairs || !obj_hw_host || !obj_hw || !obj_cell_off || !ws || !inter) return (int)hipErrorInvalidValue;
+    return bits_inter_launch(pairs, P, obj_hw_host, obj_hw, obj_cell_off, ws, ws_bytes, n, inter, stream);
+}
+
+int seam_rle_bits_area(const int* obj_hw_host, const int* obj_hw, const int64_t* obj_cell_off, const void* ws, int64_t ws_bytes,
+                       int n, int64_t* area, void* stream) {
+    if (n < 0 || ws_bytes < 0 || (ws_bytes & 3)) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!obj_hw_host || !obj_hw || !obj_cell_off || !ws || !area) return (int)hipErrorInvalidValue;
+    return bits_inter_launch(nullptr, n, obj_hw_host, obj_hw, obj_cell_off, ws, ws_bytes, n, area, stream);
 }
 
 }  // extern "C"

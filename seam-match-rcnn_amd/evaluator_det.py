@@ -97,6 +97,15 @@ def _mask_iou(inter: np.ndarray, det_area: np.ndarray, gt_pix: np.ndarray, crowd
     return np.where(den == 0, 0.0, iou)
 
 
+def _load_json(doc):
+    """A parsed JSON document, or the path of one."""
+    if isinstance(doc, (str, bytes)) or hasattr(doc, "__fspath__"):
+        import json
+        with open(doc) as f:
+            return json.load(f)
+    return doc
+
+
 def _match(ious: List[List[float]], gt_ignore: List[bool], gt_crowd: List[bool]):
     """COCOeval.evaluateImg's greedy matching: ious[d][g] with the detections in score order and the ground truths ordered
     non-ignored first -> (matched [T,D] bool, matched-to-ignored [T,D] bool)."""
@@ -186,6 +195,61 @@ class DetectionEvaluator:
                                                crowd)
                 rec["area"]["segm"] = v["det_area"].reshape(-1)
             self.images.append(rec)
+
+    def update_results(self, gt, results) -> None:
+        """Score a saved COCO results file: ``gt`` is a COCO-format dict (or the path of its JSON) with ``images`` (``id``,
+        ``height``, ``width``) and ``annotations`` (``image_id``, ``category_id``, ``bbox`` xywh, ``area``, ``iscrowd``,
+        ``segmentation`` as polygons, uncompressed or compressed RLE); ``results`` is a list as ``coco_results`` writes it (or
+        its path).  Every image of ``gt`` gets the record ``update`` builds -- an image without results counts its ground
+        truths -- in the order of ``gt["images"]``; a result for an unknown image id raises ValueError.  Boxes: ``bbIou`` on the
+        stored xywh values, detection area ``w*h``.  Masks: the detections' RLEs become bitmaps straight from their run lists,
+        ground-truth polygons are rasterised (``mask_utils.masks_from_annotations``) and bit-packed by the encoder's values
+        stage, and one pair-intersection launch serves as many images as ``ops.RLE_BITS_BUDGET_BYTES`` holds (one host copy
+        each); the detection area is the mask's popcount.  No model and no dense detection mask is involved."""
+        from . import mask_utils as M
+        gt, results = _load_json(gt), _load_json(results)
+        images = list(gt["images"])
+        index = {im["id"]: i for i, im in enumerate(images)}
+        if len(index) != len(images):
+            raise ValueError("update_results: image ids must be distinct")
+        anns, dets = [[] for _ in images], [[] for _ in images]
+        for a in gt.get("annotations", []):
+            if a["image_id"] not in index:
+                raise ValueError(f"update_results: annotation for unknown image id {a['image_id']!r}")
+            anns[index[a["image_id"]]].append(a)
+        for r in results:
+            if r["image_id"] not in index:
+                raise ValueError(f"update_results: result for unknown image id {r['image_id']!r}")
+            dets[index[r["image_id"]]].append(r)
+        need = [k for t, k in (("bbox", "bbox"), ("segm", "segmentation")) if t in self.iou_types]
+        for r in results:
+            if any(k not in r for k in need):
+                raise ValueError(f"update_results: a result of image {r['image_id']!r} lacks {need}")
+        sizes = [(int(im["height"]), int(im["width"])) for im in images]
+        recs = []
+        for a_i, d_i in zip(anns, dets):
+            crowd = np.asarray([int(a.get("iscrowd", 0)) != 0 for a in a_i], dtype=bool)
+            gbox = np.asarray([a["bbox"] for a in a_i], dtype=np.float64).reshape(-1, 4)
+            rec = dict(labels=np.asarray([r["category_id"] for r in d_i], dtype=np.int64),
+                       scores=np.asarray([r["score"] for r in d_i], dtype=np.float64),
+                       gt_labels=np.asarray([a["category_id"] for a in a_i], dtype=np.int64), gt_crowd=crowd,
+                       gt_area=np.asarray([a["area"] if "area" in a else a["bbox"][2] * a["bbox"][3] for a in a_i], dtype=np.float64),
+                       iou={}, area={})
+            if "bbox" in self.iou_types:
+                dbox = np.asarray([r["bbox"] for r in d_i], dtype=np.float64).reshape(-1, 4)
+                rec["iou"]["bbox"] = _box_iou_xywh(*(dbox[:, k] for k in range(4)), *(gbox[:, k] for k in range(4)), crowd)
+                rec["area"]["bbox"] = dbox[:, 2] * dbox[:, 3]
+            recs.append(rec)
+        if "segm" in self.iou_types:
+            cells = ops.rle_bits_cells(sizes)
+            costs = [4 * c * (len(d_i) + len(a_i)) + h * w * sum(isinstance(a["segmentation"], (list, tuple)) for a in a_i)
+                     for c, (h, w), a_i, d_i in zip(cells, sizes, anns, dets)]
+            for lo, hi in ops.budget_chunks(costs):
+                tables = M.results_inter_tables(anns[lo:hi], dets[lo:hi], sizes[lo:hi])
+                for rec, (inter, d_area, g_pix) in zip(recs[lo:hi], tables):
+                    rec["iou"]["segm"] = _mask_iou(inter, d_area.astype(np.float64), g_pix.astype(np.float64), rec["gt_crowd"])
+                    rec["area"]["segm"] = d_area.astype(np.float64)
+        self.images.extend(recs)
 
     @staticmethod
     def _mask_tables(out, tgt):
@@ -362,5 +426,15 @@ def evaluate(model, data_loader, device, iou_types: Sequence[str] = ("bbox", "se
             model.paste_masks = old
         else:
             del model.paste_masks
+    stats = ev.summarize(verbose=verbose)
+    return (stats, ev) if return_report else stats
+
+
+def evaluate_results(gt, results, iou_types: Sequence[str] = ("bbox", "segm"), verbose: bool = True, return_report: bool = False):
+    """Box and mask AP of a saved COCO results file against a COCO annotation file (dicts / lists or paths, as
+    ``DetectionEvaluator.update_results`` takes them): run the detector once, keep ``coco_results``' JSON, score it later.
+    -> {"bbox": [12 floats], "segm": [12 floats]} in COCO's order; with ``return_report`` also the evaluator."""
+    ev = DetectionEvaluator(iou_types)
+    ev.update_results(gt, results)
     stats = ev.summarize(verbose=verbose)
     return (stats, ev) if return_report else stats

@@ -15,7 +15,10 @@ The other direction: ``encode`` (dense masks, NumPy or device) and ``encode_dete
 mask) run ``csrc/seam_rle.hip`` and bring a few hundred integers per object to the host, where ``counts_to_bytes`` writes the
 compressed strings with vectorised NumPy; ``decode``, ``area``, ``toBbox``, ``annToRLE`` and ``iou`` complete the reference's
 module.  A pixel is set iff its byte is non-zero (pycocotools' ``encode`` agrees for bytes 0/1 only).
-Not here: ``merge``, ``frPyObjects``.
+
+``merge``, ``frPyObjects`` and ``iou`` on RLEs work on bitmaps of one bit per pixel (``ops.rle_bits`` straight from the run lists,
+``ops.bits_combine``, ``ops.bits_to_rle``, ``ops.bits_inter``): no dense mask is written for an RLE operation.  Like the rest of
+the module they are held by restatements of the published procedure (tests/rle_algebra_refs.py), not pinned against pycocotools.
 """
 from __future__ import annotations
 
@@ -288,10 +291,105 @@ def annToRLE(ann, size) -> dict:
     return encode(masks_from_annotations([[ann]], [size], torch.device("cuda"))[0])[0]
 
 
+def merge(rleObjs, intersect: bool = False) -> dict:
+    """The reference's ``merge``: the union (``intersect``: the intersection) of a list of RLE dicts of one size -> one compressed
+    RLE dict.  The run lists become bitmaps, are combined word by word and encoded again, all on the device.  One input comes back
+    re-encoded.  The result is the canonical run list of the combined mask -- the first count a run of zeros that may be 0, no
+    interior zero-length run -- which is what ``maskApi.c``'s ``rleMerge`` gives for canonical inputs; for inputs that carry
+    interior zero-length runs ``rleMerge`` can keep such a run, and this function still returns the canonical form of the same
+    mask.  An empty list gives ``{"size": [0, 0], "counts": b""}``.  Inputs of different sizes raise ValueError (pycocotools
+    silently returns an empty RLE there)."""
+    rles = list(rleObjs) if isinstance(rleObjs, (list, tuple)) else [rleObjs]
+    if not rles:
+        return {"size": [0, 0], "counts": b""}
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"merge: the RLEs must share a size, got {sorted(sizes)}")
+    size = sizes.pop()
+    counts = ops.rle_merge([[_counts(r, f"merge: object {j}") for j, r in enumerate(rles)]], [size], bool(intersect))
+    return _rle_dicts(counts, [size])[0]
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _box_polygon(bb) -> list:
+    """``rleFrBbox``: the box [x, y, w, h] as the polygon [x, y, x, y+h, x+w, y+h, x+w, y], in float64."""
+    x, y, bw, bh = (float(v) for v in bb)
+    xe, ye = x + bw, y + bh
+    return [x, y, x, ye, xe, ye, xe, y]
+
+
+def frPyObjects(pyobj, h, w):
+    """The reference's ``frPyObjects(pyobj, h, w)``, by pycocotools' dispatch rules: an ``ndarray [n,4]`` or a list of 4-lists are
+    boxes ``[x, y, w, h]``, a list of longer lists are polygons ``[x0, y0, x1, y1, ...]``, a list of dicts with ``counts`` and
+    ``size`` are uncompressed RLEs -> a list with one compressed RLE dict each (polygons are NOT merged); a single 4-list, longer
+    list or dict -> one RLE dict.  A box is rasterised as its four-corner polygon (``rleFrBbox``).  Boxes and polygons go through
+    the polygon rasteriser and the encoder on the device; an RLE's ``size`` must be ``[h, w]``."""
+    h, w = int(h), int(w)
+
+    def polys(parts_per_object):
+        if not parts_per_object:
+            return []
+        return encode(masks_from_annotations([[[p] for p in parts_per_object]], [(h, w)], torch.device("cuda"))[0])
+
+    def boxes(rows):
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != 4:
+            raise ValueError(f"frPyObjects: boxes must be [n,4], got shape {rows.shape}")
+        return polys([_box_polygon(r) for r in rows])
+
+    def unc(dicts):
+        counts = [_split(d, (h, w), f"frPyObjects: object {j}")[1] for j, d in enumerate(dicts)]
+        ops.pack_rle_masks([counts], [(h, w)])                         # validates: integers, non-negative, sum h*w
+        return _rle_dicts([np.asarray(c, dtype=np.int64) for c in counts], [(h, w)] * len(counts))
+
+    def is_rle(v):
+        return isinstance(v, dict) and "counts" in v and "size" in v
+
+    if isinstance(pyobj, np.ndarray):
+        return boxes(pyobj)
+    if isinstance(pyobj, (list, tuple)) and len(pyobj) and is_rle(pyobj[0]):
+        return unc(pyobj)
+    if isinstance(pyobj, (list, tuple)) and len(pyobj) and isinstance(pyobj[0], (list, tuple, np.ndarray)):
+        if len(pyobj[0]) == 4:
+            return boxes(pyobj)
+        if len(pyobj[0]) > 4:
+            return polys([list(p) for p in pyobj])
+    elif isinstance(pyobj, (list, tuple)) and len(pyobj) == 4 and all(_is_number(v) for v in pyobj):
+        return boxes([pyobj])[0]
+    elif isinstance(pyobj, (list, tuple)) and len(pyobj) > 4 and all(_is_number(v) for v in pyobj):
+        return polys([list(pyobj)])[0]
+    elif is_rle(pyobj):
+        return unc([pyobj])[0]
+    raise ValueError("frPyObjects: input type is not supported")
+
+
+def rle_inter_tables(dt_counts: Sequence, gt_counts: Sequence, size):
+    """Detections and ground truths of one ``size`` as counts arrays -> (inter int64 [D,G], det_area int64 [D], gt_area int64 [G]):
+    bitmaps from the run lists and pair-wise popcounts, the detections in chunks of ``ops.RLE_BITS_BUDGET_BYTES`` (every chunk
+    carries the ground truths), one host copy per chunk."""
+    nd, ng = len(dt_counts), len(gt_counts)
+    per = 4 * ops.rle_bits_cells([size])[0]
+    inter, d_area, g_area = np.zeros((nd, ng), np.int64), np.zeros(nd, np.int64), np.zeros(ng, np.int64)
+    budget = max(ops.RLE_BITS_BUDGET_BYTES - per * ng, per)
+    for lo, hi in ops.budget_chunks([per] * nd, budget) or [(0, 0)]:
+        k = hi - lo
+        ws, lay = ops.rle_bits(list(dt_counts[lo:hi]) + list(gt_counts), [size] * (k + ng))
+        pairs = np.stack(np.meshgrid(np.arange(k), k + np.arange(ng), indexing="ij"), -1).reshape(-1, 2)
+        table = ops.bits_inter(ws, lay, pairs).cpu().numpy()          # the chunk's one device-to-host copy
+        inter[lo:hi] = table[:k * ng].reshape(k, ng)
+        d_area[lo:hi] = table[k * ng:k * ng + k]
+        g_area[:] = table[k * ng + k:]
+    return inter, d_area, g_area
+
+
 def iou(dt, gt, iscrowd) -> np.ndarray:
     """The reference's ``iou(dt, gt, iscrowd)`` -> float64 ``[len(dt), len(gt)]``.  Boxes (``[n,4]`` xywh arrays or lists of
-    4-lists) go through ``evaluator_det``'s restatement of ``bbIou``; lists of RLE dicts are decoded on the device and the
-    intersections counted there (not a hot path).  A crowd ground truth divides by the detection's area."""
+    4-lists) go through ``evaluator_det``'s restatement of ``bbIou``; lists of RLE dicts become bitmaps on the device, straight
+    from their run lists, and the intersections and areas are popcounts of words (``rle_inter_tables``): no dense mask is
+    written.  A crowd ground truth divides by the detection's area."""
     from . import evaluator_det as E
     crowd = np.asarray(iscrowd, dtype=np.int64).reshape(-1) != 0
 
@@ -307,11 +405,68 @@ def iou(dt, gt, iscrowd) -> np.ndarray:
     if not is_rle(dt):
         d, g = (np.asarray(v, dtype=np.float64).reshape(-1, 4) for v in (dt, gt))
         return E._box_iou_xywh(*(d[:, i] for i in range(4)), *(g[:, i] for i in range(4)), crowd)
-    dm, gm = decode(dt, keep_on_device=True) != 0, decode(gt, keep_on_device=True) != 0
-    if tuple(dm.shape[1:]) != tuple(gm.shape[1:]):
+    sizes = {tuple(int(v) for v in r["size"]) for r in dt + gt}
+    if len(sizes) > 1:
         raise ValueError("iou: dt and gt RLEs differ in size")
-    inter = torch.stack([(dm & g[None]).sum((1, 2)) for g in gm], 1)
-    table = torch.cat([inter.reshape(-1).to(torch.float64), dm.sum((1, 2)).to(torch.float64),
-                       gm.sum((1, 2)).to(torch.float64)]).cpu().numpy()
-    nd, ng = len(dt), len(gt)
-    return E._mask_iou(table[:nd * ng].reshape(nd, ng), table[nd * ng:nd * ng + nd], table[nd * ng + nd:], crowd)
+    inter, d_area, g_area = rle_inter_tables([_counts(r, f"iou: dt {j}") for j, r in enumerate(dt)],
+                                             [_counts(r, f"iou: gt {j}") for j, r in enumerate(gt)], sizes.pop())
+    return E._mask_iou(inter, d_area.astype(np.float64), g_area.astype(np.float64), crowd)
+
+
+def results_inter_tables(anns_per_image: Sequence[Sequence[dict]], dets_per_image: Sequence[Sequence[dict]], sizes) -> list:
+    """The mask tables of a batch of images for ``evaluator_det.update_results``: per image (inter int64 [D,G], det_area int64
+    [D], gt_pixels int64 [G]) from the results' ``segmentation`` RLEs against the annotations' ``segmentation`` (polygons,
+    uncompressed or compressed RLE).  All RLEs of the batch become bitmaps in one launch; the polygon ground truths are rasterised
+    in one ``masks_from_annotations`` call and bit-packed behind them; one pair launch and one host copy serve the batch."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    counts, obj_size, dense_at, det_idx, gt_idx = [], [], [], [], []
+    polys, poly_sizes = [], []
+    for i, (anns, dets, size) in enumerate(zip(anns_per_image, dets_per_image, sizes)):
+        det_idx.append(list(range(len(counts), len(counts) + len(dets))))
+        for j, r in enumerate(dets):
+            c = _split(r["segmentation"], size, f"results: image {i} detection {j}")[1]
+            if c is None:
+                raise ValueError(f"results: image {i} detection {j}: a result's segmentation must be an RLE")
+            counts.append(np.asarray(c, dtype=np.int64).reshape(-1))
+            obj_size.append(size)
+        idx, mine = [], []
+        for j, a in enumerate(anns):
+            parts, c = _split(_segm(a), size, f"annotations: image {i} object {j}")
+            if c is None:
+                idx.append(("dense", len(dense_at) + len(mine)))
+                mine.append(parts)
+            else:
+                idx.append(("runs", len(counts)))
+                counts.append(np.asarray(c, dtype=np.int64).reshape(-1))
+                obj_size.append(size)
+        gt_idx.append(idx)
+        if mine:
+            dense_at += [size] * len(mine)
+            polys.append(mine)
+            poly_sizes.append(size)
+    dense = None
+    if polys:
+        stacks = masks_from_annotations(polys, poly_sizes, torch.device("cuda"))
+        base = stacks[0].untyped_storage()
+        if all(s.untyped_storage().data_ptr() == base.data_ptr() for s in stacks):      # views of the rasteriser's one flat buffer
+            flat = torch.empty(0, dtype=torch.uint8, device=stacks[0].device).set_(base)
+            starts = [s.storage_offset() for s in stacks]
+        else:
+            flat = torch.cat([s.reshape(-1) for s in stacks])
+            starts = np.cumsum([0] + [s.numel() for s in stacks[:-1]]).tolist()
+        offs = [st + k * h * w for st, s, (h, w) in zip(starts, stacks, poly_sizes) for k in range(s.shape[0])]
+        dense = (flat, offs, dense_at)
+    n_runs = len(counts)
+    ws, lay = ops.rle_bits(counts, obj_size, dense=dense)
+    pairs, spans = [], []
+    for d_i, g_i in zip(det_idx, gt_idx):
+        g_obj = [k if kind == "runs" else n_runs + k for kind, k in g_i]
+        spans.append((len(pairs), d_i, g_obj))
+        pairs += [(d, g) for d in d_i for g in g_obj]
+    table = ops.bits_inter(ws, lay, pairs).cpu().numpy()              # the batch's one device-to-host copy
+    area = table[len(pairs):]
+    out = []
+    for at, d_i, g_obj in spans:
+        nd, ng = len(d_i), len(g_obj)
+        out.append((table[at:at + nd * ng].reshape(nd, ng), area[np.asarray(d_i, np.int64)], area[np.asarray(g_obj, np.int64)]))
+    return out

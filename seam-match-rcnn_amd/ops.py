@@ -2062,6 +2062,197 @@ def rle_encode_paste(probs: torch.Tensor, boxes: torch.Tensor, hw) -> list:
         return _rle_finish(counts, last, [(h, w)] * d, positions)
 
 
+# ---------------------------------------------------------------------------------------------------- RLE algebra on bitmaps (csrc/seam_rle.hip)
+RLE_BITS_BUDGET_BYTES = 64 << 20   # bitmap words (and dense bytes packed into them) of one chunk of a merge / iou / scoring job
+
+
+@dataclass
+class BitsLayout:
+    """The objects of one bitmap workspace (int32 words, ``[ceil(h/32)][w]`` per object): object o's words start at
+    ``cell_off[o]``; the objects lie one after the other in index order."""
+    hw: object                     # NumPy int32 [n,2], the launchers' host table
+    cell_off: object               # NumPy int64 [n+1], running sum of the objects' cells
+    dev: dict                      # device tables: obj_hw int32 [n,2], cell_off int64 [n+1]
+
+    @property
+    def n(self) -> int:
+        return int(self.hw.shape[0])
+
+    @property
+    def cells(self) -> int:
+        return int(self.cell_off[-1])
+
+    @property
+    def hw_ptr(self):
+        return self.hw.ctypes.data_as(C.c_void_p)
+
+
+def rle_bits_cells(sizes: Sequence[Sequence[int]]) -> list:
+    """Words of each object's bitmap, ``w * ceil(h/32)``; ValueError for a size the kernels refuse."""
+    memo = {}
+    return [memo[s] if s in memo else memo.setdefault(s, _rle_cells(*s)) for s in ((int(h), int(w)) for h, w in sizes)]
+
+
+def _bits_layout(sizes, device, extra: Optional[dict] = None):
+    """-> (layout, device copies of ``extra``'s tables): one upload for everything a chunk needs."""
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray([(int(h), int(w)) for h, w in sizes], np.int32).reshape(-1, 2))
+    cell_off = np.zeros(len(hw) + 1, np.int64)
+    np.cumsum(rle_bits_cells(hw.tolist()), out=cell_off[1:])
+    tables = dict(extra or {}, obj_hw=hw, cell_off=cell_off)
+    d = _upload_tables(tables, tuple(tables), device)
+    return BitsLayout(hw, cell_off, dict(obj_hw=d["obj_hw"], cell_off=d["cell_off"])), d
+
+
+def rle_bits(counts_per_object: Sequence, sizes: Sequence[Sequence[int]], device=None, dense=None):
+    """Uncompressed RLE counts -> bitmaps, one bit per pixel, without a dense mask (``seam_rle_bits_from_runs``).
+    ``counts_per_object[o]``: object o's counts, ``sizes[o] = (h, w)`` (any mix of sizes).  ``dense``: optional
+    ``(flat uint8 tensor, byte offsets, sizes)`` of further objects that lie as row-major masks on the device (the rasteriser's
+    output); they follow the run-list objects in the workspace, packed by the encoder's values stage.
+    -> (ws int32 [cells] device tensor, BitsLayout).  One table upload; errors as ``pack_rle_masks``."""
+    import numpy as np
+    device = _mask_device(device if device is not None else (dense[0].device if dense is not None else "cuda"))
+    n_runs_obj = len(counts_per_object)
+    if len(sizes) != n_runs_obj:
+        raise ValueError(f"rle_bits: {n_runs_obj} objects but {len(sizes)} sizes")
+    _, t = pack_rle_masks([[c] for c in counts_per_object], sizes)   # validates: integers, non-negative, sum h*w
+    d_sizes = [(int(h), int(w)) for h, w in dense[2]] if dense is not None else []
+    extra = dict(run_start=t["run_start"], obj_run_off=t["obj_run_off"])
+    all_sizes = [(int(h), int(w)) for h, w in sizes] + d_sizes
+    cells = rle_bits_cells(all_sizes)
+    first_dense = int(sum(cells[:n_runs_obj]))
+    if d_sizes:
+        extra["dense_off"] = np.asarray(dense[1], np.int64).reshape(-1)
+        if extra["dense_off"].size != len(d_sizes):
+            raise ValueError("rle_bits: one byte offset per dense object is needed")
+        extra["dense_cell_off"] = np.cumsum([0] + cells[n_runs_obj:-1], dtype=np.int64)      # from the dense objects' first word
+    lay, d = _bits_layout(all_sizes, device, extra)
+    ws = torch.empty((lay.cells,), dtype=torch.int32, device=device)
+    lib = _native.lib()
+    with torch.cuda.device(device):
+        if n_runs_obj:
+            _native.check(lib.seam_rle_bits_from_runs(_ptr(d["run_start"]) if d["run_start"].numel() else None, _ptr(d["obj_run_off"]),
+                                                      int(t["obj_run_off"][-1]), lay.hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]),
+                                                      _ptr(ws), 4 * lay.cells, n_runs_obj, _stream()), "seam_rle_bits_from_runs")
+        if d_sizes:
+            flat = _req(dense[0], torch.uint8, "dense")
+            if flat.dim() != 1 or flat.device != device:
+                raise ValueError(f"rle_bits: the dense buffer must be a flat uint8 tensor on {device}")
+            tail = ws[first_dense:]
+            scratch = torch.empty_like(tail)                          # the encoder's count stage comes with its values stage
+            hw_tail = np.ascontiguousarray(lay.hw[n_runs_obj:])
+            _native.check(lib.seam_rle_encode_masks_u8(_ptr(flat), flat.numel(), hw_tail.ctypes.data_as(C.c_void_p),
+                                                       _ptr(d["obj_hw"][2 * n_runs_obj:]), _ptr(d["dense_off"]),
+                                                       _ptr(d["dense_cell_off"]), _ptr(tail), 4 * tail.numel(), _ptr(scratch),
+                                                       len(d_sizes), _stream()), "seam_rle_encode_masks_u8")
+    return ws, lay
+
+
+def bits_combine(ws: torch.Tensor, lay: BitsLayout, groups: Sequence[Sequence[int]], intersect: bool = False):
+    """``groups[g]``: indices of objects of ``(ws, lay)``, all of one size -> (ws2, lay2) with object g the union (``intersect``:
+    the intersection) of its group (``seam_rle_bits_combine``).  ValueError for an empty group, an index out of range or a group
+    of mixed sizes."""
+    import numpy as np
+    sizes = []
+    for g, grp in enumerate(groups):
+        idx = [int(i) for i in grp]
+        if not idx or min(idx) < 0 or max(idx) >= lay.n:
+            raise ValueError(f"bits_combine: group {g} must name at least one object of 0..{lay.n - 1}")
+        shapes = {(int(lay.hw[i, 0]), int(lay.hw[i, 1])) for i in idx}
+        if len(shapes) > 1:
+            raise ValueError(f"bits_combine: group {g} mixes the sizes {sorted(shapes)}")
+        sizes.append(shapes.pop())
+    group_off = np.zeros(len(groups) + 1, np.int32)
+    np.cumsum([len(g) for g in groups], out=group_off[1:])
+    group_obj = np.asarray([int(i) for g in groups for i in g], np.int32)
+    lay2, d = _bits_layout(sizes, ws.device, dict(group_off=group_off, group_obj=group_obj))
+    ws2 = torch.empty((lay2.cells,), dtype=torch.int32, device=ws.device)
+    if groups:
+        with torch.cuda.device(ws.device):
+            _native.check(_native.lib().seam_rle_bits_combine(
+                _ptr(d["group_off"]), _ptr(d["group_obj"]), int(group_obj.size), _ptr(lay.dev["obj_hw"]), _ptr(lay.dev["cell_off"]),
+                _ptr(ws), 4 * ws.numel(), lay.n, lay2.hw_ptr, _ptr(lay2.dev["obj_hw"]), _ptr(lay2.dev["cell_off"]), _ptr(ws2),
+                4 * lay2.cells, lay2.n, int(bool(intersect)), _stream()), "seam_rle_bits_combine")
+    return ws2, lay2
+
+
+def bits_to_rle(ws: torch.Tensor, lay: BitsLayout) -> list:
+    """Bitmaps -> one NumPy int64 canonical ``counts`` array per object (``seam_rle_count_bits``, the prefix sum,
+    ``seam_rle_positions_masks``): what ``rle_encode`` gives for the same masks.  Two device-to-host copies, as ``rle_encode``."""
+    if lay.n == 0:
+        return []
+    counts = torch.empty((lay.cells,), dtype=torch.int32, device=ws.device)
+    lib = _native.lib()
+    d = lay.dev
+    with torch.cuda.device(ws.device):
+        _native.check(lib.seam_rle_count_bits(lay.hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]), _ptr(ws), 4 * lay.cells,
+                                              _ptr(counts), lay.n, _stream()), "seam_rle_count_bits")
+
+        def positions(scan, pos, total):
+            _native.check(lib.seam_rle_positions_masks(lay.hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]), _ptr(ws), 4 * lay.cells,
+                                                       _ptr(scan), _ptr(pos) if total else None, total, lay.n, _stream()),
+                          "seam_rle_positions_masks")
+
+        return _rle_finish(counts, d["cell_off"][1:] - 1, [(int(h), int(w)) for h, w in lay.hw], positions)
+
+
+def bits_inter(ws: torch.Tensor, lay: BitsLayout, pairs, areas: bool = True) -> torch.Tensor:
+    """``pairs`` int [P,2] (object indices of one size each) -> device int64 ``[P (+ n)]``: the pairs' ``popcount(a & b)``
+    (``seam_rle_bits_inter``) followed, with ``areas``, by every object's own popcount (``seam_rle_bits_area``), so that one
+    host copy brings both.  ValueError for an index out of range or a pair of two sizes."""
+    import numpy as np
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int64).reshape(-1, 2))
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= lay.n):
+        raise ValueError(f"bits_inter: pairs must name objects of 0..{lay.n - 1}")
+    if pairs.size and (lay.hw[pairs[:, 0]] != lay.hw[pairs[:, 1]]).any():
+        raise ValueError("bits_inter: the two objects of a pair must share a size")
+    P = int(pairs.shape[0])
+    out = torch.empty((P + (lay.n if areas else 0),), dtype=torch.int64, device=ws.device)
+    lib = _native.lib()
+    d = lay.dev
+    with torch.cuda.device(ws.device):
+        if P:
+            dp = torch.from_numpy(pairs.astype(np.int32)).to(ws.device)
+            _native.check(lib.seam_rle_bits_inter(_ptr(dp), P, lay.hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]), _ptr(ws),
+                                                  4 * lay.cells, lay.n, _ptr(out), _stream()), "seam_rle_bits_inter")
+        if areas and lay.n:
+            _native.check(lib.seam_rle_bits_area(lay.hw_ptr, _ptr(d["obj_hw"]), _ptr(d["cell_off"]), _ptr(ws), 4 * lay.cells, lay.n,
+                                                 _ptr(out[P:]), _stream()), "seam_rle_bits_area")
+    return out
+
+
+def budget_chunks(costs: Sequence[int], budget: int = None) -> list:
+    """Consecutive index ranges ``(lo, hi)`` whose costs sum to at most ``budget`` (``RLE_BITS_BUDGET_BYTES``); an item that
+    alone exceeds it gets a chunk of its own."""
+    budget = RLE_BITS_BUDGET_BYTES if budget is None else int(budget)
+    out, lo, acc = [], 0, 0
+    for i, c in enumerate(costs):
+        if i > lo and acc + c > budget:
+            out.append((lo, i))
+            lo, acc = i, 0
+        acc += int(c)
+    if len(costs) > lo:
+        out.append((lo, len(costs)))
+    return out
+
+
+def rle_merge(groups: Sequence[Sequence], sizes: Sequence[Sequence[int]], intersect: bool = False) -> list:
+    """``groups[g]``: the counts arrays of the RLEs to merge, all of ``sizes[g]`` -> one canonical counts array per group.  The
+    groups are processed in chunks of ``RLE_BITS_BUDGET_BYTES`` of source and destination bitmaps."""
+    cells = rle_bits_cells(sizes)
+    out = []
+    for lo, hi in budget_chunks([4 * c * (len(g) + 1) for c, g in zip(cells, groups)]):
+        flat = [c for g in groups[lo:hi] for c in g]
+        flat_sizes = [sizes[i] for i in range(lo, hi) for _ in groups[i]]
+        ws, lay = rle_bits(flat, flat_sizes)
+        idx, k = [], 0
+        for g in groups[lo:hi]:
+            idx.append(list(range(k, k + len(g))))
+            k += len(g)
+        out += bits_to_rle(*bits_combine(ws, lay, idx, intersect))
+    return out
+
+
 # ------------------------------------------------------------------------------ optimizer step + in-place pack refresh
 def sgd_chunk_table(numels: Sequence[int], chunk: int):
     """Host logic of ``seam_sgd_step_f32``'s chunk table: (tensor, count, offset) rows that put every element of every tensor into

@@ -6,24 +6,31 @@ A refactor that only moves helpers between files must leave every kernel's assem
 .hip there and here with the Makefile's flags plus -S --cuda-device-only, drops comments, replaces the per-translation-unit
 __hip_cuid_<hash> by a constant, splits the rest at the kernel labels and prints every kernel whose text differs, with the first
 differing line.  It compares texts only.  Exit code 1 if any kernel differs (or a file fails to compile).  Needs no GPU.
+A kernel that <git-ref> does not have is listed as added and is no difference; the module's closing metadata, which names every
+kernel, is then not compared.
 usage: isa_same.py <git-ref> [-DNAME[=VALUE] ...] [file.hip ...]"""
 import glob, io, os, re, subprocess, sys, tarfile, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "seam-match-rcnn_amd/csrc"
+METADATA = "<module metadata>"
 
 
 def kernels(asm):
     """{label: [lines]} of one assembly text: comments dropped, the cuid hash normalised, split at the kernel (function) labels;
-    what precedes the first label and the metadata behind the last kernel are kept too, under '' and under their own labels."""
+    what precedes the first label and the metadata behind the last kernel are kept too, under '' and under their own labels.  A
+    function's own `.section .text.<symbol>` line opens its text (it precedes the label), the module's closing sections open
+    METADATA: what follows a kernel does not depend on which kernel comes next."""
     out, label = {"": []}, ""
     for l in re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", asm).splitlines():
         l = l.split(";")[0].rstrip() if '"' not in l else l.rstrip()
         if not l.strip():
             continue
-        m = re.match(r"^(_Z[\w$]*|[A-Za-z][\w$]*):", l)
+        m = re.match(r"^(_Z[\w$]*|[A-Za-z][\w$]*):", l) or re.match(r"^\s*\.section\s+\.text\.([\w$]+),", l)
         if m:
             label = m.group(1)
+        elif re.match(r"^\s*(\.section\s+\.AMDGPU\.|\.amdgpu_metadata)", l):
+            label = METADATA
         out.setdefault(label, []).append(l)
     return out
 
@@ -65,6 +72,10 @@ def main(argv):
             bad += 1
             continue
         diff = differing(old.stdout, new.stdout)
+        added = [k for k, x, _ in diff if x == "<absent>" and k not in kernels(old.stdout)]
+        if added:
+            print(f"{f}: added, not at {ref}: {', '.join(k[:100] for k in added)}")
+            diff = [d for d in diff if d[0] not in added and d[0] != METADATA]
         for k, x, y in diff:
             print(f"{f}: {k[:100]}: `{x}` -> `{y}`")
         print(f"{f}: {len(kernels(new.stdout)) - 1} labels compared, {len(diff)} differ")
