@@ -915,6 +915,31 @@ int seam_rle_masks_u8(const int* run_start, const int* obj_run_off, const int* o
                       uint8_t* out, int n, seam_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The input stage of a training step, csrc/seam_input.hip: a batch that crossed the bus as image bytes and annotation integers.
+ *
+ * seam_preprocess_u8_batch_f32: n uint8 HWC RGB images of different sizes in one flat DEVICE buffer `imgs` of imgs_bytes bytes,
+ *   image i at byte img_off[i] (int64 [n], any alignment), img_dims int32 [n][5] = (in_h, in_w, out_h, out_w, flip).  ONE launch:
+ *   ToTensor (byte / 255.f) + horizontal flip + (v - mean) / std + bilinear resize to (out_h, out_w) + zero pad to (Hp, Wp) +
+ *   layout: s2d = 0 -> out [n, Hp, Wp, 4] (fourth channel zero), s2d != 0 -> out [n, Hp/2, Wp/2, 12], channel (dy*2 + dx)*3 + c
+ *   = pixel (2Y+dy, 2X+dx), colour c.  Every cell of `out` is written (zero outside an image's out_h x out_w).  The arithmetic is
+ *   seam_preprocess_f32 / seam_preprocess_s2d_batch_f32 on the flipped byte / 255.f image, bit for bit.  An image whose entry
+ *   does not fit imgs_bytes or the padded frame is written as zeros.
+ *   Refused: n < 1, n > 65535, Hp or Wp < 1, Hp > 65535, odd Hp / Wp with s2d, a NULL pointer.
+ * seam_poly_masks_resized_u8 / seam_rle_masks_resized_u8: the tables of seam_poly_masks_u8 / seam_rle_masks_u8 (obj_hw is the
+ *   SOURCE image size) plus obj_out int32 [n][3] = (out_h, out_w, flip); object o's [out_h, out_w] bytes go to
+ *   out + obj_out_off[o], output pixel (r, c) = source pixel (sy(r), flip ? w - 1 - sx(c) : sx(c)), s(i) = min(floor(i *
+ *   ((float)in / (float)out)), in - 1) in fp32 (ATen's nearest rule): the nearest resize of the flipped mask, without the
+ *   original-size stack.  An object reaching past out_bytes is skipped.  Same toggle + scan stages, same refusals. */
+int seam_preprocess_u8_batch_f32(const uint8_t* imgs, int64_t imgs_bytes, const int64_t* img_off, const int* img_dims, float* out,
+                                 int n, int Hp, int Wp, int s2d, seam_stream_t stream);
+int seam_poly_masks_resized_u8(const int* pts, const int* part_off, const int* part_obj, const int* edge_pt_off,
+                               const int64_t* part_ws_off, const int* obj_hw, const int* obj_out, const int64_t* obj_out_off,
+                               uint8_t* out, int64_t out_bytes, void* ws, int64_t ws_bytes, int P, int V, int T, int n,
+                               seam_stream_t stream);
+int seam_rle_masks_resized_u8(const int* run_start, const int* obj_run_off, const int* obj_hw, const int* obj_out,
+                              const int64_t* obj_out_off, uint8_t* out, int64_t out_bytes, int n, seam_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Masks to COCO run-length encoding, csrc/seam_rle.hip: maskApi.c's rleEncode, the opposite direction of the block above.
  * The mask is flattened COLUMN-MAJOR (position p = x*h + y); runs of 0 and 1 alternate, the first a run of zeros.  What the
  * device produces, per object, is the ascending list of positions p with v(p) != v(p-1), v(-1) = 0 (the pixel before (0, x)

@@ -221,6 +221,9 @@ SIGNATURES = {
     "seam_poly_masks_ws_bytes": (_i64, [_i, _i]),
     "seam_poly_masks_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "seam_rle_masks_u8": (_i, [_p, _p, _p, _p, _p, _i, _p]),
+    "seam_preprocess_u8_batch_f32": (_i, [_p, _i64, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "seam_poly_masks_resized_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i, _i, _i, _i, _p]),
+    "seam_rle_masks_resized_u8": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _p]),
     "seam_rle_encode_ws_bytes": (_i64, [_i, _i]),
     "seam_rle_encode_masks_u8": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _p]),
     "seam_rle_encode_paste_f32": (_i, [_p, _p, _i, _i, _i, _p, _i64, _p, _p]),

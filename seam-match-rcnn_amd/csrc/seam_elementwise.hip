@@ -17,18 +17,7 @@ template <typename T> struct Vec16;                       // 16 bytes of T
 template <> struct Vec16<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
 template <> struct Vec16<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(8))); static constexpr int N = 8; };
 
-__device__ __forceinline__ void bilinear_axis(int dst, int in, int out, int& i0, int& i1, float& l1) {
-    // ATen upsample_bilinear2d, align_corners=False, scale = in/out (recompute_scale_factor=True)
-    const float scale = (float)in / (float)out;
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    int i = (int)src;
-    if (i > in - 1) i = in - 1;
-    i0 = i;
-    i1 = (i < in - 1) ? i + 1 : i;
-    float l = src - (float)i;
-    l1 = fminf(fmaxf(l, 0.f), 1.f);
-}
+using seam_fpn::bilinear_axis;
 
 template <typename T>
 __global__ void preprocess_kernel(const float* __restrict__ img, T* __restrict__ out, int in_h, int in_w,

@@ -1,0 +1,86 @@
+"""The input stage of a phase-1 training step on the device: what the reference's loop does between the dataloader and the model
+(``stuffs/engine.py:38-39``, two ``.to(device)`` lines behind a dataset that has already run ``to_tensor``, the flip and
+``annToMask`` on the host), for a batch from a lazy ``datasets.DF2Dataset.DeepFashion2Dataset``::
+
+    for images, targets, ids in get_dataloader(dataset, batch_size, is_parallel):
+        images, targets = prepare_batch(images, targets, device, model)
+        loss_dict = model(images, targets)
+
+The batch crosses the bus as image bytes (3 per pixel instead of the 12 of a float CHW image) and a few KB of annotation integers.
+One launch (``ops.preprocess_u8_batch``) does ToTensor + flip + normalise + resize + pad + layout for all the images, whatever their
+sizes; one launch sequence (``mask_utils.masks_from_annotations_resized``) writes the flipped ground-truth masks at the resized
+size.  Both are the bits of the eager route (tests/test_gpu_train_input_model.py), which keeps working.
+"""
+from __future__ import annotations
+
+import math
+from typing import Sequence
+
+import torch
+
+from . import mask_utils, ops
+from .models import detection as det
+from .models.detection import PreparedImages  # noqa: F401  (the public name lives here)
+
+_LAZY_KEYS = ("segmentation", "size", "hflip")
+
+
+def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None) -> PreparedImages:
+    """uint8 ``[H,W,3]`` images (host or device) -> the batch ``model.transform`` would build from ``to_tensor`` of them (flipped
+    where ``flips[i]``) for the model's current ``min_size`` / ``max_size`` / ``size_divisible`` and stem form, in one launch."""
+    tr = model.transform
+    if det.adt(tr) != torch.float32:
+        raise NotImplementedError("prepare_batch writes fp32 batches only (training is fp32 only); with an fp16 compute dtype hand "
+                                  "the uint8 [H,W,3] images to the model as a list: the per-image uint8 path (seam_preprocess_u8)")
+    images = list(images)
+    if not images:
+        raise ValueError("prepare_batch: empty image list")
+    if not all(isinstance(i, torch.Tensor) and i.dtype == torch.uint8 and i.dim() == 3 and i.shape[2] == 3 for i in images):
+        raise ValueError("prepare_batch: the images must be uint8 [H,W,3] tensors (a dataset built with lazy=True / ToTensor(lazy=True))")
+    orig = [(int(i.shape[0]), int(i.shape[1])) for i in images]
+    sizes = [det.resized_size(h, w, tr.min_size, tr.max_size)[:2] for h, w in orig]
+    d = tr.size_divisible
+    hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
+    wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
+    s2d = tr.prepared_s2d()
+    x = ops.preprocess_u8_batch(images, sizes, hp, wp, flips, s2d, device=device)
+    return PreparedImages(x, sizes, orig, (hp, wp), tr.min_size, tr.max_size, d, s2d)
+
+
+def prepare_batch(images: Sequence[torch.Tensor], targets: Sequence[dict], device, model, masks: str = "resized"):
+    """(images, targets) of a lazy dataset -> (``PreparedImages``, targets on ``device``) for ``model(images, targets)``.
+
+    A target's ``"hflip"`` (set by ``transform.RandomHorizontalFlip`` on a uint8 image, whose bytes it leaves alone) flips the
+    image inside the preprocess launch; its boxes are flipped already and stay in original-image pixels (the model rescales
+    them).  ``"segmentation"`` + ``"size"`` become ``"masks"``: ``masks="resized"`` -- flipped, at the size the transform
+    resizes the image to, which ``resize_masks_nearest`` passes through (training); ``masks="original"`` -- flipped at the
+    image's own size, through ``targets_to_device`` and a device flip (what ``evaluator_det`` reads).  Other tensors move to
+    ``device``; other values pass through."""
+    if masks not in ("resized", "original"):
+        raise ValueError('prepare_batch: masks must be "resized" or "original"')
+    images, targets = list(images), list(targets)
+    if len(images) != len(targets):
+        raise ValueError("one target dict per image is needed")
+    flips = [bool(t.get("hflip", False)) for t in targets]
+    prepared = prepare_images(images, device, model, flips)
+    device = prepared.tensor.device
+    for i, (t, o) in enumerate(zip(targets, prepared.orig)):
+        if "segmentation" in t and "size" not in t:
+            raise ValueError(f"prepare_batch: target {i} has 'segmentation' but no 'size' (h, w)")
+        if "size" in t and tuple(int(v) for v in t["size"]) != o:
+            raise ValueError(f"prepare_batch: target {i}: size {tuple(t['size'])} is not the image's {o}")
+    if masks == "original":
+        out = mask_utils.targets_to_device([{k: v for k, v in t.items() if k != "hflip"} for t in targets], device)
+        for t, f in zip(out, flips):
+            if f and "masks" in t:
+                t["masks"] = t["masks"].flip(-1)
+        return prepared, out
+    out = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in t.items() if k not in _LAZY_KEYS} for t in targets]
+    with_segm = [i for i, t in enumerate(targets) if "segmentation" in t]
+    if with_segm:
+        stacks = mask_utils.masks_from_annotations_resized([targets[i]["segmentation"] for i in with_segm],
+                                                           [prepared.orig[i] for i in with_segm],
+                                                           [prepared.sizes[i] for i in with_segm], [flips[i] for i in with_segm], device)
+        for i, m in zip(with_segm, stacks):
+            out[i]["masks"] = m
+    return prepared, out

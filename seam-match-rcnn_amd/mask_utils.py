@@ -108,20 +108,40 @@ def masks_from_annotations(annos_per_image: Sequence[Sequence], sizes: Sequence[
     what ``torch.stack([annToMask(obj, size) for obj in anno])`` gives per image.  The whole batch is one table upload and one
     launch sequence per annotation form present.  ValueError (naming image and object) for an RLE whose counts do not sum to
     h*w, a dict size that disagrees with ``sizes[i]``, an odd-length or empty polygon part, non-finite coordinates."""
-    if len(annos_per_image) != len(sizes):
-        raise ValueError(f"masks_from_annotations: {len(annos_per_image)} images but {len(sizes)} sizes")
-    polys, rles = [], []
-    for i, (annos, size) in enumerate(zip(annos_per_image, sizes)):
-        if len(size) != 2:
-            raise ValueError(f"masks_from_annotations: image {i}: size must be (h, w)")
-        pairs = [_split(_segm(a), size, f"masks_from_annotations: image {i} object {j}") for j, a in enumerate(annos)]
-        polys.append([p for p, _ in pairs])
-        rles.append([r for _, r in pairs])
-    lay, rle_tables = ops.pack_rle_masks(rles, sizes)       # every ValueError is raised before the device is touched
-    _, poly_tables = ops.pack_poly_masks(polys, sizes)
+    lay, rle_tables, poly_tables = _pack_annotations(annos_per_image, sizes)
     flat = ops.mask_flat(lay, device)
     ops.launch_rle_masks(lay, rle_tables, device, flat)
     return ops.launch_poly_masks(lay, poly_tables, device, flat)
+
+
+def _pack_annotations(annos_per_image, sizes, who: str = "masks_from_annotations"):
+    """(layout, RLE tables, polygon tables) of a batch of annotations; every ValueError is raised before the device is touched and
+    names ``who``, the public function that was called."""
+    if len(annos_per_image) != len(sizes):
+        raise ValueError(f"{who}: {len(annos_per_image)} images but {len(sizes)} sizes")
+    polys, rles = [], []
+    for i, (annos, size) in enumerate(zip(annos_per_image, sizes)):
+        if len(size) != 2:
+            raise ValueError(f"{who}: image {i}: size must be (h, w)")
+        pairs = [_split(_segm(a), size, f"{who}: image {i} object {j}") for j, a in enumerate(annos)]
+        polys.append([p for p, _ in pairs])
+        rles.append([r for _, r in pairs])
+    lay, rle_tables = ops.pack_rle_masks(rles, sizes)
+    _, poly_tables = ops.pack_poly_masks(polys, sizes)
+    return lay, rle_tables, poly_tables
+
+
+def masks_from_annotations_resized(annos_per_image: Sequence[Sequence], sizes: Sequence[Sequence[int]],
+                                   out_sizes: Sequence[Sequence[int]], flips, device) -> list:
+    """``masks_from_annotations`` for a training step: image i's stack comes out at ``out_sizes[i]`` (the size the model's
+    transform resizes the image to), flipped left-right where ``flips[i]`` -- uint8 ``[n_i, *out_sizes[i]]``, bit for bit
+    ``resize_masks_nearest(stack.flip(-1) if flip else stack, out_size)`` of what ``masks_from_annotations`` returns, without
+    writing the original-size stack (``seam_poly_masks_resized_u8`` / ``seam_rle_masks_resized_u8``)."""
+    lay, rle_tables, poly_tables = _pack_annotations(annos_per_image, sizes, "masks_from_annotations_resized")
+    out_lay, _ = ops.resized_mask_layout(lay, out_sizes, flips)
+    flat = ops.mask_flat(out_lay, device)
+    ops.launch_rle_masks_resized(lay, rle_tables, out_sizes, flips, device, flat)
+    return ops.launch_poly_masks_resized(lay, poly_tables, out_sizes, flips, device, flat)
 
 
 def annToMask(ann, size) -> np.ndarray:

@@ -95,14 +95,48 @@ def resized_size(h: int, w: int, min_size: int = 800, max_size: int = 1333) -> T
     return int(math.floor(float(h) * scale)), int(math.floor(float(w) * scale)), scale
 
 
+class PreparedImages:
+    """A batch that ``input_pipeline.prepare_batch`` has already taken through the transform on the device: what
+    ``GeneralizedRCNNTransform.forward`` returns -- the batch tensor, ``sizes`` (resized), ``orig`` (original) and ``padded`` --
+    with the settings it was built for (``min_size``, ``max_size``, ``size_divisible``, ``s2d``: the space-to-depth layout).
+    The transform hands its contents on when the settings are the model's own and raises ValueError otherwise."""
+
+    def __init__(self, tensor, sizes, orig, padded, min_size, max_size, size_divisible, s2d):
+        self.tensor, self.sizes, self.orig, self.padded = tensor, list(sizes), list(orig), tuple(padded)
+        self.min_size, self.max_size, self.size_divisible, self.s2d = min_size, max_size, size_divisible, bool(s2d)
+
+    def __len__(self):
+        return len(self.sizes)
+
+
+def image_list(images):
+    """The images of a forward as the transform takes them: a ``PreparedImages`` as it is, anything else listed and detached."""
+    return images if isinstance(images, PreparedImages) else [i.detach() for i in images]
+
+
 class GeneralizedRCNNTransform(nn.Module):
     def __init__(self, min_size=800, max_size=1333, size_divisible=32):
         super().__init__()
         self.min_size, self.max_size, self.size_divisible = min_size, max_size, size_divisible
 
+    def prepared_s2d(self) -> bool:
+        """The layout a ``PreparedImages`` must have here: what float images get below."""
+        return STEM_S2D and cdt(self) == torch.float32
+
     def forward(self, images: Sequence[torch.Tensor]):
         """list of [3,H,W] in [0,1] -> (NHWC batch [N,Hp,Wp,4] fp32 | [N,Hp,Wp,8] fp16, image_sizes,
-        original_sizes)."""
+        original_sizes).  A ``PreparedImages`` (``input_pipeline.prepare_batch``) is that result already: its contents are
+        returned when it was built for this transform's settings and layout."""
+        if isinstance(images, PreparedImages):
+            p = images
+            if (p.min_size, p.max_size, p.size_divisible) != (self.min_size, self.max_size, self.size_divisible):
+                raise ValueError(f"PreparedImages was built for min_size, max_size, size_divisible = "
+                                 f"{(p.min_size, p.max_size, p.size_divisible)}, the model's transform has "
+                                 f"{(self.min_size, self.max_size, self.size_divisible)}: prepare the batch again")
+            if adt(self) != torch.float32 or p.tensor.dtype != torch.float32 or p.s2d != self.prepared_s2d():
+                raise ValueError("PreparedImages: the batch's layout (fp32, space-to-depth or NHWC4) is not the one the model's "
+                                 "compute dtype and stem form take: prepare the batch again")
+            return p.tensor, p.sizes, p.orig, p.padded
         # float [3,H,W] in [0,1] (the reference's input) or, as an extension, raw uint8 [H,W,3] frames
         orig = [(int(i.shape[0]), int(i.shape[1])) if i.dtype == torch.uint8 else (int(i.shape[-2]), int(i.shape[-1]))
                 for i in images]

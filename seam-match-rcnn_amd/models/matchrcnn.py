@@ -254,12 +254,13 @@ class MatchRCNN(VideoMatchRCNN):
         fpn_learns = any(p.requires_grad for p in self.backbone.fpn.parameters())
         if any(det.cdt(m) != torch.float32 for m in (self, self.backbone, self.rpn, self.roi_heads)):
             raise NotImplementedError("MatchRCNN training is fp32 only: call set_compute_dtype(torch.float32)")
-        images = list(images)
+        if not isinstance(images, det.PreparedImages):
+            images = list(images)
         if len(images) != len(targets):
             raise ValueError("one target dict per image is needed")
         if body_learns or fpn_learns:
             with torch.no_grad():
-                x, sizes, orig, padded = self.transform([i.detach() for i in images])
+                x, sizes, orig, padded = self.transform(det.image_list(images))
             if body_learns:                 # the body through BodyFunction; a frozen FPN still passes its gradient to C2..C5
                 c = body(x, taped=True)
             else:                           # body without a tape, the pyramid through FPNFunction
@@ -268,7 +269,7 @@ class MatchRCNN(VideoMatchRCNN):
             feats = self.backbone.fpn.forward_taped(c)
         else:
             with torch.no_grad():
-                feats, sizes, orig, padded = self.extract_features([i.detach() for i in images])
+                feats, sizes, orig, padded = self.extract_features(det.image_list(images))
         dev = feats["0"].device
         tg = []
         for t, s, o in zip(targets, sizes, orig):         # GeneralizedRCNNTransform.resize of the targets [TV]

@@ -296,10 +296,11 @@ class VideoMatchRCNN(nn.Module):
             raise NotImplementedError(
                 "VideoMatchRCNN on HIP is the inference forward; the reference's training loop calls it under "
                 "model.eval() + torch.no_grad() (stuffs/engine.py:113-116)")
-        images = list(images)
-        if not images:
+        if not isinstance(images, det.PreparedImages):
+            images = list(images)
+        if not len(images):
             return []
-        feats, sizes, orig, padded = self.extract_features([i.detach() for i in images])
+        feats, sizes, orig, padded = self.extract_features(det.image_list(images))
         # padded proposals: the forward synchronises with the device ONCE, at the detection counts (ONE_SYNC = False: the
         # reference's list form, one more sync at the RPN's variable-length split; identical results, tested)
         one_sync = self.ONE_SYNC if self.ONE_SYNC is not None else self.rpn.post_nms_top_n <= 1000

@@ -870,6 +870,121 @@ def preprocess(images: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, 
     return out
 
 
+def preprocess_u8_flat(flat: torch.Tensor, img_off: torch.Tensor, img_dims: torch.Tensor, hp: int, wp: int, s2d: bool,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``seam_preprocess_u8_batch_f32`` on device tables: ``flat`` uint8 [bytes] holds N HWC images, image i at byte
+    ``img_off[i]`` (int64 [N]), ``img_dims`` int32 [N,5] = (in_h, in_w, out_h, out_w, flip) -> fp32 [N,hp,wp,4] or, ``s2d``,
+    [N,hp/2,wp/2,12].  One launch; every cell of the result is written (``out``: a tensor of that shape to write into)."""
+    flat, img_off, img_dims = _req(flat, torch.uint8, "flat"), _req(img_off, torch.int64, "img_off"), _req(img_dims, torch.int32, "img_dims")
+    n = img_off.numel()
+    hp, wp = int(hp), int(wp)
+    if flat.dim() != 1 or img_off.dim() != 1 or tuple(img_dims.shape) != (n, 5):
+        raise ValueError("preprocess_u8_flat: flat uint8 [bytes], img_off int64 [N] and img_dims int32 [N,5] are needed")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"preprocess_u8_flat: 1 <= N <= 65535 images per launch, got {n}")
+    if s2d and (hp % 2 or wp % 2):
+        raise ValueError("preprocess_u8_flat(s2d=True): an even padded size is needed")
+    shape = (n, hp // 2, wp // 2, 12) if s2d else (n, hp, wp, 4)
+    if out is None:
+        out = torch.empty(shape, dtype=F32, device=flat.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == F32 and tuple(out.shape) == shape and out.is_contiguous()
+              and out.device == flat.device):
+        raise ValueError(f"preprocess_u8_flat: out must be a contiguous fp32 {shape} tensor on {flat.device}")
+    with torch.cuda.device(flat.device):
+        _native.check(_native.lib().seam_preprocess_u8_batch_f32(_ptr(flat), flat.numel(), _ptr(img_off), _ptr(img_dims), _ptr(out), n,
+                                                                 hp, wp, 1 if s2d else 0, _stream()), "seam_preprocess_u8_batch_f32")
+    return out
+
+
+_STAGING = {}      # (device, thread) -> (pinned uint8 buffer, event of the last copy out of it)
+
+
+def _staging_key(device):
+    import threading
+    return (device, threading.get_ident())
+
+
+def _staging(nbytes: int, device) -> torch.Tensor:
+    """The calling thread's pinned staging buffer for ``device``, grown when needed; the copy that last read it has finished when
+    this returns.  One buffer per device and thread: two threads that prepare batches at once never share bytes, and within a
+    thread a buffer is written only after its last copy's event, whichever stream carried that copy."""
+    key = _staging_key(device)
+    buf, ev = _STAGING.get(key, (None, None))
+    if ev is not None:
+        ev.synchronize()
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8).pin_memory()
+    _STAGING[key] = (buf, None)
+    return buf
+
+
+def stage_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips, device):
+    """The host side of ``preprocess_u8_batch`` for host images: the tables (int64 byte offsets, then int32 [N,5] dims) and the
+    images' bytes packed into the pinned staging buffer of ``device`` -> (the pinned uint8 view to copy, N)."""
+    import numpy as np
+    n = len(images_u8)
+    dims = np.asarray([(int(i.shape[0]), int(i.shape[1]), int(s[0]), int(s[1]), int(f)) for i, s, f in zip(images_u8, sizes, flips)],
+                      np.int32)
+    if (dims[:, 2:4] < 1).any() or (dims[:, 2] > hp).any() or (dims[:, 3] > wp).any():
+        raise ValueError("preprocess_u8_batch: every resized size must lie in [1, hp] x [1, wp]")
+    nbytes = dims[:, 0].astype(np.int64) * dims[:, 1] * 3
+    head = 32 * ((28 * n + 31) // 32)                     # tables first, the images from `head` on
+    off = head + np.cumsum(nbytes) - nbytes
+    total = int(head + nbytes.sum())
+    tables = np.concatenate([off.astype(np.int64).view(np.uint8), dims.reshape(-1).view(np.uint8)])
+    if device is None:                                    # images that lie on the device already: the tables alone
+        return torch.from_numpy(np.concatenate([tables, np.zeros(head - tables.size, np.uint8)])), n
+    stage = _staging(total, device)
+    stage[:tables.size].copy_(torch.from_numpy(tables))
+    for i, o, b in zip(images_u8, off.tolist(), nbytes.tolist()):
+        stage[o:o + b].copy_(i.reshape(-1))
+    return stage[:total], n
+
+
+def preprocess_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips: Optional[Sequence] = None,
+                        s2d: bool = False, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ToTensor + horizontal flip + normalise + resize + pad + layout for a batch of uint8 [H,W,3] images of different sizes in ONE
+    launch (``seam_preprocess_u8_batch_f32``): image i is resized to ``sizes[i]`` and flipped where ``flips[i]``; the result is
+    what ``preprocess([to_tensor(img).flip(-1) if flip else to_tensor(img) ...], sizes, hp, wp, s2d=s2d)`` gives, bit for bit.
+    The images are all host tensors -- packed with the tables into one pinned staging buffer, ONE host-to-device copy to
+    ``device`` (default: the current HIP device) -- or all on one HIP device (``device`` is theirs).  Without a HIP device:
+    SeamNativeError, as every preprocess branch."""
+    images_u8 = list(images_u8)
+    # device check FIRST: no CPU path exists, and nothing below may run without a HIP device to write to
+    if not torch.cuda.is_available() or not all(isinstance(i, torch.Tensor) for i in images_u8):
+        raise _native.SeamNativeError("preprocess_u8_batch: expected uint8 tensors and a HIP device (no CPU path exists)")
+    on_dev = [i.is_cuda for i in images_u8]
+    n = len(images_u8)
+    if not 1 <= n <= 65535:
+        raise ValueError(f"preprocess_u8_batch: 1 <= N <= 65535 images per launch, got {n}")
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("preprocess_u8_batch: the images must be all on the host or all on one HIP device")
+    for i in images_u8:
+        if i.dtype != torch.uint8:
+            raise TypeError(f"image: expected torch.uint8, got {i.dtype}")
+        if i.dim() != 3 or i.shape[2] != 3 or i.shape[0] < 1 or i.shape[1] < 1:
+            raise ValueError("uint8 images must be [H,W,3]")
+    flips = [False] * n if flips is None else [bool(f) for f in flips]
+    if len(sizes) != n or len(flips) != n:
+        raise ValueError("preprocess_u8_batch: one size and one flip per image are needed")
+    if s2d and (int(hp) % 2 or int(wp) % 2):
+        raise ValueError("preprocess_u8_batch(s2d=True): an even padded size is needed")
+    if all(on_dev):
+        device = images_u8[0].device
+        if any(i.device != device for i in images_u8):
+            raise ValueError("preprocess_u8_batch: the images must lie on one device")
+        tables, _ = stage_u8_batch(images_u8, sizes, hp, wp, flips, None)
+        dev = torch.cat([tables.to(device)] + [i.contiguous().reshape(-1) for i in images_u8])
+    else:
+        device = _mask_device(device if device is not None else "cuda")
+        stage, _ = stage_u8_batch(images_u8, sizes, hp, wp, flips, device)
+        dev = stage.to(device, non_blocking=True)                            # the batch's one host-to-device copy
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        _STAGING[_staging_key(device)] = (_STAGING[_staging_key(device)][0], ev)
+    return preprocess_u8_flat(dev, dev[:8 * n].view(torch.int64), dev[8 * n:28 * n].view(torch.int32).view(n, 5), hp, wp, s2d, out)
+
+
 def maxpool2d(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:
     x = _req_fp(x)
     n, h, w, c = x.shape
@@ -1840,7 +1955,7 @@ def pack_poly_masks(polys: Sequence[Sequence], sizes: Sequence[Sequence[int]]):
     sel = np.asarray(sel_obj, np.int64)
     tables = dict(pts=allp.astype(np.int32), part_off=part_off.astype(np.int32), part_obj=np.asarray(part_obj, np.int32),
                   edge_pt_off=edge_pt_off.astype(np.int32), part_ws_off=part_ws_off, obj_hw=np.ascontiguousarray(lay.obj_hw[sel]),
-                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), P=P, V=V, T=T, n=len(sel_obj))
+                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), P=P, V=V, T=T, n=len(sel_obj), sel=sel)
     return lay, tables
 
 
@@ -1871,7 +1986,7 @@ def pack_rle_masks(rles: Sequence[Sequence], sizes: Sequence[Sequence[int]]):
     sel = np.asarray(sel_obj, np.int64)
     tables = dict(run_start=(np.concatenate(starts) if starts else np.zeros(0, np.int64)).astype(np.int32),
                   obj_run_off=np.asarray(run_off, np.int32), obj_hw=np.ascontiguousarray(lay.obj_hw[sel]),
-                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), n=len(sel_obj))
+                  obj_out_off=np.ascontiguousarray(lay.obj_off[sel]), n=len(sel_obj), sel=sel)
     return lay, tables
 
 
@@ -1935,6 +2050,60 @@ def launch_rle_masks(lay: MaskLayout, t: dict, device, flat: Optional[torch.Tens
             _native.check(_native.lib().seam_rle_masks_u8(*[_ptr(d[k]) for k in names], _ptr(flat), t["n"], _stream()),
                           "seam_rle_masks_u8")
     return mask_views(flat, lay)
+
+
+def resized_mask_layout(lay: MaskLayout, out_sizes: Sequence[Sequence[int]], flips: Optional[Sequence] = None):
+    """The output side of the resized expands (csrc/seam_input.hip) for a batch laid out as ``lay``: image i's objects are written
+    at ``out_sizes[i]``, flipped where ``flips[i]``.  Returns (layout of the resized stacks, obj_out int32 [n,3] = (out_h, out_w,
+    flip) per object of the batch)."""
+    import numpy as np
+    out_lay = mask_layout(lay.counts, out_sizes)
+    flips = [False] * len(lay.counts) if flips is None else [bool(f) for f in flips]
+    if len(flips) != len(lay.counts):
+        raise ValueError(f"masks: {len(lay.counts)} images but {len(flips)} flips")
+    flip = np.repeat(np.asarray(flips, np.int32), np.asarray(lay.counts, np.int64)).reshape(-1, 1)
+    return out_lay, np.concatenate([out_lay.obj_hw, flip], axis=1).astype(np.int32)
+
+
+def _resized_tables(t: dict, out_lay: MaskLayout, obj_out) -> dict:
+    import numpy as np
+    return dict(t, obj_out=np.ascontiguousarray(obj_out[t["sel"]]), obj_out_off=np.ascontiguousarray(out_lay.obj_off[t["sel"]]))
+
+
+def launch_poly_masks_resized(lay: MaskLayout, t: dict, out_sizes, flips, device, flat: Optional[torch.Tensor] = None) -> list:
+    """``launch_poly_masks`` with the expand of ``seam_poly_masks_resized_u8``: image i's stack comes out as uint8
+    ``[n_i, *out_sizes[i]]`` = ``resize_masks_nearest(stack.flip(-1) if flips[i] else stack, out_sizes[i])`` bit for bit, and the
+    original-size stack is never written.  ``flat``: the flat buffer of the RESIZED layout (``resized_mask_layout``)."""
+    device = _mask_device(device)
+    out_lay, obj_out = resized_mask_layout(lay, out_sizes, flips)
+    flat = mask_flat(out_lay, device, flat)
+    if t["n"]:
+        t = _resized_tables(t, out_lay, obj_out)
+        names = ("pts", "part_off", "part_obj", "edge_pt_off", "part_ws_off", "obj_hw", "obj_out", "obj_out_off")
+        d = _upload_tables(t, names, device)
+        ws_bytes = 4 * int(t["part_ws_off"][-1])
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        p = [_ptr(d[k]) if d[k].numel() else None for k in names]
+        with torch.cuda.device(device):
+            _native.check(_native.lib().seam_poly_masks_resized_u8(*p, _ptr(flat), flat.numel(), _ptr(ws) if ws_bytes else None,
+                                                                   ws_bytes, t["P"], t["V"], t["T"], t["n"], _stream()),
+                          "seam_poly_masks_resized_u8")
+    return mask_views(flat, out_lay)
+
+
+def launch_rle_masks_resized(lay: MaskLayout, t: dict, out_sizes, flips, device, flat: Optional[torch.Tensor] = None) -> list:
+    """``launch_rle_masks`` with the expand of ``seam_rle_masks_resized_u8`` (arguments as ``launch_poly_masks_resized``)."""
+    device = _mask_device(device)
+    out_lay, obj_out = resized_mask_layout(lay, out_sizes, flips)
+    flat = mask_flat(out_lay, device, flat)
+    if t["n"]:
+        t = _resized_tables(t, out_lay, obj_out)
+        names = ("run_start", "obj_run_off", "obj_hw", "obj_out", "obj_out_off")
+        d = _upload_tables(t, names, device)
+        with torch.cuda.device(device):
+            _native.check(_native.lib().seam_rle_masks_resized_u8(*[_ptr(d[k]) for k in names], _ptr(flat), flat.numel(), t["n"],
+                                                                  _stream()), "seam_rle_masks_resized_u8")
+    return mask_views(flat, out_lay)
 
 
 def poly_masks(polys: Sequence[Sequence], sizes: Sequence[Sequence[int]], device) -> list:
