@@ -727,6 +727,16 @@ int seam_nlb_block_bwd_f32(const float* seq, int64_t t_stride, int64_t s_stride,
  *   vertical pass -- bit-identical to Pillow (MFDataset.py:92: half resolution); ws: seam_resize_workspace_bytes. */
 int seam_frame_noise_u8(const uint8_t* bgr, const double* noise, uint8_t* rgb, int H, int W, double sigma,
                         uint64_t seed, seam_stream_t stream);
+/* seam_noise_u8_batch: the noise of MultiDeepFashion2Dataset.__getitem__ (datasets/MultiDF2Dataset.py:157-167) for a whole batch
+ *   of uint8 HWC RGB images of different sizes, in place in the flat DEVICE buffer `buf` that seam_preprocess_u8_batch_f32 reads
+ *   (img_off int64 [n_images] byte offsets, img_dims int32 [n_images,5] of which in_h and in_w are read), ONE launch:
+ *   byte e of image i becomes uint8(clip((v / 255.0 + n * sigma[i]) * 255.0, 0, 255)) in float64, n = draws[draws_off[i] + e]
+ *   (float64 draws, element offsets) or, draws NULL, the counter-based draw seam_frame_noise_u8 makes for (seed[i], e).  Element
+ *   order is the image's own (unflipped).  An image with sigma 0, or whose in_h * in_w * 3 bytes at img_off do not lie inside
+ *   buf_bytes, is left as it is; nothing outside an image is written. */
+int seam_noise_u8_batch(uint8_t* buf, int64_t buf_bytes, const int64_t* img_off, const int* img_dims, const double* sigma,
+                        const uint64_t* seed, const double* draws, const int64_t* draws_off, int n_images,
+                        seam_stream_t stream);
 int64_t seam_resize_workspace_bytes(int H, int W, int OH, int OW);
 int seam_resize_bicubic_u8(const uint8_t* in, uint8_t* out, int H, int W, int OH, int OW, void* ws,
                            seam_stream_t stream);

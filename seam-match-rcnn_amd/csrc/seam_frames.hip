@@ -25,9 +25,26 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// out[y][x][c] = uint8(clip((in[y][x][2-c] / 255.0 + n * sigma) * 255.0, 0, 255))     (ref MFDataset.py:81-88)
-// n = noise[y][x][c] (float64 standard normal draws, e.g. np.random.randn) or, when noise == NULL, a counter-based
-// Box-Muller draw keyed by (seed, element index).  sigma == 0 and noise == NULL: plain channel flip.
+// standard normal draw number i of the stream `seed`: counter-based Box-Muller on two splitmix64 hashes
+__device__ __forceinline__ double normal_draw(uint64_t seed, size_t i) {
+    const uint64_t r0 = splitmix64(seed ^ (i * 2 + 1)), r1 = splitmix64(seed ^ (i * 2 + 2) ^ 0xD1B54A32D192ED03ull);
+    const double u0 = ((double)(r0 >> 11) + 1.0) * (1.0 / 9007199254740993.0);    // (0,1)
+    const double u1 = (double)(r1 >> 11) * (1.0 / 9007199254740992.0);
+    return sqrt(-2.0 * log(u0)) * cos(6.283185307179586 * u1);
+}
+
+// uint8(clip((v / 255.0 + n * sigma) * 255.0, 0, 255)) step by step as NumPy evaluates it (contraction is off in this file)
+__device__ __forceinline__ uint8_t noisy_byte(uint8_t v, double n, double sigma) {
+    double x = (double)v / 255.0;
+    x = x + n * sigma;
+    x = x * 255.0;
+    x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
+    return (uint8_t)x;
+}
+
+// out[y][x][c] = noisy_byte(in[y][x][2-c], n, sigma)     (ref MFDataset.py:81-88)
+// n = noise[y][x][c] (float64 standard normal draws, e.g. np.random.randn) or, when noise == NULL, normal_draw(seed, element
+// index).  sigma == 0 and noise == NULL: plain channel flip.
 __global__ void frame_noise_kernel(const uint8_t* __restrict__ in, const double* __restrict__ noise, uint8_t* __restrict__ out,
                                    size_t n_elem, double sigma, uint64_t seed) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_elem; i += (size_t)gridDim.x * blockDim.x) {
@@ -35,21 +52,30 @@ __global__ void frame_noise_kernel(const uint8_t* __restrict__ in, const double*
         const int c = (int)(i - px * 3);
         const uint8_t v = in[px * 3 + (2 - c)];
         if (sigma == 0.0 && noise == nullptr) { out[i] = v; continue; }
-        double n;
-        if (noise) {
-            n = noise[i];
-        } else {
-            const uint64_t r0 = splitmix64(seed ^ (i * 2 + 1)), r1 = splitmix64(seed ^ (i * 2 + 2) ^ 0xD1B54A32D192ED03ull);
-            const double u0 = ((double)(r0 >> 11) + 1.0) * (1.0 / 9007199254740993.0);    // (0,1)
-            const double u1 = (double)(r1 >> 11) * (1.0 / 9007199254740992.0);
-            n = sqrt(-2.0 * log(u0)) * cos(6.283185307179586 * u1);
-        }
-        double x = (double)v / 255.0;
-        x = x + n * sigma;
-        x = x * 255.0;
-        x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
-        out[i] = (uint8_t)x;
+        out[i] = noisy_byte(v, noise ? noise[i] : normal_draw(seed, i), sigma);
     }
+}
+
+// The noise of MultiDeepFashion2Dataset.__getitem__ (ref MultiDF2Dataset.py:157-167) on a staged batch, in place: grid (element
+// blocks, images); byte e of image `img` (RGB order, unflipped) becomes noisy_byte(v, n, sigma[img]) with
+// n = draws[draws_off[img] + e] or, draws == NULL, normal_draw(seed[img], e).  An image with sigma 0 is not touched, nor is one
+// whose table entry does not lie inside the buffer (the buffer half of preprocess_u8_batch_kernel's `ok`, which then writes that
+// image as zeros).  Images start at any byte and rows have odd lengths: one byte load and one byte store per element.
+__global__ void noise_u8_batch_kernel(uint8_t* __restrict__ buf, int64_t buf_bytes, const int64_t* __restrict__ img_off,
+                                      const int* __restrict__ img_dims, const double* __restrict__ sigma,
+                                      const uint64_t* __restrict__ seed, const double* __restrict__ draws,
+                                      const int64_t* __restrict__ draws_off) {
+    const int img = blockIdx.y;
+    const double s = sigma[img];
+    if (s == 0.0) return;
+    const int64_t in_h = img_dims[5 * img], in_w = img_dims[5 * img + 1], off = img_off[img];
+    if (in_h <= 0 || in_w <= 0 || off < 0 || off > buf_bytes || in_h * in_w > (buf_bytes - off) / 3) return;
+    const size_t n_elem = (size_t)(in_h * in_w) * 3;
+    uint8_t* p = buf + off;
+    const double* d = draws ? draws + draws_off[img] : nullptr;
+    const uint64_t sd = seed[img];
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_elem; e += (size_t)gridDim.x * blockDim.x)
+        p[e] = noisy_byte(p[e], d ? d[e] : normal_draw(sd, e), s);
 }
 
 __device__ __forceinline__ double bicubic_filter(double x) {
@@ -142,6 +168,20 @@ int seam_frame_noise_u8(const uint8_t* bgr, const double* noise, uint8_t* rgb, i
     if (n == 0) return 0;
     const unsigned grid = seam_launch::grid256(n, 8192);
     hipLaunchKernelGGL(frame_noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, bgr, noise, rgb, n, sigma, seed);
+    return (int)hipGetLastError();
+}
+
+int seam_noise_u8_batch(uint8_t* buf, int64_t buf_bytes, const int64_t* img_off, const int* img_dims, const double* sigma,
+                        const uint64_t* seed, const double* draws, const int64_t* draws_off, int n_images, void* stream) {
+    if (n_images < 1 || n_images > 65535 || buf_bytes < 0) return (int)hipErrorInvalidValue;
+    if (!buf || !img_off || !img_dims || !sigma || !seed || (draws && !draws_off)) return (int)hipErrorInvalidValue;
+    // the image sizes are on the device: no image is larger than the buffer, and about 16k blocks in all keep every CU busy
+    // when three images in four exit at once
+    const unsigned cap = 16384u / (unsigned)n_images;
+    const dim3 grid(seam_launch::grid256((size_t)buf_bytes, cap < 32 ? 32 : cap), (unsigned)n_images);
+    if (grid.x == 0) return 0;
+    hipLaunchKernelGGL(noise_u8_batch_kernel, grid, dim3(256), 0, (hipStream_t)stream, buf, buf_bytes, img_off, img_dims, sigma,
+                       seed, draws, draws_off);
     return (int)hipGetLastError();
 }
 

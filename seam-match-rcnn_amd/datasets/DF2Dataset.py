@@ -111,9 +111,9 @@ class DeepFashion2Dataset(Dataset):
             masks[k] = torch.from_numpy(annToMask(obj, [h, w]))
         return masks
 
-    def __getitem__(self, idx):
+    def _decode(self, img_id):
+        """(the PIL RGB image of ``img_id``, its target before any transform, the sample's third element)."""
         from PIL import Image
-        img_id = self.ids[idx]
         with Image.open(os.path.join(self.root, self.coco.imgs[img_id]["file_name"])) as f:
             img = f.convert("RGB")
         h, w = img.height, img.width
@@ -133,11 +133,14 @@ class DeepFashion2Dataset(Dataset):
         for field, name, value in _OBJECT_FIELDS:
             if field in first:
                 target[name] = torch.tensor([value(obj) for obj in kept], dtype=torch.int64)
+        return img, target, first.get("image_id", img_id)
 
+    def __getitem__(self, idx):
+        img, target, image_id = self._decode(self.ids[idx])
         sample = (image_bytes(img) if self.lazy else img), target
         if self.transforms is not None:
             sample = self.transforms(*sample)
-        return sample[0], sample[1], first.get("image_id", img_id)
+        return sample[0], sample[1], image_id
 
 
 def get_dataloader(dataset, batch_size, is_parallel, num_workers=0):
@@ -149,10 +152,11 @@ def get_dataloader(dataset, batch_size, is_parallel, num_workers=0):
 
 
 class RandomSampler(Sampler):
-    """The positions ``0 .. len(dataset.accepted_entries) - 1`` in a fresh random order (torch's global generator) per pass."""
+    """The positions ``0 .. len(entries) - 1`` in a fresh random order (torch's global generator) per pass; ``entries`` is
+    ``dataset.accepted_entries`` unless given."""
 
-    def __init__(self, dataset):
-        self.entries = dataset.accepted_entries
+    def __init__(self, dataset, entries=None):
+        self.entries = dataset.accepted_entries if entries is None else entries
         if not self.entries:
             raise ValueError("RandomSampler: the dataset has no accepted entries (no match key occurs on both sides)")
 
@@ -172,12 +176,12 @@ def _world(num_replicas, rank):
 
 
 class DistributedSampler(Sampler):
-    """This rank's share of the positions of ``dataset.accepted_entries``: the permutation seeded with the epoch (``set_epoch``;
+    """This rank's share of the positions of ``entries`` (``dataset.accepted_entries`` unless given): the permutation seeded with the epoch (``set_epoch``;
     the identity when ``shuffle`` is off) is continued cyclically to a multiple of the world size and cut into one contiguous
     slice of ``len(self)`` positions per rank, so every rank takes the same number of steps."""
 
-    def __init__(self, dataset, num_replicas=None, rank=None, shuffle=True):
-        self.entries = dataset.accepted_entries
+    def __init__(self, dataset, num_replicas=None, rank=None, shuffle=True, entries=None):
+        self.entries = dataset.accepted_entries if entries is None else entries
         self.world, self.rank = _world(num_replicas, rank)
         if not 0 <= self.rank < self.world:
             raise ValueError(f"DistributedSampler: rank {self.rank} is outside a world of {self.world}")

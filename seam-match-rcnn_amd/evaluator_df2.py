@@ -35,6 +35,7 @@ import torch
 
 from . import ops
 from .evaluator import K_THRESHOLDS
+from .input_pipeline import apply_noise
 
 STEP = 6                                # images per model call (:35)
 STRATEGIES = ("best_match", "best_box_only")
@@ -85,7 +86,8 @@ def collect_descriptors(model, data_loader, device, score_threshold: float = 0.1
                         use_gt: bool = False) -> DF2Tables:
     """evaluate_multiDF2.py:26-114: run the model over (shop image, street frames...) batches in chunks of 6, pick in every image
     the kept detection that best overlaps the product's GT box (one seam_gt_select_f32 launch per product) and gather the
-    descriptors of the chosen detections."""
+    descriptors of the chosen detections.  A batch whose targets carry ``"noise_sigma"`` goes through
+    ``input_pipeline.apply_noise`` first."""
     agg = model.roi_heads.temporal_aggregator
     shop_mat, shop_aggr, shop_prods, shop_keys, shop_sel = [], [], [], [], []
     s_mat, s_aggr, s_prod, s_img, s_sel, s_score, s_box = [], [], [], [], [], [], []
@@ -95,6 +97,8 @@ def collect_descriptors(model, data_loader, device, score_threshold: float = 0.1
         images, targets_in = batch[0], batch[1]
         count_products += 1
         product = count_products - 1
+        if any("noise_sigma" in t for t in targets_in):     # a lazy MultiDeepFashion2Dataset: its noise, on the device
+            images, targets_in = apply_noise(images, targets_in, device)
         images = [im.to(device) for im in images]
         targets = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in t.items()} for t in targets_in]
         targets = [{k: (v.float() if k == "boxes" else v) for k, v in t.items()} for t in targets]

@@ -10,6 +10,11 @@ The batch crosses the bus as image bytes (3 per pixel instead of the 12 of a flo
 One launch (``ops.preprocess_u8_batch``) does ToTensor + flip + normalise + resize + pad + layout for all the images, whatever their
 sizes; one launch sequence (``mask_utils.masks_from_annotations_resized``) writes the flipped ground-truth masks at the resized
 size.  Both are the bits of the eager route (tests/test_gpu_train_input_model.py), which keeps working.
+
+A phase-2 batch from a lazy ``datasets.MultiDF2Dataset.MultiDeepFashion2Dataset`` carries ``"noise_sigma"`` / ``"noise_seed"`` in
+its targets: the reference's per-image host noise then runs as one launch (``seam_noise_u8_batch``) on the staged bytes, before
+the preprocess launch reads them, in the same copy and on the same stream.  ``apply_noise`` is that launch alone, for callers that
+hand the model lists of images.
 """
 from __future__ import annotations
 
@@ -23,11 +28,35 @@ from .models import detection as det
 from .models.detection import PreparedImages  # noqa: F401  (the public name lives here)
 
 _LAZY_KEYS = ("segmentation", "size", "hflip")
+_NOISE_KEYS = ("noise_sigma", "noise_seed")
 
 
-def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None) -> PreparedImages:
+def _noise_of(targets):
+    """``(sigmas, seeds)`` for ``ops`` when any target carries ``"noise_sigma"`` (a target without it: sigma 0), else None."""
+    if not any("noise_sigma" in t for t in targets):
+        return None
+    return [float(t.get("noise_sigma", 0.0)) for t in targets], [int(t.get("noise_seed", 0)) for t in targets]
+
+
+def _without(t: dict, keys) -> dict:
+    return {k: v for k, v in t.items() if k not in keys}
+
+
+def apply_noise(images: Sequence[torch.Tensor], targets: Sequence[dict], device):
+    """uint8 ``[H,W,3]`` images and the targets of a lazy ``MultiDeepFashion2Dataset`` -> (the noisy uint8 images on ``device``,
+    the targets without ``"noise_sigma"`` / ``"noise_seed"``), one copy and one launch (``ops.noise_u8_batch``).  For callers that
+    feed the model lists: the fp16 compute dtype, where ``prepare_images`` refuses, and the evaluator's chunks of 6."""
+    images, targets = list(images), list(targets)
+    if len(images) != len(targets):
+        raise ValueError("one target dict per image is needed")
+    sigmas, seeds = _noise_of(targets) or ([0.0] * len(targets), [0] * len(targets))
+    return ops.noise_u8_batch(images, sigmas, seeds, device=device), [_without(t, _NOISE_KEYS) for t in targets]
+
+
+def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None, noise=None) -> PreparedImages:
     """uint8 ``[H,W,3]`` images (host or device) -> the batch ``model.transform`` would build from ``to_tensor`` of them (flipped
-    where ``flips[i]``) for the model's current ``min_size`` / ``max_size`` / ``size_divisible`` and stem form, in one launch."""
+    where ``flips[i]``) for the model's current ``min_size`` / ``max_size`` / ``size_divisible`` and stem form, in one launch.
+    ``noise`` = ``(sigmas, seeds)``: the images are first given the noise ``ops.noise_u8_batch`` gives them, one launch more."""
     tr = model.transform
     if det.adt(tr) != torch.float32:
         raise NotImplementedError("prepare_batch writes fp32 batches only (training is fp32 only); with an fp16 compute dtype hand "
@@ -43,7 +72,7 @@ def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None) ->
     hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
     wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
     s2d = tr.prepared_s2d()
-    x = ops.preprocess_u8_batch(images, sizes, hp, wp, flips, s2d, device=device)
+    x = ops.preprocess_u8_batch(images, sizes, hp, wp, flips, s2d, device=device, noise=noise)
     return PreparedImages(x, sizes, orig, (hp, wp), tr.min_size, tr.max_size, d, s2d)
 
 
@@ -54,15 +83,18 @@ def prepare_batch(images: Sequence[torch.Tensor], targets: Sequence[dict], devic
     image inside the preprocess launch; its boxes are flipped already and stay in original-image pixels (the model rescales
     them).  ``"segmentation"`` + ``"size"`` become ``"masks"``: ``masks="resized"`` -- flipped, at the size the transform
     resizes the image to, which ``resize_masks_nearest`` passes through (training); ``masks="original"`` -- flipped at the
-    image's own size, through ``targets_to_device`` and a device flip (what ``evaluator_det`` reads).  Other tensors move to
-    ``device``; other values pass through."""
-    if masks not in ("resized", "original"):
-        raise ValueError('prepare_batch: masks must be "resized" or "original"')
+    image's own size, through ``targets_to_device`` and a device flip (what ``evaluator_det`` reads); ``masks="none"`` -- both keys
+    are dropped and nothing is rasterised (phase 2's loops and ``evaluator_df2`` read boxes only).  ``"noise_sigma"`` /
+    ``"noise_seed"`` (a lazy ``MultiDeepFashion2Dataset``) put the noise launch in front of the preprocess launch and are
+    dropped.  Other tensors move to ``device``; other values pass through."""
+    if masks not in ("resized", "original", "none"):
+        raise ValueError('prepare_batch: masks must be "resized", "original" or "none"')
     images, targets = list(images), list(targets)
     if len(images) != len(targets):
         raise ValueError("one target dict per image is needed")
     flips = [bool(t.get("hflip", False)) for t in targets]
-    prepared = prepare_images(images, device, model, flips)
+    prepared = prepare_images(images, device, model, flips, _noise_of(targets))
+    targets = [_without(t, _NOISE_KEYS) for t in targets]
     device = prepared.tensor.device
     for i, (t, o) in enumerate(zip(targets, prepared.orig)):
         if "segmentation" in t and "size" not in t:
@@ -77,7 +109,7 @@ def prepare_batch(images: Sequence[torch.Tensor], targets: Sequence[dict], devic
         return prepared, out
     out = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in t.items() if k not in _LAZY_KEYS} for t in targets]
     with_segm = [i for i, t in enumerate(targets) if "segmentation" in t]
-    if with_segm:
+    if with_segm and masks == "resized":
         stacks = mask_utils.masks_from_annotations_resized([targets[i]["segmentation"] for i in with_segm],
                                                            [prepared.orig[i] for i in with_segm],
                                                            [prepared.sizes[i] for i in with_segm], [flips[i] for i in with_segm], device)

@@ -918,9 +918,24 @@ def _staging(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
-def stage_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips, device):
+def _noise_tables(noise, n: int):
+    """``(sigmas, seeds)`` of a batch -> the 16 * n table bytes the noise launch reads: float64 [n] sigmas, then uint64 [n] seeds."""
+    import math
+    import numpy as np
+    sigmas, seeds = noise
+    sigmas, seeds = [float(v) for v in sigmas], [int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds]
+    if len(sigmas) != n or len(seeds) != n:
+        raise ValueError("noise: one sigma and one seed per image are needed")
+    if not all(math.isfinite(v) for v in sigmas):
+        raise ValueError("noise: every sigma must be finite")
+    return np.concatenate([np.asarray(sigmas, np.float64).view(np.uint8), np.asarray(seeds, np.uint64).view(np.uint8)])
+
+
+def stage_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips, device, noise=None):
     """The host side of ``preprocess_u8_batch`` for host images: the tables (int64 byte offsets, then int32 [N,5] dims) and the
-    images' bytes packed into the pinned staging buffer of ``device`` -> (the pinned uint8 view to copy, N)."""
+    images' bytes packed into the pinned staging buffer of ``device`` -> (the pinned uint8 view to copy, N).  ``noise`` =
+    ``(sigmas, seeds)``: the view is 16 * N bytes longer at its end -- behind the last image, from the next multiple of 8 on, lie
+    the float64 sigmas and the uint64 seeds of ``seam_noise_u8_batch``; everything before is what it is without ``noise``."""
     import numpy as np
     n = len(images_u8)
     dims = np.asarray([(int(i.shape[0]), int(i.shape[1]), int(s[0]), int(s[1]), int(f)) for i, s, f in zip(images_u8, sizes, flips)],
@@ -933,56 +948,122 @@ def stage_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp
     total = int(head + nbytes.sum())
     tables = np.concatenate([off.astype(np.int64).view(np.uint8), dims.reshape(-1).view(np.uint8)])
     if device is None:                                    # images that lie on the device already: the tables alone
+        if noise is not None:
+            raise ValueError("stage_u8_batch: the noise tables are staged with host images only")
         return torch.from_numpy(np.concatenate([tables, np.zeros(head - tables.size, np.uint8)])), n
-    stage = _staging(total, device)
+    tail = None if noise is None else _noise_tables(noise, n)
+    at = (total + 7) // 8 * 8
+    stage = _staging(total if tail is None else at + tail.size, device)
     stage[:tables.size].copy_(torch.from_numpy(tables))
     for i, o, b in zip(images_u8, off.tolist(), nbytes.tolist()):
         stage[o:o + b].copy_(i.reshape(-1))
-    return stage[:total], n
+    if tail is None:
+        return stage[:total], n
+    stage[total:at] = 0
+    stage[at:at + tail.size].copy_(torch.from_numpy(tail))
+    return stage[:at + tail.size], n
 
 
-def preprocess_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips: Optional[Sequence] = None,
-                        s2d: bool = False, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ToTensor + horizontal flip + normalise + resize + pad + layout for a batch of uint8 [H,W,3] images of different sizes in ONE
-    launch (``seam_preprocess_u8_batch_f32``): image i is resized to ``sizes[i]`` and flipped where ``flips[i]``; the result is
-    what ``preprocess([to_tensor(img).flip(-1) if flip else to_tensor(img) ...], sizes, hp, wp, s2d=s2d)`` gives, bit for bit.
-    The images are all host tensors -- packed with the tables into one pinned staging buffer, ONE host-to-device copy to
-    ``device`` (default: the current HIP device) -- or all on one HIP device (``device`` is theirs).  Without a HIP device:
-    SeamNativeError, as every preprocess branch."""
-    images_u8 = list(images_u8)
+def _u8_batch_to_device(what: str, images_u8, sizes, hp: int, wp: int, flips, s2d: bool, device, noise):
+    """The checks and the staging that ``preprocess_u8_batch`` and ``noise_u8_batch`` share -> (the flat device buffer: tables,
+    images [, noise tables], its int64 offsets, its int32 [N,5] dims, the device float64 sigmas and uint64 seeds or None)."""
     # device check FIRST: no CPU path exists, and nothing below may run without a HIP device to write to
     if not torch.cuda.is_available() or not all(isinstance(i, torch.Tensor) for i in images_u8):
-        raise _native.SeamNativeError("preprocess_u8_batch: expected uint8 tensors and a HIP device (no CPU path exists)")
+        raise _native.SeamNativeError(f"{what}: expected uint8 tensors and a HIP device (no CPU path exists)")
     on_dev = [i.is_cuda for i in images_u8]
     n = len(images_u8)
     if not 1 <= n <= 65535:
-        raise ValueError(f"preprocess_u8_batch: 1 <= N <= 65535 images per launch, got {n}")
+        raise ValueError(f"{what}: 1 <= N <= 65535 images per launch, got {n}")
     if any(on_dev) and not all(on_dev):
-        raise ValueError("preprocess_u8_batch: the images must be all on the host or all on one HIP device")
+        raise ValueError(f"{what}: the images must be all on the host or all on one HIP device")
     for i in images_u8:
         if i.dtype != torch.uint8:
             raise TypeError(f"image: expected torch.uint8, got {i.dtype}")
         if i.dim() != 3 or i.shape[2] != 3 or i.shape[0] < 1 or i.shape[1] < 1:
             raise ValueError("uint8 images must be [H,W,3]")
-    flips = [False] * n if flips is None else [bool(f) for f in flips]
     if len(sizes) != n or len(flips) != n:
-        raise ValueError("preprocess_u8_batch: one size and one flip per image are needed")
+        raise ValueError(f"{what}: one size and one flip per image are needed")
     if s2d and (int(hp) % 2 or int(wp) % 2):
-        raise ValueError("preprocess_u8_batch(s2d=True): an even padded size is needed")
+        raise ValueError(f"{what}(s2d=True): an even padded size is needed")
+    sig = seed = None
     if all(on_dev):
         device = images_u8[0].device
         if any(i.device != device for i in images_u8):
-            raise ValueError("preprocess_u8_batch: the images must lie on one device")
+            raise ValueError(f"{what}: the images must lie on one device")
         tables, _ = stage_u8_batch(images_u8, sizes, hp, wp, flips, None)
         dev = torch.cat([tables.to(device)] + [i.contiguous().reshape(-1) for i in images_u8])
+        if noise is not None:
+            tail = torch.from_numpy(_noise_tables(noise, n)).to(device)
+            sig, seed = tail[:8 * n].view(torch.float64), tail[8 * n:]
     else:
         device = _mask_device(device if device is not None else "cuda")
-        stage, _ = stage_u8_batch(images_u8, sizes, hp, wp, flips, device)
+        stage, _ = stage_u8_batch(images_u8, sizes, hp, wp, flips, device, noise)
         dev = stage.to(device, non_blocking=True)                            # the batch's one host-to-device copy
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(device))
         _STAGING[_staging_key(device)] = (_STAGING[_staging_key(device)][0], ev)
-    return preprocess_u8_flat(dev, dev[:8 * n].view(torch.int64), dev[8 * n:28 * n].view(torch.int32).view(n, 5), hp, wp, s2d, out)
+        if noise is not None:
+            at = dev.numel() - 16 * n
+            sig, seed = dev[at:at + 8 * n].view(torch.float64), dev[at + 8 * n:]
+    return dev, dev[:8 * n].view(torch.int64), dev[8 * n:28 * n].view(torch.int32).view(n, 5), sig, seed
+
+
+def _launch_noise(dev, img_off, img_dims, sig, seed, draws=None, draws_off=None) -> None:
+    with torch.cuda.device(dev.device):
+        _native.check(_native.lib().seam_noise_u8_batch(_ptr(dev), dev.numel(), _ptr(img_off), _ptr(img_dims), _ptr(sig), _ptr(seed),
+                                                        _ptr(draws), _ptr(draws_off), img_off.numel(), _stream()),
+                      "seam_noise_u8_batch")
+
+
+def preprocess_u8_batch(images_u8: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, wp: int, flips: Optional[Sequence] = None,
+                        s2d: bool = False, device=None, out: Optional[torch.Tensor] = None, noise=None) -> torch.Tensor:
+    """ToTensor + horizontal flip + normalise + resize + pad + layout for a batch of uint8 [H,W,3] images of different sizes in ONE
+    launch (``seam_preprocess_u8_batch_f32``): image i is resized to ``sizes[i]`` and flipped where ``flips[i]``; the result is
+    what ``preprocess([to_tensor(img).flip(-1) if flip else to_tensor(img) ...], sizes, hp, wp, s2d=s2d)`` gives, bit for bit.
+    The images are all host tensors -- packed with the tables into one pinned staging buffer, ONE host-to-device copy to
+    ``device`` (default: the current HIP device) -- or all on one HIP device (``device`` is theirs).  ``noise`` =
+    ``(sigmas, seeds)``, one each per image: ``seam_noise_u8_batch`` runs on the staged device buffer first, on the same stream
+    (its tables travel in the same copy), so that the images preprocessed are the ones ``noise_u8_batch`` returns for these
+    sigmas and seeds; the noise is keyed by the unflipped element index and the flip happens here, as the reference's dataset
+    adds noise before its transform flips.  Without a HIP device: SeamNativeError, as every preprocess branch."""
+    images_u8 = list(images_u8)
+    flips = [False] * len(images_u8) if flips is None else [bool(f) for f in flips]
+    dev, img_off, img_dims, sig, seed = _u8_batch_to_device("preprocess_u8_batch", images_u8, sizes, hp, wp, flips, s2d, device, noise)
+    if noise is not None:
+        _launch_noise(dev, img_off, img_dims, sig, seed)
+    return preprocess_u8_flat(dev, img_off, img_dims, hp, wp, s2d, out)
+
+
+def noise_u8_batch(images: Sequence[torch.Tensor], sigmas: Sequence[float], seeds: Sequence[int],
+                   noise_values: Optional[Sequence[torch.Tensor]] = None, device=None) -> list:
+    """The noise of the reference's ``MultiDeepFashion2Dataset.__getitem__`` for a batch of uint8 [H,W,3] RGB images of different
+    sizes in ONE launch (``seam_noise_u8_batch``): image i becomes ``uint8(clip((img / 255.0 + n * sigmas[i]) * 255.0, 0, 255))`` in
+    float64 with ``n`` = ``noise_values[i]`` (float64 [H,W,3] draws, e.g. ``np.random.randn``: the NumPy arithmetic bit for bit)
+    or, without ``noise_values``, the counter-based draws of ``frame_noise`` for ``seeds[i]``; sigma 0 leaves an image as it is.
+    Returns uint8 [H,W,3] device tensors, views of one buffer; the caller's tensors are never written.  The images are all host
+    tensors (one pinned copy through the staging buffer) or all on one HIP device."""
+    images = list(images)
+    shapes = [tuple(i.shape) if isinstance(i, torch.Tensor) else None for i in images]
+    if noise_values is not None:
+        noise_values = list(noise_values)
+        if len(noise_values) != len(images) or not all(isinstance(v, torch.Tensor) and v.dtype == torch.float64
+                                                       and tuple(v.shape) == z for v, z in zip(noise_values, shapes)):
+            raise ValueError("noise_u8_batch: noise_values must be one float64 tensor of the image's shape per image")
+    own = [z[:2] if z is not None and len(z) == 3 else (1, 1) for z in shapes]     # a wrong image is refused below
+    hp, wp = max((z[0] for z in own), default=1), max((z[1] for z in own), default=1)
+    dev, img_off, img_dims, sig, seed = _u8_batch_to_device("noise_u8_batch", images, own, hp, wp, [False] * len(images), False,
+                                                            device, (sigmas, seeds))
+    draws = draws_off = None
+    if noise_values is not None:
+        draws = torch.cat([v.to(dev.device).reshape(-1) for v in noise_values])
+        counts = [v.numel() for v in noise_values]
+        draws_off = torch.tensor([sum(counts[:k]) for k in range(len(counts))], dtype=torch.int64).to(dev.device)
+    _launch_noise(dev, img_off, img_dims, sig, seed, draws, draws_off)
+    head, out = 32 * ((28 * len(images) + 31) // 32), []
+    for h, w in own:
+        out.append(dev[head:head + h * w * 3].view(h, w, 3))
+        head += h * w * 3
+    return out
 
 
 def maxpool2d(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:
