@@ -168,6 +168,19 @@ int seam_pack_conv1x1_weight_sxpc(const float* w, void* w_packed, int K, int C, 
 int seam_conv1x1_sxpc(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
                       long long M, int C, int K, int relu, seam_stream_t stream);
 
+/* conv1x1_sxpc_dual (csrc/seam_pwsx.hip): the same kernel with a reduction over TWO sources -- torchvision's Bottleneck with a
+ * projection shortcut, bn3(conv3(h)) + bn_d(conv_d(x)) + ReLU, as one GEMM over [x1 | x2 sampled at stride2] (the operands of
+ * seam_conv2d_dual_f32).  x1 [N, Ho, Wo, C1], x2 [N, H2, W2, C2] read at (n, stride2 ho, stride2 wo); w_packed is
+ * seam_pack_conv1x1_weight_sxpc of the [K, C1 + C2] matrix.  The result is bit for bit seam_conv1x1_sxpc on the materialised
+ * concatenation; no residual.
+ *   _supported: 1 when C1, C2 are multiples of 64 and (M, C1 + C2, K) is a shape of seam_conv1x1_sxpc_supported, else 0;
+ *   seam_conv1x1_sxpc_dual: also needs stride2 >= 1, (Ho - 1) stride2 < H2, (Wo - 1) stride2 < W2, relu 0 | 1, and the images of
+ *   x2 that one tile of 128 output pixels touches within 2 GiB (x2 itself may be any size); otherwise it returns
+ *   hipErrorInvalidValue and launches nothing. */
+int seam_conv1x1_sxpc_dual_supported(long long M, int C1, int C2, int K);
+int seam_conv1x1_sxpc_dual(const float* x1, const float* x2, const void* w_packed, const float* scale, const float* shift, float* y,
+                           int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int K, int relu, seam_stream_t stream);
+
 /* fp16 twin of seam_conv1x1_sw_f32 (csrc/seam_pwh.hip, round 6): the config-5 path's 1x1 layers [TV Bottleneck conv1 / conv3 /
  * stride-1 projection shortcut, FeaturePyramidNetwork.inner_blocks; behind models/video_matchrcnn.py:337] as a STREAMING kernel --
  * weights stationary in LDS, independent waves, 16-byte NHWC pieces in and out -- with the contract of seam_conv2d_f16 /

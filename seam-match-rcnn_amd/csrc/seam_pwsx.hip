@@ -29,6 +29,13 @@
 // within a k-step the six piece products of an accumulator tile in its order (activation piece, weight piece) = (2,0) (1,1) (0,2)
 // (1,0) (0,1) (0,0), every accumulator tile starts from zero; the products are exact, so which operand is the MFMA's A is immaterial.
 //
+// The two-source form conv1x1_sxpc_dual (sxpc_body<true>) runs the projection-shortcut blocks, bn3(conv3(h)) + bn_d(conv_d(x)), as one
+// reduction over [x1 | x2 sampled at stride2]: only the producers differ.  A tile's first C1 / 64 chunks are its rows of x1 as above;
+// the others are the pixels (n, stride2 ho, stride2 wo) of x2 through a second descriptor, rebased per tile at the first image the
+// tile touches, and eight per-lane offsets recomputed once per tile; per chunk a scalar branch picks the source, the same eight loads
+// on either side.  Weights, consumers and epilogue are the plain kernel's on the [K, C1 + C2] matrix; the bits are those of the plain
+// kernel on the concatenated rows.
+//
 // LDS map (139264 bytes, one block per CU):
 //   [0, 102400)        two chunk buffers of 128 pixel rows x 400 bytes: plane 0 | plane 1 | plane 2 (64 bf16 = 128 bytes each) | 16
 //                      bytes of padding -- 25 slots of 16 bytes, odd, so the 16 lanes of a ds_read_b128 cycle (16 consecutive
@@ -37,6 +44,7 @@
 #include <hip/hip_runtime.h>
 #include "seam_device.h"
 #include <stdint.h>
+#include <algorithm>
 #include <type_traits>
 #include "seam_fastdiv.h"
 #include "seam_launch.h"
@@ -78,7 +86,22 @@ struct SxpcArgs {
     unsigned m_tiles_n;
 };
 
-__global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
+// The second source of the dual form (conv1x1_sxpc_dual): chunks [0, n1) of a tile are its 128 consecutive rows of x = x1 [M, C1],
+// chunks [n1, nchunks) the pixels (n, stride2 ho, stride2 wo) of x2 [N, H2, W2, C2]; SxpcArgs::C = C1 + C2 (the consumers' reduction).
+struct SxpcDual {
+    const float* x2;
+    unsigned long long img2_bytes;      // H2 * W2 * C2 * 4
+    int N, C1, n1;
+    unsigned HoWo, Wo;
+    // row rl of the first image's output grid (rl < BM + HoWo) -> image rl / HoWo = umulhi(rl, m_howo) + rl * one_howo + (rl >= thr):
+    // HoWo = 1: (0, 1, never); 2 <= HoWo < BM: (magic, 0, never); HoWo >= BM (at most two images): (0, 0, HoWo).  No branch, any map.
+    unsigned m_howo, one_howo, thr;
+    unsigned m_wo, one_wo;              // the remainder by Wo: umulhi(rem, m_wo) + rem * one_wo
+    unsigned img_step, row_step, px_step;      // byte steps of x2 per image / per output row (stride2 W2 C2 4) / per output pixel (stride2 C2 4)
+};
+
+template <bool DUAL>
+__device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -91,7 +114,8 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
     const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
     const int tile0 = xt.tile0();
-    const size_t row_bytes = (size_t)p.C * 4, out_row = (size_t)p.K * 4;
+    const int c1 = DUAL ? d.C1 : p.C;     // channels of a row of x
+    const size_t row_bytes = (size_t)c1 * 4, out_row = (size_t)p.K * 4;
     const int total_chunks = ntiles * n;
 
     if (!consumer) {
@@ -102,7 +126,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
 #pragma unroll
         for (int r = 0; r < NP; ++r) {
             const int row = (ptid >> 4) + 16 * r;
-            goff[r] = (unsigned)(row * p.C * 4 + (ptid & 15) * 16);
+            goff[r] = (unsigned)(row * c1 * 4 + (ptid & 15) * 16);
             lp[r] = (LDSQ char*)smem + row * ROWB + (ptid & 15) * 8;
         }
         f32x4 rq[2][NP];                        // two chunks in registers (chunk parity)
@@ -117,15 +141,46 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
                                                      (int)(rows * row_bytes), 0x00020000);
         };
         __amdgpu_buffer_rsrc_t rs = x_desc(tile);
-        auto request = [&](f32x4 (&dst)[NP]) {
+        // DUAL: the second source of tile tl -- its descriptor, rebased at the first image the tile touches (32-bit lane offsets for
+        // any x2; the plan has checked that the images of one tile fit the descriptor), and this thread's eight pixel offsets: once
+        // per tile, nothing per chunk.  Rows past M get kOob; past the block's last tile the descriptor is empty.
+        unsigned goff2[DUAL ? NP : 1];
+        __amdgpu_buffer_rsrc_t rs2;
+        auto x2_tile = [&](const int tl) {
+            const bool live = tiles_left > 0;
+            const unsigned row0 = live ? (unsigned)fdivu(tl, p.tiles_n, p.m_tiles_n) * BM : 0u;
+            const unsigned n_first = __builtin_amdgcn_readfirstlane(row0 / d.HoWo);       // (a true division: once per tile, any M)
+            const unsigned long long left = (unsigned long long)((unsigned)d.N - n_first) * d.img2_bytes;
+            rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)d.x2 + (size_t)n_first * d.img2_bytes), 0,
+                                                    live ? (int)(left > kOob ? kOob : (unsigned)left) : 0, 0x00020000);
+            const unsigned rl0 = row0 - n_first * d.HoWo + (unsigned)(ptid >> 4);      // row inside that image's output grid
 #pragma unroll
-            for (int r = 0; r < NP; ++r)
-                dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (SEAM_SXPC_ABL & 1) ? kOob : goff[r], ck * (CK * 4), 0));
+            for (int r = 0; r < NP; ++r) {
+                const unsigned rl = rl0 + 16 * r;       // < BM + HoWo
+                const unsigned nl = __umulhi(rl, d.m_howo) + rl * d.one_howo + (rl >= d.thr ? 1u : 0u);
+                const unsigned rem = rl - nl * d.HoWo;
+                const unsigned ho = __umulhi(rem, d.m_wo) + rem * d.one_wo, wo = rem - ho * d.Wo;
+                const unsigned off = nl * d.img_step + ho * d.row_step + wo * d.px_step + (unsigned)((ptid & 15) * 16);
+                goff2[r] = row0 + (unsigned)(ptid >> 4) + 16 * r < (unsigned)p.M ? off : kOob;
+            }
+        };
+        if (DUAL) x2_tile(tile);
+        auto request = [&](f32x4 (&dst)[NP]) {
+            if (!DUAL || ck < d.n1) {
+#pragma unroll
+                for (int r = 0; r < NP; ++r)
+                    dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (SEAM_SXPC_ABL & 1) ? kOob : goff[r], ck * (CK * 4), 0));
+            } else {                            // (a scalar branch: the same eight loads on either side)
+#pragma unroll
+                for (int r = 0; r < NP; ++r)
+                    dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs2, (SEAM_SXPC_ABL & 1) ? kOob : goff2[r], (ck - d.n1) * (CK * 4), 0));
+            }
             if (++ck == n) {                    // the next request belongs to the next tile
                 ck = 0;
                 tile += S;
                 --tiles_left;
                 rs = x_desc(tile);
+                if (DUAL) x2_tile(tile);
             }
         };
         auto store_chunk = [&](const f32x4 (&src)[NP], const int buf) {
@@ -335,6 +390,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) {
     }
 }
 
+__global__ __launch_bounds__(512, 2) void conv1x1_sxpc(const SxpcArgs p) { sxpc_body<false>(p, SxpcDual{}); }
+__global__ __launch_bounds__(512, 2) void conv1x1_sxpc_dual(const SxpcArgs p, const SxpcDual d) { sxpc_body<true>(p, d); }
+
 // [K, C] fp32 (row-major) -> three bf16 planes in fragment order [K/128][4][C/16][3][64][8]
 __global__ void sxpc_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int K, int C) {
     const size_t total = (size_t)K * C / 8;
@@ -354,6 +412,38 @@ int sxpc_plan(SxpcArgs& a, long long M, int C, int K) {
     // (the producers and the ring preload run one grid stride past the block's last tile: numerators below 2 * total + 2^16)
     if (!seam_fastdiv::exact(a.tiles_n, 2ull * total + (1ull << 16))) return 1;
     a.m_tiles_n = seam_fastdiv::magic(a.tiles_n);
+    return 0;
+}
+
+// the dual form: the plain plan of (M, C1 + C2, K) and the second source's geometry
+int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long long Wo, int C1, long long H2, long long W2, int C2, int stride2, int K) {
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || H2 <= 0 || W2 <= 0 || C1 < CK || C2 < CK || (C1 % CK) || (C2 % CK) || stride2 < 1) return 1;
+    if (N >= (1LL << 31) || Ho >= (1LL << 31) || Wo >= (1LL << 31) || H2 >= (1LL << 31) || W2 >= (1LL << 31)) return 1;
+    if ((Ho - 1) * stride2 >= H2 || (Wo - 1) * stride2 >= W2) return 1;
+    if (Ho * Wo >= (1LL << 31) || N * (Ho * Wo) >= (1LL << 31)) return 1;
+    if (sxpc_plan(a, N * Ho * Wo, C1 + C2, K)) return 1;
+    const long long HoWo = Ho * Wo;
+    if ((unsigned long long)H2 * W2 >= (1ull << 31) / ((unsigned long long)C2 * 4)) return 1;      // one image of x2 inside a descriptor
+    const unsigned long long img2 = (unsigned long long)H2 * W2 * C2 * 4;
+    // a tile's 128 rows touch at most this many images; their pixels are addressed from the first one's start with 32-bit offsets
+    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
+    if (imgs * img2 > kOob) return 1;
+    // divisions of the producers: a row of the tile's image span by HoWo (by multiply-high for 2 <= HoWo < BM only: numerators
+    // below BM + HoWo), its remainder by Wo
+    const bool mid = HoWo >= 2 && HoWo < BM;
+    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
+    if (!seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)HoWo)) return 1;
+    d.img2_bytes = img2;
+    d.N = (int)N; d.C1 = C1; d.n1 = C1 / CK; d.HoWo = (unsigned)HoWo; d.Wo = (unsigned)Wo;
+    d.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
+    d.one_howo = HoWo == 1 ? 1u : 0u;
+    d.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
+    d.m_wo = seam_fastdiv::magic((unsigned long long)Wo);       // (0 for Wo = 1)
+    d.one_wo = Wo == 1 ? 1u : 0u;
+    // (a step that exceeds 32 bits multiplies an index that is always 0: Ho = 1 / Wo = 1 with a large stride)
+    d.img_step = (unsigned)img2;
+    d.row_step = (unsigned)((unsigned long long)stride2 * W2 * C2 * 4);
+    d.px_step = (unsigned)((unsigned long long)stride2 * C2 * 4);
     return 0;
 }
 
@@ -391,6 +481,31 @@ int seam_conv1x1_sxpc(const float* x, const void* w_packed, const float* scale, 
     if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
     hipLaunchKernelGGL(conv1x1_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+/* 1 when the channel counts and M of a two-source layer suit seam_conv1x1_sxpc_dual (C1, C2 multiples of 64; the plain rule for
+ * (M, C1 + C2, K)), else 0; the launch checks the geometry as well */
+int seam_conv1x1_sxpc_dual_supported(long long M, int C1, int C2, int K) {
+    SxpcArgs a;
+    if (C1 < CK || C2 < CK || (C1 % CK) || (C2 % CK) || (long long)C1 + C2 >= (1LL << 30)) return 0;
+    return sxpc_plan(a, M, C1 + C2, K) == 0 ? 1 : 0;
+}
+
+/* y[N, Ho, Wo, K] = act(scale * ([x1 | x2 at (stride2 ho, stride2 wo)] . w^T) + shift): the bits of seam_conv1x1_sxpc on the
+ * concatenated rows, which are never written; w_packed: seam_pack_conv1x1_weight_sxpc of [K, C1 + C2]; relu 0 | 1 */
+int seam_conv1x1_sxpc_dual(const float* x1, const float* x2, const void* w_packed, const float* scale, const float* shift, float* y,
+                           int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int K, int relu, void* stream) {
+    SxpcArgs a;
+    SxpcDual d;
+    if ((relu != 0 && relu != 1) || !x2 || sxpc_dual_plan(a, d, N, Ho, Wo, C1, H2, W2, C2, stride2, K)) return (int)hipErrorInvalidValue;
+    a.x = x1; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    d.x2 = x2;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_dual>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc_dual, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
     return (int)hipGetLastError();
 }
 

@@ -57,13 +57,15 @@ def adt(module) -> torch.dtype:
 # product, where the exact kernels are one rounding of each partial sum away.  The module attribute ``split_f32`` (set for a whole
 # model with ``set_split_f32``; SEAM_SPLIT_F32=0 for the process) switches it off and restores the exact-fp32 kernels bit for bit.
 # Classes: c1 = bottleneck 1x1 reductions, c3 = 1x1 expansions with their residual (C >= SPLIT_C3_MIN_C), c2s2 = the three
-# stride-2 3x3s.  The two-source shortcut GEMMs and the FPN laterals keep their fused fp32 kernels (the split kernel has neither form).
-# The long 1x1 layers of c1 / c3 (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel conv1x1_sxpc (ops.SXPC;
-# the same bits as conv_igemm_sx), the others on conv_igemm_sx.
+# stride-2 3x3s, c3ds = the two-source shortcut GEMMs of layer2.0 / layer3.0 / layer4.0 (C1 + C2 >= SPLIT_C3DS_MIN_C: layer1.0, 64 + 64 on
+# one map, stays on conv1x1_sw).  The FPN laterals keep their fused fp32 kernels (the split kernel has no upsampled residual).
+# The long 1x1 layers of c1 / c3 (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel conv1x1_sxpc, c3ds on
+# its two-source form conv1x1_sxpc_dual (ops.SXPC; the same bits as conv_igemm_sx on the concatenated rows), the others on conv_igemm_sx.
 SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
 SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
 SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; the short reductions of layer1 / layer2 (C = 64, 128) are faster on conv1x1_sw
-SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2").split(",") if c)
+SPLIT_C3DS_MIN_C = 384    # C1 + C2 of the served shortcut GEMMs: a rule on the layer's geometry alone, never on the batch
+SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds").split(",") if c)
 
 
 def split_on(module) -> bool:
@@ -266,8 +268,14 @@ class ResNet50Body(nn.Module):
                             e["ds"] = ops.pack_conv(b.downsample[0].weight, None, b.downsample[1].tensors(),
                                                     stride=b.stride, bn_eps=b.downsample[1].eps, dtype=dt)
                             if dt in (torch.float32, torch.float16) and FUSE_SHORTCUT:     # conv3 + projection shortcut as one GEMM
-                                e["c3ds"] = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight,
-                                                               b.downsample[1].tensors(), bn_eps=b.bn3.eps, dtype=dt)
+                                # (its split twin is packed beside it from the SAME folded matrix: one derived source for PackPlan)
+                                twin = (sx and "c3ds" in SPLIT_CLASSES and SPLIT_DTYPE == ops.SX6
+                                        and b.conv3.in_channels + b.downsample[0].in_channels >= SPLIT_C3DS_MIN_C)
+                                packs = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight, b.downsample[1].tensors(),
+                                                           bn_eps=b.bn3.eps, dtype=(dt, ops.SX6) if twin else (dt,))
+                                e["c3ds"] = packs[0]
+                                if twin:
+                                    e["c3dsx"] = packs[1]
                         if sx:      # split twins of the exact packs (the exact ones stay: the switch and the grad-enabled walk use them)
                             if "c1" in SPLIT_CLASSES:
                                 e["c1x"] = ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=SPLIT_DTYPE)
@@ -341,7 +349,7 @@ class ResNet50Body(nn.Module):
                 o = ops.conv2d(x, e.get("c1x", e["c1"]) if sx else e["c1"], relu=True)
                 o = ops.conv2d(o, e.get("c2x", e["c2"]) if sx else e["c2"], relu=True)
                 if "c3ds" in e:       # projection-shortcut block: bn3(conv3(o)) + bn_d(conv_d(x)) + ReLU in one launch
-                    x = ops.conv2d_dual(o, x, e["c3ds"], getattr(self, f"layer{li}")[bi].stride, relu=True)
+                    x = ops.conv2d_dual(o, x, e.get("c3dsx", e["c3ds"]) if sx else e["c3ds"], getattr(self, f"layer{li}")[bi].stride, relu=True)
                     continue
                 idt = ops.conv2d(x, e["ds"]) if "ds" in e else x
                 x = ops.conv2d(o, e.get("c3x", e["c3"]) if sx else e["c3"], relu=True, residual=idt,   # bn3 + add + ReLU fused

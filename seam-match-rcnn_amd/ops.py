@@ -99,7 +99,8 @@ PWHPC_MIN_C = int(_os.environ.get("SEAM_PWHPC_MIN_C", "1024"))  # reductions fro
 # them on conv_igemm_sx.  The two kernels give the same bits, so the choice may depend on the batch: launches of at least
 # SXPC_MIN_TILES tiles of 128 pixels x 128 channels take it -- every shape of a step does (1.05-1.26x); with fewer tiles than CUs the
 # persistent blocks' long tiles lose to the implicit GEMM's smaller ones (196 tiles: 1.16x, 100 tiles: 0.87x, 40 tiles: 0.66x;
-# profiles/sxpc_layer_ab.txt).  SXPC_RULE = False: every supported shape (tests, tools/sxpc_ab.py).
+# profiles/sxpc_layer_ab.txt).  SXPC_RULE = False: every supported shape (tests, tools/sxpc_ab.py).  The two-source form
+# (conv1x1_sxpc_dual, ``conv2d_dual`` on an SX6 pack) has no tile rule: it wins from one image on (profiles/sxpc_dual_layer_ab.txt).
 SXPC = _os.environ.get("SEAM_SXPC", "1") != "0"
 SXPC_MIN_TILES = int(_os.environ.get("SEAM_SXPC_MIN_TILES", "196"))
 SXPC_RULE = True
@@ -717,34 +718,61 @@ def conv2d_topdown(x: torch.Tensor, pc: PackedConv, top: torch.Tensor) -> torch.
 def pack_conv_dual(w1: torch.Tensor, bn1, w2: torch.Tensor, bn2, bn_eps: float = 1e-5, dtype=F32) -> PackedConv:
     """Weights of ``conv2d_dual``: two 1x1 convs, each followed by its own (Frozen)BatchNorm, summed.
     The scales are folded into the weights (one fp32 rounding per weight) and the shifts added:
-    bn_a(W_a . h) + bn_b(W_b . x) = [s_a W_a | s_b W_b] . [h ; x] + (t_a + t_b)."""
+    bn_a(W_a . h) + bn_b(W_b . x) = [s_a W_a | s_b W_b] . [h ; x] + (t_a + t_b).
+    ``dtype``: fp32 / fp16 / SX6 (an eligible layer then has ``wx``, the form of ``seam_conv1x1_sxpc_dual``, beside ``w``); a tuple of
+    them yields a tuple of packs of ONE folded matrix and shift (one ``derived_source`` each, whatever the number of packs)."""
     def fold(w, bn):
         bw, bb, rm, rv = (t.detach().to(F32) for t in bn)
         sc = bw * torch.rsqrt(rv + bn_eps)
         return w.detach().to(F32).reshape(w.shape[0], -1) * sc[:, None], bb - rm * sc
     w = derived_source(lambda: torch.cat([fold(w1, bn1)[0], fold(w2, bn2)[0]], 1).contiguous(), (w1, w2))
     shift = derived_source(lambda: (fold(w1, bn1)[1] + fold(w2, bn2)[1]).contiguous(), ())      # the two BN shifts: no parameter in it
+    if isinstance(dtype, tuple):
+        return tuple(pack_conv(w[:, :, None, None], shift, wino=False, dtype=d) for d in dtype)
     return pack_conv(w[:, :, None, None], shift, wino=False, dtype=dtype)
 
 
+def _sxpc_dual_map_ok(n, ho, wo, h2, w2, c2) -> bool:
+    """The geometry rule of ``seam_conv1x1_sxpc_dual`` (csrc/seam_pwsx.hip sxpc_dual_plan; integers only): the images of x2 one tile
+    of 128 output pixels touches lie within 2 GiB, and the producers' division by Wo is exact for every pixel of a map."""
+    return 4 * h2 * w2 * c2 * min(n, 126 // (ho * wo) + 2) <= 1 << 31 and ho * wo * wo < 1 << 32
+
+
 def conv2d_dual(x1: torch.Tensor, x2: torch.Tensor, pc: PackedConv, stride2: int = 1, relu: bool = False) -> torch.Tensor:
-    """y = act(W[:, :C1] . x1 + W[:, C1:] . x2[:, ::stride2, ::stride2] + shift) in ONE launch (``seam_conv2d_dual_f32`` / ``_f16``):
+    """y = act(W[:, :C1] . x1 + W[:, C1:] . x2[:, ::stride2, ::stride2] + shift) in ONE launch (``seam_conv2d_dual_f32`` / ``_f16``;
+    an SX6 pack: ``seam_conv1x1_sxpc_dual``, six-term split-bf16 products):
     the residual block with a projection shortcut [TV Bottleneck.forward] without writing the shortcut branch to memory.
-    x1 NHWC [N,Ho,Wo,C1], x2 NHWC [N,H2,W2,C2] -> NHWC [N,Ho,Wo,K]; exact fp32 or fp16 operands (the packed weights' precision)."""
+    x1 NHWC [N,Ho,Wo,C1], x2 NHWC [N,H2,W2,C2] -> NHWC [N,Ho,Wo,K]; the operands' precision is the packed weights'."""
     x1 = _req(x1, None, "x1")
-    if pc.dtype not in (F32, F16) or pc.R != 1 or pc.S != 1:
-        raise ValueError("conv2d_dual: needs fp32 / fp16 1x1 weights from pack_conv_dual")
-    dt = pc.dtype
+    if pc.dtype not in (F32, F16, SX6) or pc.R != 1 or pc.S != 1:
+        raise ValueError("conv2d_dual: needs fp32 / fp16 / split-bf16 (SX6) 1x1 weights from pack_conv_dual")
+    dt = F32 if pc.dtype == SX6 else pc.dtype
     x1, x2 = _req(x1, dt, "x1"), _req(x2, dt, "x2")
     n, ho, wo, c1 = x1.shape
     n2, h2, w2, c2 = x2.shape
     cm = 32 if dt == F32 else 64
     if n2 != n or c1 + c2 != pc.Cstore or c1 % cm or c2 % cm:
         raise ValueError(f"conv2d_dual: channel / batch mismatch (C1, C2 must be multiples of {cm} and sum to the packed width)")
-    if (ho - 1) * stride2 >= h2 or (wo - 1) * stride2 >= w2:
+    if stride2 < 1 or (ho - 1) * stride2 >= h2 or (wo - 1) * stride2 >= w2:
         raise ValueError("conv2d_dual: x2 too small for the output grid")
-    y = torch.empty((n, ho, wo, pc.K), dtype=dt, device=x1.device)
     lib = _native.lib()
+    if pc.dtype == SX6:
+        # six-term split-bf16 products (csrc/seam_pwsx.hip conv1x1_sxpc_dual).  Without the kernel (ops.SXPC off, no ``wx``, a shape
+        # or a map it does not take) the sampled shortcut input is gathered, concatenated and multiplied by ``conv2d`` on the same
+        # pack: conv_igemm_sx / conv1x1_sxpc on the materialised rows -- the same bits, one more pass over memory.
+        if (SXPC and pc.wx is not None and relu in (0, 1, False, True) and lib.seam_conv1x1_sxpc_dual_supported(n * ho * wo, c1, c2, pc.K) == 1
+                and _sxpc_dual_map_ok(n, ho, wo, h2, w2, c2)):
+            y = torch.empty((n, ho, wo, pc.K), dtype=F32, device=x1.device)
+            tr = CONV_TRACE is not None and _trace_begin(
+                "conv1x1_sxpc_dual", 2.0 * n * ho * wo * pc.K * (c1 + c2), (n, ho, wo, c1 + c2, pc.K, 1, 1),
+                float(x1.element_size() * (x1.numel() + n * ho * wo * c2 + pc.K * (c1 + c2) + y.numel())))
+            _native.check(lib.seam_conv1x1_sxpc_dual(_ptr(x1), _ptr(x2), _ptr(pc.wx), _ptr(pc.scale), _ptr(pc.shift), _ptr(y), n, ho, wo, c1,
+                                                     h2, w2, c2, stride2, pc.K, 1 if relu else 0, _stream()), "seam_conv1x1_sxpc_dual")
+            if tr:
+                _trace_end(tr)
+            return y
+        return conv2d(torch.cat([x1, x2[:, :(ho - 1) * stride2 + 1:stride2, :(wo - 1) * stride2 + 1:stride2]], -1), pc, relu=relu)
+    y = torch.empty((n, ho, wo, pc.K), dtype=dt, device=x1.device)
     same = stride2 == 1 and (h2, w2) == (ho, wo)      # the pointwise kernels read both inputs on the output grid
     sw = dt == F32 and same and _sw_ok(pc, ho, wo)
     swh = dt == F16 and same and _swh_ok(pc, ho, wo) and lib.seam_conv1x1_swh_config(n * ho * wo, c1, c2, pc.K) != 0
