@@ -750,6 +750,24 @@ int seam_frame_noise_u8(const uint8_t* bgr, const double* noise, uint8_t* rgb, i
 int seam_noise_u8_batch(uint8_t* buf, int64_t buf_bytes, const int64_t* img_off, const int* img_dims, const double* sigma,
                         const uint64_t* seed, const double* draws, const int64_t* draws_off, int n_images,
                         seam_stream_t stream);
+/* seam_frames_prepare_batch_u8: the per-frame work of MovingFashionDataset.__getitem__ (datasets/MFDataset.py:79-95) for a whole
+ *   batch of uint8 HWC images of different sizes, ONE launch.  Image i lies at byte in_off[i] of the flat DEVICE buffer `in`
+ *   (in_off int64 [n_images]; dims int32 [n_images,3] = (h, w, mode)) and its result is written at byte out_off[i] of `out`:
+ *     mode 0  the bytes as they are (the RGB shop image, the zero placeholder of an unreadable frame), h x w;
+ *     mode 1  BGR -> RGB (the dataset's noise=False branch), h x w;
+ *     mode 2  BGR -> RGB, the noise of seam_frame_noise_u8 (sigma[i]; n = draws[draws_off[i] + e], float64 draws at element
+ *             offsets, draws_len of them in all, or, draws NULL, the counter-based draw for (seed[i], e), e the element index
+ *             in the full-resolution RGB frame), then seam_resize_bicubic_u8 to (h / 2) x (w / 2), fused: no intermediate
+ *             image is written.  Bit-identical to seam_frame_noise_u8 + seam_resize_bicubic_u8 for h, w >= 2.
+ *   max_h / max_w: the largest h and w of the batch (the sizes themselves are on the device; they size the grid).  An image
+ *   whose input or output bytes do not lie inside in_bytes / out_bytes, whose draws do not lie inside draws_len, whose mode is
+ *   not 0..2, that exceeds max_h / max_w or (mode 2) has h or w < 2 is skipped: nothing of it is read or written.  `in` and
+ *   `out` must not overlap, nor the outputs of two images.  The output buffer is in the layout seam_preprocess_u8_batch_f32
+ *   reads, with out_off as its img_off. */
+int seam_frames_prepare_batch_u8(const uint8_t* in, int64_t in_bytes, const int64_t* in_off, const int* dims,
+                                 const double* sigma, const uint64_t* seed, const double* draws, const int64_t* draws_off,
+                                 int64_t draws_len, uint8_t* out, int64_t out_bytes, const int64_t* out_off, int n_images,
+                                 int max_h, int max_w, seam_stream_t stream);
 int64_t seam_resize_workspace_bytes(int H, int W, int OH, int OW);
 int seam_resize_bicubic_u8(const uint8_t* in, uint8_t* out, int H, int W, int OH, int OW, void* ws,
                            seam_stream_t stream);

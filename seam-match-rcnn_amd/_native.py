@@ -195,6 +195,7 @@ SIGNATURES = {
     "seam_bn1d_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "seam_frame_noise_u8": (_i, [_p, _p, _p, _i, _i, C.c_double, C.c_uint64, _p]),
     "seam_noise_u8_batch": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "seam_frames_prepare_batch_u8": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _i, _i, _i, _p]),
     "seam_resize_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "seam_resize_bicubic_u8": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "seam_ce2_fwd_bwd_f32": (_i, [_p, _p, _p, _p, _p, _i64, _p]),

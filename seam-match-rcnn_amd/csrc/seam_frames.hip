@@ -86,10 +86,12 @@ __device__ __forceinline__ double bicubic_filter(double x) {
     return 0.0;
 }
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for one axis: bounds[xx] = (xmin, count), kk[xx][KMAX] fixed point.
-__global__ void resize_coeff_kernel(int inSize, int outSize, int* __restrict__ bounds, int* __restrict__ kk) {
-    const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (xx >= outSize) return;
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output sample xx of one axis: the first input sample, the number of taps
+// and kk[NT] fixed-point weights (zero from the tap count on).  NT >= the tap count: the weights do not depend on NT, since taps
+// past the count add nothing to the sum they are normalised by.  The one definition, for the per-frame table kernel below
+// (NT = KMAX) and for the fused batch kernel (NT = FK).
+template <int NT>
+__device__ __forceinline__ void resize_coeffs(int inSize, int outSize, int xx, int& first, int& count, int* __restrict__ kk) {
     const float in0 = 0.f, in1 = (float)inSize;
     double scale = (double)(in1 - in0) / outSize;
     double filterscale = scale;
@@ -102,9 +104,9 @@ __global__ void resize_coeff_kernel(int inSize, int outSize, int* __restrict__ b
     int xmax = (int)(center + support + 0.5);
     if (xmax > inSize) xmax = inSize;
     xmax -= xmin;
-    double k[KMAX];
+    double k[NT];
     double ww = 0.0;
-    for (int x = 0; x < KMAX; ++x) {
+    for (int x = 0; x < NT; ++x) {
         double w = 0.0;
         if (x < xmax) {
             w = bicubic_filter((x + xmin - center + 0.5) * ss);
@@ -112,13 +114,20 @@ __global__ void resize_coeff_kernel(int inSize, int outSize, int* __restrict__ b
         }
         k[x] = w;
     }
-    for (int x = 0; x < KMAX; ++x) {
+    for (int x = 0; x < NT; ++x) {
         double v = k[x];
         if (x < xmax && ww != 0.0) v /= ww;
-        kk[(size_t)xx * KMAX + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
+        kk[x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
     }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
+    first = xmin;
+    count = xmax;
+}
+
+// one axis' tables for seam_resize_bicubic_u8: bounds[xx] = (xmin, count), kk[xx][KMAX]
+__global__ void resize_coeff_kernel(int inSize, int outSize, int* __restrict__ bounds, int* __restrict__ kk) {
+    const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (xx >= outSize) return;
+    resize_coeffs<KMAX>(inSize, outSize, xx, bounds[2 * xx], bounds[2 * xx + 1], kk + (size_t)xx * KMAX);
 }
 
 __device__ __forceinline__ uint8_t clip8(int v) {
@@ -146,6 +155,100 @@ __global__ void resize_pass_kernel(const uint8_t* __restrict__ in, uint8_t* __re
             for (int t = 0; t < cnt; ++t) ss += (int)col[(size_t)t * W * 3] * k[t];
         }
         out[i] = clip8(ss);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the fused batch kernel
+// The per-frame work of MovingFashionDataset.__getitem__ for N images of different sizes in one launch: grid (tiles, images).
+//   mode 0  bytes copied (the shop image, the zero placeholder)        mode 1  BGR -> RGB (noise=False)
+//   mode 2  BGR -> RGB, noise, Pillow's resize to (h / 2, w / 2): a block makes one FT x FT tile of the half-size image.
+// Halving has scale s = in / (in / 2) in [2, 3] and support 2 s, so an output sample has at most 4 s + 1 <= 13 taps (FK = 16) and
+// the n <= FT samples of a tile read at most (n + 3) s + 1 input samples: at most 2 FT + 1 when the whole axis is one tile
+// (n = in / 2), at most 67 (2 + 1 / 64) + 1 < 137 otherwise -- FWIN = 2 FT + 16 covers both.  The window is walked in chunks of
+// FCH rows: noisy RGB bytes of the chunk into LDS (every draw keyed by its element index in the full frame: a halo sample gets
+// the draw its owner gets, whatever the tiling), the horizontal pass from there into the window's half-width rows, also LDS, and
+// once all rows are there the vertical pass out to memory.  LDS: 2 FT FK ints of weights + 4 FT ints of bounds + FCH FWIN 3 +
+// FWIN FT 3 bytes = 43,776 bytes.
+constexpr int FT = 64;
+constexpr int FK = 16;
+constexpr int FWIN = 2 * FT + 16;
+constexpr int FCH = 16;
+
+__global__ __launch_bounds__(256) void frames_prepare_batch_kernel(
+        const uint8_t* __restrict__ in, int64_t in_bytes, const int64_t* __restrict__ in_off, const int* __restrict__ dims,
+        const double* __restrict__ sigma, const uint64_t* __restrict__ seed, const double* __restrict__ draws,
+        const int64_t* __restrict__ draws_off, int64_t draws_len, uint8_t* __restrict__ out, int64_t out_bytes,
+        const int64_t* __restrict__ out_off, int max_h, int max_w) {
+    __shared__ int s_kx[FT * FK], s_ky[FT * FK], s_bx[2 * FT], s_by[2 * FT];
+    __shared__ uint8_t s_rgb[FCH * FWIN * 3], s_h[FWIN * FT * 3];
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const int64_t H = dims[3 * img], W = dims[3 * img + 1];
+    const int mode = dims[3 * img + 2];
+    const int64_t ioff = in_off[img], ooff = out_off[img];
+    // an entry that does not lie inside both buffers, or that the grid was not sized for, is never touched
+    if (H <= 0 || W <= 0 || H > max_h || W > max_w || mode < 0 || mode > 2 || (mode == 2 && (H < 2 || W < 2))) return;
+    if (ioff < 0 || ioff > in_bytes || H * W > (in_bytes - ioff) / 3) return;
+    const int OH = mode == 2 ? (int)(H / 2) : (int)H, OW = mode == 2 ? (int)(W / 2) : (int)W;
+    if (ooff < 0 || ooff > out_bytes || (int64_t)OH * OW > (out_bytes - ooff) / 3) return;
+    const uint8_t* src = in + ioff;
+    uint8_t* dst = out + ooff;
+    if (mode != 2) {
+        const size_t n_elem = (size_t)(H * W) * 3;
+        for (size_t e = (size_t)blockIdx.x * 256 + tid; e < n_elem; e += (size_t)gridDim.x * 256) {
+            const size_t px = e / 3;
+            dst[e] = mode == 0 ? src[e] : src[px * 3 + (2 - (int)(e - px * 3))];
+        }
+        return;
+    }
+    const double* d = nullptr;
+    if (draws) {
+        const int64_t doff = draws_off[img];
+        if (doff < 0 || doff > draws_len || H * W > (draws_len - doff) / 3) return;
+        d = draws + doff;
+    }
+    const int tiles_x = (OW + FT - 1) / FT, tiles_y = (OH + FT - 1) / FT;
+    if (blockIdx.x >= (unsigned)(tiles_x * tiles_y)) return;
+    const int ox0 = (int)(blockIdx.x % tiles_x) * FT, oy0 = (int)(blockIdx.x / tiles_x) * FT;
+    const int nx = OW - ox0 < FT ? OW - ox0 : FT, ny = OH - oy0 < FT ? OH - oy0 : FT;
+    if (tid < nx) resize_coeffs<FK>((int)W, OW, ox0 + tid, s_bx[2 * tid], s_bx[2 * tid + 1], s_kx + tid * FK);
+    else if (tid >= FT && tid - FT < ny)
+        resize_coeffs<FK>((int)H, OH, oy0 + tid - FT, s_by[2 * (tid - FT)], s_by[2 * (tid - FT) + 1], s_ky + (tid - FT) * FK);
+    __syncthreads();
+    const int xlo = s_bx[0], win_w = s_bx[2 * (nx - 1)] + s_bx[2 * (nx - 1) + 1] - xlo;
+    const int ylo = s_by[0], win_h = s_by[2 * (ny - 1)] + s_by[2 * (ny - 1) + 1] - ylo;
+    if (win_w > FWIN || win_h > FWIN) return;       // cannot happen for a halving (above); the same in every thread of the block
+    const double s = sigma[img];
+    const uint64_t sd = seed[img];
+    const bool plain = s == 0.0 && d == nullptr;    // frame_noise_kernel's rule: the channel flip alone
+    const int row_len = win_w * 3, out_len = nx * 3;
+    for (int r0 = 0; r0 < win_h; r0 += FCH) {
+        const int rows = win_h - r0 < FCH ? win_h - r0 : FCH;
+        for (int e = tid; e < rows * row_len; e += 256) {
+            const int r = e / row_len, j = e - r * row_len, px = j / 3, c = j - px * 3;
+            const size_t at = ((size_t)(ylo + r0 + r) * W + (xlo + px)) * 3;
+            const uint8_t v = src[at + (2 - c)];
+            s_rgb[e] = plain ? v : noisy_byte(v, d ? d[at + c] : normal_draw(sd, at + c), s);
+        }
+        __syncthreads();
+        for (int e = tid; e < rows * out_len; e += 256) {
+            const int r = e / out_len, j = e - r * out_len, x = j / 3, c = j - x * 3;
+            const int cnt = s_bx[2 * x + 1];
+            const int* k = s_kx + x * FK;
+            const uint8_t* p = s_rgb + r * row_len + (s_bx[2 * x] - xlo) * 3 + c;
+            int ss = 1 << (PRECISION_BITS - 1);
+            for (int t = 0; t < cnt; ++t) ss += (int)p[3 * t] * k[t];
+            s_h[((r0 + r) * FT + x) * 3 + c] = clip8(ss);
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < ny * out_len; e += 256) {
+        const int y = e / out_len, j = e - y * out_len, x = j / 3, c = j - x * 3;
+        const int cnt = s_by[2 * y + 1];
+        const int* k = s_ky + y * FK;
+        const uint8_t* p = s_h + ((s_by[2 * y] - ylo) * FT + x) * 3 + c;
+        int ss = 1 << (PRECISION_BITS - 1);
+        for (int t = 0; t < cnt; ++t) ss += (int)p[t * FT * 3] * k[t];
+        dst[((size_t)(oy0 + y) * OW + (ox0 + x)) * 3 + c] = clip8(ss);
     }
 }
 
@@ -182,6 +285,23 @@ int seam_noise_u8_batch(uint8_t* buf, int64_t buf_bytes, const int64_t* img_off,
     if (grid.x == 0) return 0;
     hipLaunchKernelGGL(noise_u8_batch_kernel, grid, dim3(256), 0, (hipStream_t)stream, buf, buf_bytes, img_off, img_dims, sigma,
                        seed, draws, draws_off);
+    return (int)hipGetLastError();
+}
+
+int seam_frames_prepare_batch_u8(const uint8_t* in, int64_t in_bytes, const int64_t* in_off, const int* dims, const double* sigma,
+                                 const uint64_t* seed, const double* draws, const int64_t* draws_off, int64_t draws_len,
+                                 uint8_t* out, int64_t out_bytes, const int64_t* out_off, int n_images, int max_h, int max_w,
+                                 void* stream) {
+    if (n_images < 1 || n_images > 65535 || in_bytes < 0 || out_bytes < 0 || draws_len < 0 || max_h < 1 || max_w < 1)
+        return (int)hipErrorInvalidValue;
+    if (!in || !out || !in_off || !out_off || !dims || !sigma || !seed || (draws && !draws_off)) return (int)hipErrorInvalidValue;
+    // the image sizes are on the device; the caller's largest height and width size the grid: one block per tile of the largest
+    // half-size image, and an image beyond them is skipped as a bad entry is.  Copies (modes 0 and 1) stride over these blocks.
+    const int64_t tiles = (int64_t)((max_h / 2 + FT - 1) / FT) * ((max_w / 2 + FT - 1) / FT);
+    if (tiles > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : tiles), (unsigned)n_images);
+    hipLaunchKernelGGL(frames_prepare_batch_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, in_bytes, in_off, dims, sigma, seed,
+                       draws, draws_off, draws_len, out, out_bytes, out_off, max_h, max_w);
     return (int)hipGetLastError();
 }
 

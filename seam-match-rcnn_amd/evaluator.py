@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import frames, ops
 
 K_THRESHOLDS = (1, 5, 10, 20)          # ref evaluate_movingfashion.py:15
 
@@ -62,6 +62,8 @@ def collect_descriptors(model, data_loader, device, score_threshold: float = 0.0
     count_products = count_street = 0
     for images, targets in data_loader:
         count_products += 1
+        if any("frame_prep" in t for t in targets):         # a lazy MovingFashionDataset: the frame work of its eager form, here
+            images, targets = frames.prepare_frames(images, targets, device)
         images = [im.to(device) for im in images]
         output = [o for x in range(0, len(images), step) for o in model(images[x:x + step])]
         keep0 = output[0]["scores"] >= score_threshold

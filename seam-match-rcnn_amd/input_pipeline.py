@@ -15,6 +15,11 @@ A phase-2 batch from a lazy ``datasets.MultiDF2Dataset.MultiDeepFashion2Dataset`
 its targets: the reference's per-image host noise then runs as one launch (``seam_noise_u8_batch``) on the staged bytes, before
 the preprocess launch reads them, in the same copy and on the same stream.  ``apply_noise`` is that launch alone, for callers that
 hand the model lists of images.
+
+A phase-3 batch from a lazy ``datasets.MFDataset.MovingFashionDataset`` carries ``"frame_prep"`` / ``"frame_sigma"`` /
+``"frame_seed"``: the decoded frames cross the bus at full resolution, and the reference's per-frame host work (BGR -> RGB, noise,
+PIL resize to half size) runs as one launch (``seam_frames_prepare_batch_u8``) in front of the preprocess launch, which reads its
+output buffer; both tables travel in the batch's one copy.  ``frames.prepare_frames`` is that launch alone.
 """
 from __future__ import annotations
 
@@ -23,12 +28,14 @@ from typing import Sequence
 
 import torch
 
+from . import frames as frames_mod
 from . import mask_utils, ops
 from .models import detection as det
 from .models.detection import PreparedImages  # noqa: F401  (the public name lives here)
 
 _LAZY_KEYS = ("segmentation", "size", "hflip")
 _NOISE_KEYS = ("noise_sigma", "noise_seed")
+_FRAME_KEYS = frames_mod.FRAME_KEYS
 
 
 def _noise_of(targets):
@@ -53,10 +60,12 @@ def apply_noise(images: Sequence[torch.Tensor], targets: Sequence[dict], device)
     return ops.noise_u8_batch(images, sigmas, seeds, device=device), [_without(t, _NOISE_KEYS) for t in targets]
 
 
-def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None, noise=None) -> PreparedImages:
+def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None, noise=None, frames=None) -> PreparedImages:
     """uint8 ``[H,W,3]`` images (host or device) -> the batch ``model.transform`` would build from ``to_tensor`` of them (flipped
     where ``flips[i]``) for the model's current ``min_size`` / ``max_size`` / ``size_divisible`` and stem form, in one launch.
-    ``noise`` = ``(sigmas, seeds)``: the images are first given the noise ``ops.noise_u8_batch`` gives them, one launch more."""
+    ``noise`` = ``(sigmas, seeds)``: the images are first given the noise ``ops.noise_u8_batch`` gives them, one launch more.
+    ``frames`` = ``(modes, sigmas, seeds)``: the images are first prepared as ``ops.frames_prepare_batch`` prepares them, one
+    launch more, and ``orig`` holds the sizes after that (halved for mode 2)."""
     tr = model.transform
     if det.adt(tr) != torch.float32:
         raise NotImplementedError("prepare_batch writes fp32 batches only (training is fp32 only); with an fp16 compute dtype hand "
@@ -66,12 +75,33 @@ def prepare_images(images: Sequence[torch.Tensor], device, model, flips=None, no
         raise ValueError("prepare_batch: empty image list")
     if not all(isinstance(i, torch.Tensor) and i.dtype == torch.uint8 and i.dim() == 3 and i.shape[2] == 3 for i in images):
         raise ValueError("prepare_batch: the images must be uint8 [H,W,3] tensors (a dataset built with lazy=True / ToTensor(lazy=True))")
-    orig = [(int(i.shape[0]), int(i.shape[1])) for i in images]
-    sizes = [det.resized_size(h, w, tr.min_size, tr.max_size)[:2] for h, w in orig]
     d = tr.size_divisible
-    hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
-    wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
     s2d = tr.prepared_s2d()
+
+    def plan(orig):
+        sizes = [det.resized_size(h, w, tr.min_size, tr.max_size)[:2] for h, w in orig]
+        return sizes, int(math.ceil(max(s[0] for s in sizes) / d) * d), int(math.ceil(max(s[1] for s in sizes) / d) * d)
+
+    if frames is not None:
+        if noise is not None:
+            raise ValueError("prepare_batch: a batch carries frame keys or noise keys, not both")
+        flips = [False] * len(images) if flips is None else [bool(f) for f in flips]
+        if len(flips) != len(images):
+            raise ValueError("prepare_batch: one flip per image is needed")
+        modes = list(frames[0])
+        if len(modes) != len(images):
+            raise ValueError("prepare_batch: one mode per image is needed")
+        orig = [ops.frame_out_size(i.shape[0], i.shape[1], m) for i, m in zip(images, modes)]
+        if any(min(z) < 1 for z in orig):
+            raise ValueError("prepare_batch: a frame that is halved needs at least 2 x 2 pixels")
+        sizes, hp, wp = plan(orig)
+        # the preprocess launch's table is staged with the frames launch's: one copy for both
+        pre_dims = [(o[0], o[1], z[0], z[1], int(f)) for o, z, f in zip(orig, sizes, flips)]
+        st = ops.stage_frames("prepare_batch", images, *frames, device, pre_dims=pre_dims)
+        x = ops.preprocess_u8_flat(ops.launch_frames(st), st.out_off, st.pre_dims, hp, wp, s2d)
+        return PreparedImages(x, sizes, orig, (hp, wp), tr.min_size, tr.max_size, d, s2d)
+    orig = [(int(i.shape[0]), int(i.shape[1])) for i in images]
+    sizes, hp, wp = plan(orig)
     x = ops.preprocess_u8_batch(images, sizes, hp, wp, flips, s2d, device=device, noise=noise)
     return PreparedImages(x, sizes, orig, (hp, wp), tr.min_size, tr.max_size, d, s2d)
 
@@ -86,15 +116,21 @@ def prepare_batch(images: Sequence[torch.Tensor], targets: Sequence[dict], devic
     image's own size, through ``targets_to_device`` and a device flip (what ``evaluator_det`` reads); ``masks="none"`` -- both keys
     are dropped and nothing is rasterised (phase 2's loops and ``evaluator_df2`` read boxes only).  ``"noise_sigma"`` /
     ``"noise_seed"`` (a lazy ``MultiDeepFashion2Dataset``) put the noise launch in front of the preprocess launch and are
-    dropped.  Other tensors move to ``device``; other values pass through."""
+    dropped.  ``"frame_prep"`` / ``"frame_sigma"`` / ``"frame_seed"`` (a lazy ``MovingFashionDataset``; ``masks="none"`` is the
+    natural setting, its targets have no ``"segmentation"``) put the frames launch there instead and are dropped;
+    ``PreparedImages.orig`` then holds the sizes after halving, which the boxes refer to.  A batch that mixes frame keys with
+    ``"noise_sigma"`` raises ValueError.  Other tensors move to ``device``; other values pass through."""
     if masks not in ("resized", "original", "none"):
         raise ValueError('prepare_batch: masks must be "resized", "original" or "none"')
     images, targets = list(images), list(targets)
     if len(images) != len(targets):
         raise ValueError("one target dict per image is needed")
     flips = [bool(t.get("hflip", False)) for t in targets]
-    prepared = prepare_images(images, device, model, flips, _noise_of(targets))
-    targets = [_without(t, _NOISE_KEYS) for t in targets]
+    with_frames = any("frame_prep" in t for t in targets)
+    if with_frames and any("noise_sigma" in t for t in targets):
+        raise ValueError("prepare_batch: a batch carries frame keys (MovingFashion) or noise keys (Multi-DeepFashion2), not both")
+    prepared = prepare_images(images, device, model, flips, _noise_of(targets), frames_mod.frame_args(targets) if with_frames else None)
+    targets = [_without(t, _NOISE_KEYS + _FRAME_KEYS) for t in targets]
     device = prepared.tensor.device
     for i, (t, o) in enumerate(zip(targets, prepared.orig)):
         if "segmentation" in t and "size" not in t:

@@ -1597,6 +1597,177 @@ def resize_bicubic_u8(img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor
     return out
 
 
+FRAME_AS_IS, FRAME_RGB, FRAME_NOISY_HALF = 0, 1, 2      # the modes of seam_frames_prepare_batch_u8
+
+
+def frame_out_size(h: int, w: int, mode: int) -> tuple:
+    """The size ``seam_frames_prepare_batch_u8`` writes an ``h`` x ``w`` image of ``mode`` at: halved for mode 2, else its own."""
+    return (int(h) // 2, int(w) // 2) if int(mode) == FRAME_NOISY_HALF else (int(h), int(w))
+
+
+def frames_prepare_flat(flat: torch.Tensor, in_off: torch.Tensor, dims: torch.Tensor, sigma: torch.Tensor, seed: torch.Tensor,
+                        out: torch.Tensor, out_off: torch.Tensor, max_h: int, max_w: int, draws: Optional[torch.Tensor] = None,
+                        draws_off: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``seam_frames_prepare_batch_u8`` on device tables: ``flat`` uint8 [bytes] holds N HWC images, image i at byte ``in_off[i]``
+    (int64 [N]) with ``dims`` int32 [N,3] = (h, w, mode), ``sigma`` float64 [N], ``seed`` int64 [N] (the uint64 seeds' bits); the
+    results go to ``out`` uint8 [bytes] at ``out_off`` (int64 [N]).  ``max_h`` / ``max_w``: the largest h and w.  ``draws`` float64
+    [elements] + ``draws_off`` int64 [N]: given standard-normal draws instead of the generator's.  One launch; returns ``out``."""
+    flat, out = _req(flat, torch.uint8, "flat"), _req(out, torch.uint8, "out")
+    in_off, out_off = _req(in_off, torch.int64, "in_off"), _req(out_off, torch.int64, "out_off")
+    dims, sigma, seed = _req(dims, torch.int32, "dims"), _req(sigma, torch.float64, "sigma"), _req(seed, torch.int64, "seed")
+    n = in_off.numel()
+    if flat.dim() != 1 or out.dim() != 1 or in_off.dim() != 1 or tuple(dims.shape) != (n, 3) \
+            or any(tuple(t.shape) != (n,) for t in (out_off, sigma, seed)):
+        raise ValueError("frames_prepare_flat: flat / out uint8 [bytes], in_off / out_off / seed int64 [N], sigma float64 [N] and "
+                         "dims int32 [N,3] are needed")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"frames_prepare_flat: 1 <= N <= 65535 images per launch, got {n}")
+    if int(max_h) < 1 or int(max_w) < 1:
+        raise ValueError("frames_prepare_flat: max_h and max_w must be positive")
+    if (draws is None) != (draws_off is None):
+        raise ValueError("frames_prepare_flat: draws and draws_off go together")
+    if draws is not None:
+        draws, draws_off = _req(draws, torch.float64, "draws"), _req(draws_off, torch.int64, "draws_off")
+        if draws.dim() != 1 or tuple(draws_off.shape) != (n,):
+            raise ValueError("frames_prepare_flat: draws float64 [elements] and draws_off int64 [N] are needed")
+    if any(t.device != flat.device for t in (out, in_off, out_off, dims, sigma, seed, draws, draws_off) if t is not None):
+        raise ValueError("frames_prepare_flat: every tensor must lie on one device")
+    with torch.cuda.device(flat.device):
+        _native.check(_native.lib().seam_frames_prepare_batch_u8(
+            _ptr(flat), flat.numel(), _ptr(in_off), _ptr(dims), _ptr(sigma), _ptr(seed), _ptr(draws), _ptr(draws_off),
+            0 if draws is None else draws.numel(), _ptr(out), out.numel(), _ptr(out_off), n, int(max_h), int(max_w), _stream()),
+            "seam_frames_prepare_batch_u8")
+    return out
+
+
+class StagedFrames:
+    """A frame batch on the device: ``dev`` (the flat buffer: tables, then the images' bytes) and views of its tables."""
+    __slots__ = ("dev", "in_off", "out_off", "sigma", "seed", "dims", "pre_dims", "out_hw", "out_bytes", "max_h", "max_w")
+
+
+def stage_frames(what: str, images, modes, sigmas, seeds, device, pre_dims=None) -> StagedFrames:
+    """The checks and the staging of a frame batch.  Host images: the tables and the images' bytes are packed into the pinned
+    staging buffer of ``device`` and cross in ONE copy; device images: the tables alone are uploaded and joined with the bytes
+    there.  Tables, in this order from byte 0: int64 [N] input offsets (into the buffer itself), int64 [N] output offsets (packed
+    from 0), float64 [N] sigmas, uint64 [N] seeds, int32 [N,3] (h, w, mode) and, with ``pre_dims`` (int32 [N,5] rows for
+    ``seam_preprocess_u8_batch_f32``, which reads the output buffer with the output offsets), those."""
+    import math
+    import numpy as np
+    # device check FIRST: no CPU path exists, and nothing below may run without a HIP device to write to
+    if not torch.cuda.is_available() or not all(isinstance(i, torch.Tensor) for i in images):
+        raise _native.SeamNativeError(f"{what}: expected uint8 tensors and a HIP device (no CPU path exists)")
+    n = len(images)
+    if not 1 <= n <= 65535:
+        raise ValueError(f"{what}: 1 <= N <= 65535 images per launch, got {n}")
+    on_dev = [i.is_cuda for i in images]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError(f"{what}: the images must be all on the host or all on one HIP device")
+    for i in images:
+        if i.dtype != torch.uint8:
+            raise TypeError(f"image: expected torch.uint8, got {i.dtype}")
+        if i.dim() != 3 or i.shape[2] != 3 or i.shape[0] < 1 or i.shape[1] < 1:
+            raise ValueError("uint8 images must be [H,W,3]")
+    if len(modes) != n or len(sigmas) != n or len(seeds) != n:
+        raise ValueError(f"{what}: one mode, one sigma and one seed per image are needed")
+    modes, sigmas = [int(m) for m in modes], [float(s) for s in sigmas]
+    if any(m not in (FRAME_AS_IS, FRAME_RGB, FRAME_NOISY_HALF) for m in modes):
+        raise ValueError(f"{what}: a mode is 0 (as is), 1 (BGR -> RGB) or 2 (BGR -> RGB, noise, half resolution)")
+    if not all(math.isfinite(s) for s in sigmas):
+        raise ValueError(f"{what}: every sigma must be finite")
+    if any(m == FRAME_NOISY_HALF and min(i.shape[0], i.shape[1]) < 2 for i, m in zip(images, modes)):
+        raise ValueError(f"{what}: a frame that is halved needs at least 2 x 2 pixels")
+    dims = np.asarray([(int(i.shape[0]), int(i.shape[1]), m) for i, m in zip(images, modes)], np.int32)
+    out_hw = [frame_out_size(*d) for d in dims.tolist()]
+    in_bytes = dims[:, 0].astype(np.int64) * dims[:, 1] * 3
+    out_bytes = np.asarray([h * w * 3 for h, w in out_hw], np.int64)
+    extra = None
+    if pre_dims is not None:
+        extra = np.ascontiguousarray(pre_dims, np.int32)
+        if extra.shape != (n, 5) or [tuple(r) for r in extra[:, :2].tolist()] != out_hw:
+            raise ValueError(f"{what}: pre_dims must be int32 [N,5] rows that start with the output sizes")
+    size = 44 * n + (20 * n if extra is not None else 0)
+    head = 32 * ((size + 31) // 32)
+    in_off = head + np.cumsum(in_bytes) - in_bytes
+    out_off = np.cumsum(out_bytes) - out_bytes
+    parts = [in_off.astype(np.int64).view(np.uint8), out_off.astype(np.int64).view(np.uint8), np.asarray(sigmas, np.float64).view(np.uint8),
+             np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64).view(np.uint8), dims.reshape(-1).view(np.uint8)]
+    if extra is not None:
+        parts.append(extra.reshape(-1).view(np.uint8))
+    tables = np.concatenate(parts + [np.zeros(head - size, np.uint8)])
+    total = int(head + in_bytes.sum())
+    if all(on_dev):
+        device = images[0].device
+        if any(i.device != device for i in images):
+            raise ValueError(f"{what}: the images must lie on one device")
+        dev = torch.cat([torch.from_numpy(tables).to(device)] + [i.contiguous().reshape(-1) for i in images])
+    else:
+        device = _mask_device(device if device is not None else "cuda")
+        stage = _staging(total, device)
+        stage[:head].copy_(torch.from_numpy(tables))
+        for i, o, b in zip(images, in_off.tolist(), in_bytes.tolist()):
+            stage[o:o + b].copy_(i.reshape(-1))
+        dev = stage[:total].to(device, non_blocking=True)                     # the batch's one host-to-device copy
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        _STAGING[_staging_key(device)] = (_STAGING[_staging_key(device)][0], ev)
+    st = StagedFrames()
+    st.dev = dev
+    st.in_off, st.out_off = dev[:8 * n].view(torch.int64), dev[8 * n:16 * n].view(torch.int64)
+    st.sigma, st.seed = dev[16 * n:24 * n].view(torch.float64), dev[24 * n:32 * n].view(torch.int64)
+    st.dims = dev[32 * n:44 * n].view(torch.int32).view(n, 3)
+    st.pre_dims = dev[44 * n:64 * n].view(torch.int32).view(n, 5) if extra is not None else None
+    st.out_hw, st.out_bytes = out_hw, int(out_bytes.sum())
+    st.max_h, st.max_w = int(dims[:, 0].max()), int(dims[:, 1].max())
+    return st
+
+
+def launch_frames(st: StagedFrames, noise_values=None) -> torch.Tensor:
+    """The frames launch on a staged batch -> the flat uint8 output buffer (image i at ``st.out_off[i]``, ``st.out_hw[i]``)."""
+    draws = draws_off = None
+    if noise_values is not None:
+        device = st.dev.device
+        given = [v.to(device).reshape(-1) for v in noise_values if v is not None]
+        draws = torch.cat(given) if given else torch.zeros(1, dtype=torch.float64, device=device)
+        offs, pos = [], 0
+        for v in noise_values:
+            offs.append(pos)
+            pos += 0 if v is None else v.numel()
+        draws_off = torch.tensor(offs, dtype=torch.int64).to(device)
+    out = torch.empty((max(st.out_bytes, 1),), dtype=torch.uint8, device=st.dev.device)
+    return frames_prepare_flat(st.dev, st.in_off, st.dims, st.sigma, st.seed, out, st.out_off, st.max_h, st.max_w, draws, draws_off)
+
+
+def frames_prepare_batch(images: Sequence[torch.Tensor], modes: Sequence[int], sigmas: Sequence[float], seeds: Sequence[int],
+                         noise_values: Optional[Sequence] = None, device=None) -> list:
+    """The per-frame work of the reference's ``MovingFashionDataset.__getitem__`` for a batch of uint8 [H,W,3] images of different
+    sizes in ONE launch (``seam_frames_prepare_batch_u8``).  ``modes[i]``: 0 -- the image as it is (the RGB shop image, the zero
+    placeholder of an unreadable frame); 1 -- BGR -> RGB (``noise=False``); 2 -- BGR -> RGB, noise of ``sigmas[i]``, then Pillow's
+    BICUBIC resize to ``(H // 2, W // 2)``: what ``resize_bicubic_u8(frame_noise(bgr, sigma, noise, seed), H // 2, W // 2)`` gives,
+    bit for bit, with no full-resolution intermediate.  The draws are ``noise_values[i]`` (float64 [H,W,3], or None for an image
+    that is not mode 2) or, without ``noise_values``, the counter-based ones of ``frame_noise`` for ``seeds[i]``.
+    Returns uint8 [h,w,3] RGB device tensors, views of one buffer; the caller's tensors are never written.  The images are all
+    host tensors (one pinned copy through the staging buffer, the tables in the same copy, to ``device``, default: the current
+    HIP device) or all on one HIP device.  Without a HIP device: SeamNativeError."""
+    images, modes = list(images), list(modes)
+    if noise_values is not None:
+        noise_values = list(noise_values)
+        ok = len(noise_values) == len(images) == len(modes)
+        for v, i, m in zip(noise_values, images, modes):
+            if m == FRAME_NOISY_HALF or v is not None:
+                ok = ok and isinstance(v, torch.Tensor) and isinstance(i, torch.Tensor) and v.dtype == torch.float64 \
+                    and tuple(v.shape) == tuple(i.shape)
+        if not ok:
+            raise ValueError("frames_prepare_batch: noise_values must hold one float64 tensor of the image's shape per mode-2 image")
+        noise_values = [v if m == FRAME_NOISY_HALF else None for v, m in zip(noise_values, modes)]
+    st = stage_frames("frames_prepare_batch", images, modes, list(sigmas), list(seeds), device)
+    flat = launch_frames(st, noise_values)
+    out, pos = [], 0
+    for h, w in st.out_hw:
+        out.append(flat[pos:pos + h * w * 3].view(h, w, 3))
+        pos += h * w * 3
+    return out
+
+
 # ------------------------------------------------------------------------------ RoI heads training branch (csrc/seam_roi_train.hip)
 SAMPLE_MAX_CANDIDATES = 16384      # per image: rpn_post_nms_top_n_train (8000) + the GT boxes fit
 

@@ -59,7 +59,8 @@ class ToTensor:
 class RandomHorizontalFlip:
     """With probability ``prob`` (one ``random.random()`` per call): mirror the sample left-right.  Boxes become
     ``(width - x2, y1, width - x1, y2)``, in place.  A float ``[3,H,W]`` image and dense ``"masks"`` are flipped here; a uint8
-    ``[H,W,3]`` image keeps its bytes and the target's ``"hflip"`` is toggled instead."""
+    ``[H,W,3]`` image keeps its bytes and the target's ``"hflip"`` is toggled instead (a MovingFashion frame with
+    ``"frame_prep" == 2`` is still at full resolution there: its boxes are mirrored in the half-size image they refer to)."""
 
     def __init__(self, prob):
         self.prob = prob
@@ -72,6 +73,8 @@ class RandomHorizontalFlip:
             raise ValueError("RandomHorizontalFlip: a uint8 [H,W,3] image is flipped on the device, which needs the target's "
                              "'segmentation' instead of dense 'masks' (build the dataset with lazy=True)")
         width = image.shape[1] if lazy else image.shape[-1]
+        if lazy and target.get("frame_prep") == 2:      # a MovingFashion frame still at full resolution: its boxes refer to half
+            width //= 2
         boxes = target["boxes"]
         left = width - boxes[:, 2]
         boxes[:, 2] = width - boxes[:, 0]
