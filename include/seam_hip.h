@@ -181,6 +181,19 @@ int seam_conv1x1_sxpc_dual_supported(long long M, int C1, int C2, int K);
 int seam_conv1x1_sxpc_dual(const float* x1, const float* x2, const void* w_packed, const float* scale, const float* shift, float* y,
                            int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int K, int relu, seam_stream_t stream);
 
+/* conv1x1_sxpc_up (csrc/seam_pwsx.hip): the same kernel with a nearest-upsampled coarse map as its residual -- torchvision's
+ * FeaturePyramidNetwork lateral 1x1 (inner_blocks) plus the top-down merge, inner_lateral + F.interpolate(last_inner, size=...,
+ * mode="nearest"), in one launch.  x [N, Ho, Wo, C], top [N, rH, rW, K] read at (n, nearest(ho), nearest(wo)) by ATen's rule
+ * src = min(floor(dst * (float)in / (float)out), in - 1).  The result is bit for bit seam_conv1x1_sxpc (scale, shift, no residual,
+ * no ReLU) followed by seam_upsample_add_f32 and, if asked, ReLU.
+ *   _supported: 1 when (M, C, K) is a shape of seam_conv1x1_sxpc_supported, M == N Ho Wo, rH, rW >= 1, every grid side is below
+ *   2^24 and the coarse images that one tile of 128 output pixels touches lie within 2 GiB (top itself may be any size), else 0;
+ *   Wo == 1 and 1 x 1 maps are served;
+ *   seam_conv1x1_sxpc_up: a null top, relu outside 0 | 1 or an unsupported geometry returns hipErrorInvalidValue and launches nothing. */
+int seam_conv1x1_sxpc_up_supported(long long M, int N, int Ho, int Wo, int C, int K, int rH, int rW);
+int seam_conv1x1_sxpc_up(const float* x, const void* w_packed, const float* scale, const float* shift, const float* top, float* y,
+                         int N, int Ho, int Wo, int C, int K, int rH, int rW, int relu, seam_stream_t stream);
+
 /* fp16 twin of seam_conv1x1_sw_f32 (csrc/seam_pwh.hip, round 6): the config-5 path's 1x1 layers [TV Bottleneck conv1 / conv3 /
  * stride-1 projection shortcut, FeaturePyramidNetwork.inner_blocks; behind models/video_matchrcnn.py:337] as a STREAMING kernel --
  * weights stationary in LDS, independent waves, 16-byte NHWC pieces in and out -- with the contract of seam_conv2d_f16 /

@@ -104,6 +104,8 @@ SIGNATURES = {
     "seam_conv1x1_sxpc": (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _p]),
     "seam_conv1x1_sxpc_dual_supported": (_i, [C.c_longlong, _i, _i, _i]),
     "seam_conv1x1_sxpc_dual": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_conv1x1_sxpc_up_supported": (_i, [C.c_longlong, _i, _i, _i, _i, _i, _i, _i]),
+    "seam_conv1x1_sxpc_up": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv1x1_swh_f16": (_i, [_p, _p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_stem_s2d_swh_f16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "seam_conv2d_dual_f16": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),

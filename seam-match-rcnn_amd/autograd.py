@@ -450,7 +450,7 @@ class FPNFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, packed, c2, c3, c4, c5, *params):
-        inner, layer = packed
+        inner, layer = packed[:2]      # (the exact packs: the split twins behind them are never taped)
         feats = [f.detach() for f in (c2, c3, c4, c5)]
         last = ops.conv2d(feats[3], inner[3])
         inners = [None, None, None, last]

@@ -36,17 +36,30 @@
 // on either side.  Weights, consumers and epilogue are the plain kernel's on the [K, C1 + C2] matrix; the bits are those of the plain
 // kernel on the concatenated rows.
 //
-// LDS map (139264 bytes, one block per CU):
+// The upsampled-residual form conv1x1_sxpc_up (sxpc_body<false, true>) runs the FPN's lateral 1x1 with its nearest top-down merge:
+// conv(x) * scale + shift, + top[n, nearest_src(ho), nearest_src(wo), :], ReLU.  Only the source of the epilogue's 16 residual pieces
+// per lane differs from the plain kernel.  The PRODUCERS compute the byte offset of each of the tile's 128 pixels in the coarse map
+// (one pixel per thread pair: the image by the two-source form's multiply-high rules, ho / wo by multiply-high, two
+// seam_fpn::nearest_src) and put them into a 512-byte LDS table with the store of the tile's first chunk; the consumers read it at
+// the tile's last chunk, which any chunk barrier in between orders; two tables by tile parity (a table is rewritten two tiles later,
+// behind a barrier the consumers reach only in the next tile).  The table's layout is [pixel & 7][pixel group][i], so the row-layout
+// lane fetches one pixel group's four offsets with one ds_read_b128 right before that group's four loads.  The coarse map's
+// descriptor is rebased per tile at the first image the tile touches (its index travels behind the table), so lane offsets stay 32-bit.
+// The bits are those of the plain kernel (scale, shift) followed by seam_upsample_add_f32 and ReLU.
+//
+// LDS map (139264 bytes, one block per CU; the upsampled-residual form: + 1056):
 //   [0, 102400)        two chunk buffers of 128 pixel rows x 400 bytes: plane 0 | plane 1 | plane 2 (64 bf16 = 128 bytes each) | 16
 //                      bytes of padding -- 25 slots of 16 bytes, odd, so the 16 lanes of a ds_read_b128 cycle (16 consecutive
 //                      pixels) meet 16 different bank groups
 //   [102400, 139264)   per consumer wave two transpose buffers of 32 pixels x (32 channels + 16 bytes)
+//   [139264, 140320)   (conv1x1_sxpc_up) two tables of 128 coarse-map byte offsets + the tile's first image (16 bytes)
 #include <hip/hip_runtime.h>
 #include "seam_device.h"
 #include <stdint.h>
 #include <algorithm>
 #include <type_traits>
 #include "seam_fastdiv.h"
+#include "seam_fpn_common.h"
 #include "seam_launch.h"
 #include "seam_pack_items.h"
 #include "seam_split.h"
@@ -65,6 +78,10 @@ constexpr int TBUF = 32 * TROW;             // 4608 bytes
 constexpr int TR0 = 2 * ABUF;
 constexpr int LDS_BYTES = TR0 + 4 * 2 * TBUF;
 static_assert(LDS_BYTES <= 160 * 1024 && ABUF + 3 * PLB < 65536 && 4 * 32 * ROWB < 65536, "LDS map / ds immediates");
+constexpr int TBLB = BM * 4 + 16;           // conv1x1_sxpc_up: one offset table (128 pixels) + the index of the tile's first image
+constexpr int TBL0 = LDS_BYTES;
+constexpr int LDS_UP_BYTES = LDS_BYTES + 2 * TBLB;
+static_assert(LDS_UP_BYTES <= 160 * 1024, "LDS map of the upsampled-residual form");
 constexpr int RB = 4;                       // k-steps of weight fragments in flight per consumer wave (= KS: the ring slot of a k-step is its index in the chunk)
 static_assert(RB == KS, "ring slot = k-step of the chunk");
 constexpr int RVA = 3;                      // pixel groups whose residual pieces are requested before the tile's last chunk (the fourth: at the
@@ -100,8 +117,19 @@ struct SxpcDual {
     unsigned img_step, row_step, px_step;      // byte steps of x2 per image / per output row (stride2 W2 C2 4) / per output pixel (stride2 C2 4)
 };
 
-template <bool DUAL>
-__device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) {
+// The coarse map of the upsampled-residual form (conv1x1_sxpc_up): output pixel (n, ho, wo) adds top[n, nearest_src(ho), nearest_src(wo), :]
+struct SxpcUp {
+    const float* top;                   // [N, rH, rW, K]
+    unsigned long long img_bytes;       // rH * rW * K * 4
+    int N, Ho, Wo, rH, rW;
+    unsigned HoWo;
+    unsigned m_howo, one_howo, thr;     // a row of the tile's image span -> its image: SxpcDual's rules
+    unsigned m_wo, one_wo;              // the remainder by Wo
+    unsigned img_step, row_step, px_step;      // byte steps of top per image / per coarse row (rW K 4) / per coarse pixel (K 4)
+};
+
+template <bool DUAL, bool UP = false>
+__device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, const SxpcUp& u = SxpcUp{}) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -183,7 +211,34 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
                 if (DUAL) x2_tile(tile);
             }
         };
+        // UP: the offset table of tile tl (see the header): pixel ptid >> 1 of the tile, written by the even thread of the pair
+        int st_tile = tile0, st_ck = 0, st_left = ntiles, st_par = 0;      // the STORE stage's tile / chunk (the request stage runs ahead)
+        const float fh = UP ? (float)u.rH / (float)u.Ho : 0.f, fw = UP ? (float)u.rW / (float)u.Wo : 0.f;
+        auto up_table = [&](const int tl, const int par) {
+            const unsigned row0 = (unsigned)fdivu(tl, p.tiles_n, p.m_tiles_n) * BM;
+            const unsigned n_first = __builtin_amdgcn_readfirstlane(row0 / u.HoWo);       // (a true division: once per tile, any M)
+            const unsigned r = (unsigned)ptid >> 1;
+            const unsigned rl = row0 - n_first * u.HoWo + r;       // row inside that image's output grid: < BM + HoWo
+            const unsigned nl = __umulhi(rl, u.m_howo) + rl * u.one_howo + (rl >= u.thr ? 1u : 0u);
+            const unsigned rem = rl - nl * u.HoWo;
+            const unsigned ho = __umulhi(rem, u.m_wo) + rem * u.one_wo, wo = rem - ho * u.Wo;
+            const unsigned hs = (unsigned)seam_fpn::nearest_src((int)ho, fh, u.rH), ws = (unsigned)seam_fpn::nearest_src((int)wo, fw, u.rW);
+            const unsigned off = nl * u.img_step + hs * u.row_step + ws * u.px_step;
+            LDSQ char* const tb = (LDSQ char*)smem + TBL0 + par * TBLB;
+            if (!(ptid & 1))
+                *reinterpret_cast<unsigned LDSQ*>(tb + ((r & 7) * 16 + (r >> 5) * 4 + ((r >> 3) & 3)) * 4) = row0 + r < (unsigned)p.M ? off : kOob;
+            if (ptid == 0) *reinterpret_cast<unsigned LDSQ*>(tb + BM * 4) = n_first;
+        };
         auto store_chunk = [&](const f32x4 (&src)[NP], const int buf) {
+            if constexpr (UP) {                 // with a tile's first chunk: its table (past the block's last tile: none)
+                if (st_ck == 0 && st_left > 0) up_table(st_tile, st_par);
+                if (++st_ck == n) {
+                    st_ck = 0;
+                    st_tile += S;
+                    --st_left;
+                    st_par ^= 1;
+                }
+            }
             if (SEAM_SXPC_ABL & 1) return;
 #pragma unroll
             for (int r = 0; r < NP; ++r) {
@@ -250,6 +305,8 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
         LDSQ char* const tw = (LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane & 31) * TROW + (lane >> 5) * 16;   // accumulator layout: piece 2 qd + h
         const LDSQ char* const tr = (const LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane >> 3) * TROW + (lane & 7) * 16;
         const int K32 = 32 * p.K * 4, K8 = 8 * p.K * 4;        // byte steps of a 32-pixel group / of 8 pixels
+        const LDSQ char* const tbr = (const LDSQ char*)smem + TBL0 + (lane >> 3) * 64;       // UP: this lane's pixel row of the offset table
+        int tpar = 0;                           // ... of the current tile (tile parity)
         int tile = tile0;
         ring_preload(tile);
         f32x4 rv[4][4], sc, sh;
@@ -262,6 +319,15 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
             const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)((const char*)(p.res ? p.res : p.y) + (size_t)tm_k * BM * out_row), 0, (int)(rows * out_row), 0x00020000);
             const unsigned ocol = ooff + (unsigned)(tn_k * 512);
+            const unsigned ccol = (unsigned)(tn_k * 512 + 128 * wn) + (unsigned)((lane & 7) * 16);      // UP: the lane's piece inside a coarse pixel
+            __amdgpu_buffer_rsrc_t t_rsrc = y_rsrc;         // UP: the coarse map from the tile's first image on (set at the last chunk)
+            // UP: pixel group m's residual pieces through the tile's offset table (rows past M: kOob, zeros)
+            auto up_request = [&](const int m) {
+                const u32x4 to = *reinterpret_cast<const u32x4 LDSQ*>(tbr + tpar * TBLB + m * 16);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(t_rsrc, to[i] + ccol, 0, 0));
+            };
             // the tile's first fragments (a tile's last chunk reads them ahead like every chunk, but they are not kept across the
             // epilogue, which needs the registers)
 #pragma unroll
@@ -279,7 +345,14 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
                     const f32x4 b = *reinterpret_cast<const f32x4*>((p.shift ? p.shift : (const float*)p.w) + ch);
                     sc = a;                     // (replaced in the epilogue: a select here would wait for the loads at once)
                     sh = b;
-                    if (p.res) {
+                    if constexpr (UP) {
+                        const unsigned n_first = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const unsigned LDSQ*>((const LDSQ char*)smem + TBL0 + tpar * TBLB + BM * 4));
+                        const unsigned long long left = (unsigned long long)((unsigned)u.N - n_first) * u.img_bytes;
+                        t_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)u.top + (size_t)n_first * u.img_bytes), 0,
+                                                                   (int)(left > kOob ? kOob : (unsigned)left), 0x00020000);
+#pragma unroll
+                        for (int m = 0; m < RVA; ++m) up_request(m);
+                    } else if (p.res) {
 #pragma unroll
                         for (int m = 0; m < RVA; ++m)
 #pragma unroll
@@ -347,9 +420,13 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
                 if (RES) {
 #pragma unroll
                     for (int m = RVA; m < 4; ++m)   // the pixel groups the last chunk had no registers for
+                        if constexpr (UP) {
+                            up_request(m);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, ocol + m * K32 + i * K8, 0, 0));
+                            for (int i = 0; i < 4; ++i)
+                                rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, ocol + m * K32 + i * K8, 0, 0));
+                        }
                     // (one wait for everything that came from memory, before the first store)
 #pragma unroll
                     for (int m = 0; m < 4; ++m) asm volatile("" :: "v"(rv[m][0]), "v"(rv[m][1]), "v"(rv[m][2]), "v"(rv[m][3]));
@@ -381,8 +458,9 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d) 
                     }
                 }
             };
-            if (p.res) {
+            if (UP || p.res) {
                 if (p.relu) finish_tile(std::true_type{}, std::true_type{}); else finish_tile(std::true_type{}, std::false_type{});
+                if constexpr (UP) tpar ^= 1;
             } else {
                 if (p.relu) finish_tile(std::false_type{}, std::true_type{}); else finish_tile(std::false_type{}, std::false_type{});
             }
@@ -399,6 +477,9 @@ __global__ void sxpc_pack_kernel(const float* __restrict__ w, unsigned short* __
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
         seam_pack::sxpc_item(w, out, i, C);
 }
+
+// (behind the pack kernel: the existing kernels keep their place in the module)
+__global__ __launch_bounds__(512, 2) void conv1x1_sxpc_up(const SxpcArgs p, const SxpcUp u) { sxpc_body<false, true>(p, SxpcDual{}, u); }
 
 int sxpc_plan(SxpcArgs& a, long long M, int C, int K) {
     if (M <= 0 || C < 256 || (C % CK) || K < 128 || (K % 128)) return 1;
@@ -444,6 +525,34 @@ int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long lon
     d.img_step = (unsigned)img2;
     d.row_step = (unsigned)((unsigned long long)stride2 * W2 * C2 * 4);
     d.px_step = (unsigned)((unsigned long long)stride2 * C2 * 4);
+    return 0;
+}
+
+// the upsampled-residual form: the plain plan of (N Ho Wo, C, K) and the coarse map's geometry
+int sxpc_up_plan(SxpcArgs& a, SxpcUp& u, long long N, long long Ho, long long Wo, int C, int K, long long rH, long long rW) {
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || rH <= 0 || rW <= 0) return 1;
+    if (N >= (1LL << 31) || Ho >= (1LL << 24) || Wo >= (1LL << 24) || rH >= (1LL << 24) || rW >= (1LL << 24)) return 1;     // (nearest_src: indices exact in fp32)
+    if (Ho * Wo >= (1LL << 31) || N * (Ho * Wo) >= (1LL << 31)) return 1;
+    if (sxpc_plan(a, N * Ho * Wo, C, K)) return 1;
+    const long long HoWo = Ho * Wo;
+    if ((unsigned long long)rH * rW >= (1ull << 31) / ((unsigned long long)K * 4)) return 1;       // one image of top inside a descriptor
+    const unsigned long long img = (unsigned long long)rH * rW * K * 4;
+    // a tile's 128 rows touch at most this many images; their pixels are addressed from the first one's start with 32-bit offsets
+    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
+    if (imgs * img > kOob) return 1;
+    const bool mid = HoWo >= 2 && HoWo < BM;
+    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
+    if (!seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)HoWo)) return 1;
+    u.img_bytes = img;
+    u.N = (int)N; u.Ho = (int)Ho; u.Wo = (int)Wo; u.rH = (int)rH; u.rW = (int)rW; u.HoWo = (unsigned)HoWo;
+    u.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
+    u.one_howo = HoWo == 1 ? 1u : 0u;
+    u.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
+    u.m_wo = seam_fastdiv::magic((unsigned long long)Wo);       // (0 for Wo = 1)
+    u.one_wo = Wo == 1 ? 1u : 0u;
+    u.img_step = (unsigned)img;
+    u.row_step = (unsigned)((unsigned long long)rW * K * 4);
+    u.px_step = (unsigned)((unsigned long long)K * 4);
     return 0;
 }
 
@@ -506,6 +615,32 @@ int seam_conv1x1_sxpc_dual(const float* x1, const float* x2, const void* w_packe
     if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
     hipLaunchKernelGGL(conv1x1_sxpc_dual, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
+    return (int)hipGetLastError();
+}
+
+/* 1 when seam_conv1x1_sxpc_up takes this lateral: the plain rule for (M, C, K), M == N Ho Wo, rH, rW >= 1 and the geometry rules of
+ * the launch (the coarse images one tile touches within 2 GiB, exact multiply-high divisions); else 0.  Wo == 1 and 1 x 1 maps are served. */
+int seam_conv1x1_sxpc_up_supported(long long M, int N, int Ho, int Wo, int C, int K, int rH, int rW) {
+    SxpcArgs a;
+    SxpcUp u;
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || M != (long long)N * Ho * Wo) return 0;
+    return sxpc_up_plan(a, u, N, Ho, Wo, C, K, rH, rW) == 0 ? 1 : 0;
+}
+
+/* y[N, Ho, Wo, K] = act(scale * (x[N Ho Wo, C] . w^T) + shift + top[n, nearest(ho), nearest(wo), :]): the bits of seam_conv1x1_sxpc
+ * (scale, shift) followed by seam_upsample_add_f32 and ReLU; top [N, rH, rW, K]; relu 0 | 1 */
+int seam_conv1x1_sxpc_up(const float* x, const void* w_packed, const float* scale, const float* shift, const float* top, float* y,
+                         int N, int Ho, int Wo, int C, int K, int rH, int rW, int relu, void* stream) {
+    SxpcArgs a;
+    SxpcUp u;
+    if ((relu != 0 && relu != 1) || !top || sxpc_up_plan(a, u, N, Ho, Wo, C, K, rH, rW)) return (int)hipErrorInvalidValue;
+    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    u.top = top;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_up>(LDS_UP_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc_up, dim3(grid), dim3(512), LDS_UP_BYTES, (hipStream_t)stream, a, u);
     return (int)hipGetLastError();
 }
 

@@ -58,14 +58,17 @@ def adt(module) -> torch.dtype:
 # model with ``set_split_f32``; SEAM_SPLIT_F32=0 for the process) switches it off and restores the exact-fp32 kernels bit for bit.
 # Classes: c1 = bottleneck 1x1 reductions, c3 = 1x1 expansions with their residual (C >= SPLIT_C3_MIN_C), c2s2 = the three
 # stride-2 3x3s, c3ds = the two-source shortcut GEMMs of layer2.0 / layer3.0 / layer4.0 (C1 + C2 >= SPLIT_C3DS_MIN_C: layer1.0, 64 + 64 on
-# one map, stays on conv1x1_sw).  The FPN laterals keep their fused fp32 kernels (the split kernel has no upsampled residual).
-# The long 1x1 layers of c1 / c3 (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel conv1x1_sxpc, c3ds on
-# its two-source form conv1x1_sxpc_dual (ops.SXPC; the same bits as conv_igemm_sx on the concatenated rows), the others on conv_igemm_sx.
+# one map, stays on conv1x1_sw), lat = the FPN's four lateral 1x1s (inner_blocks: 256 / 512 / 1024 / 2048 -> 256, three of them with
+# the nearest top-down merge), mdeconv = the mask head's 2x2 / stride-2 transposed conv as the 1x1 conv of its [1024, 256] matrix.
+# The long 1x1 layers of c1 / c3 / lat / mdeconv (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel
+# conv1x1_sxpc, c3ds on its two-source form conv1x1_sxpc_dual, the three merging laterals on its upsampled-residual form
+# conv1x1_sxpc_up (ops.SXPC; each the bits of conv_igemm_sx -- on the concatenated rows / followed by upsample_add_), the others on
+# conv_igemm_sx.  lat and mdeconv need SPLIT_DTYPE == SX6 (the only split form of those kernels).
 SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
 SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
 SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; the short reductions of layer1 / layer2 (C = 64, 128) are faster on conv1x1_sw
 SPLIT_C3DS_MIN_C = 384    # C1 + C2 of the served shortcut GEMMs: a rule on the layer's geometry alone, never on the batch
-SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds").split(",") if c)
+SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds,lat,mdeconv").split(",") if c)
 
 
 def split_on(module) -> bool:
@@ -465,21 +468,31 @@ class FeaturePyramidNetwork(nn.Module):
     def _pack_tensors(self):
         return list(self.parameters())
 
+    def _split_twins(self) -> bool:
+        return (cdt(self) == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True) and "lat" in SPLIT_CLASSES
+                and SPLIT_DTYPE == ops.SX6)
+
     def _pack_key(self):
-        return _key(self.parameters(), cdt(self))
+        return _key(self.parameters(), cdt(self)) + (self._split_twins(),)
 
     def packed(self):
+        """(lateral packs, output packs, split twins of the lateral packs or None): the twins (class ``lat``) are packed beside the
+        exact packs from the same parameters; ``forward`` takes them under ``split_on``, ``forward_taped`` never does."""
         dt = cdt(self)
         key = self._pack_key()
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
-                self._pk = ([ops.pack_conv(m.weight, m.bias, dtype=dt) for m in self.inner_blocks],
-                            [ops.pack_conv(m.weight, m.bias, pad=1, dtype=dt) for m in self.layer_blocks])
+                inner = [ops.pack_conv(m.weight, m.bias, dtype=(dt, ops.SX6) if self._split_twins() else (dt,)) for m in self.inner_blocks]
+                self._pk = ([p[0] for p in inner],
+                            [ops.pack_conv(m.weight, m.bias, pad=1, dtype=dt) for m in self.layer_blocks],
+                            [p[1] for p in inner] if self._split_twins() else None)
             self._pk_key = key
         return self._pk
 
     def forward(self, feats: List[torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
-        inner, layer = self.packed()
+        inner, layer, twins = self.packed()
+        if twins is not None and split_on(self):
+            inner = twins
         x3 = feats[3]
         if not (LEVEL_STREAMS and x3.is_cuda):
             last = ops.conv2d(x3, inner[3])
@@ -1017,13 +1030,17 @@ class MaskRCNNPredictor(nn.Module):
         4 sub-pixel channel groups (a,b); the 1x1 logits conv commutes with the depth-to-space, so
         it runs per group and ``seam_mask_select_f32`` reads the 28x28 map straight out of it."""
         dt = cdt(self)
-        key = _key(self.parameters(), dt)
+        twin = (dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True) and "mdeconv" in SPLIT_CLASSES
+                and SPLIT_DTYPE == ops.SX6)
+        key = _key(self.parameters(), dt) + (twin,)
         if self._pk is None or key != self._pk_key:
             with torch.no_grad():
-                self._pk = (ops.pack_conv(self.conv5_mask.weight, self.conv5_mask.bias, transposed2x2=True, dtype=dt),
+                # (class ``mdeconv``: the split twin of the transposed conv's matrix beside its exact pack, taken under ``split_on``)
+                self._pk = (ops.pack_conv(self.conv5_mask.weight, self.conv5_mask.bias, transposed2x2=True, dtype=(dt, ops.SX6) if twin else (dt,)),
                             ops.pack_conv(self.mask_fcn_logits.weight, self.mask_fcn_logits.bias, dtype=dt))
             self._pk_key = key
-        up, logits = self._pk
+        ups, logits = self._pk
+        up = ups[1] if twin and split_on(self) else ups[0]
         k = x.shape[0]
         y = ops.conv2d(x, up, relu=True)                                  # [K,14,14,4*256]
         o = ops.linear(y.view(k * 14 * 14 * 4, -1), logits)              # [K*196*4, ncls]

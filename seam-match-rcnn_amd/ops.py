@@ -101,6 +101,8 @@ PWHPC_MIN_C = int(_os.environ.get("SEAM_PWHPC_MIN_C", "1024"))  # reductions fro
 # persistent blocks' long tiles lose to the implicit GEMM's smaller ones (196 tiles: 1.16x, 100 tiles: 0.87x, 40 tiles: 0.66x;
 # profiles/sxpc_layer_ab.txt).  SXPC_RULE = False: every supported shape (tests, tools/sxpc_ab.py).  The two-source form
 # (conv1x1_sxpc_dual, ``conv2d_dual`` on an SX6 pack) has no tile rule: it wins from one image on (profiles/sxpc_dual_layer_ab.txt).
+# The upsampled-residual form (conv1x1_sxpc_up, ``conv2d_topdown`` on an SX6 pack) follows the tile rule: below it the un-fused
+# conv_igemm_sx + upsample_add_ gives the same bits (profiles/sxpc_up_layer_ab.txt: the losing shapes have 10-50 tiles).
 SXPC = _os.environ.get("SEAM_SXPC", "1") != "0"
 SXPC_MIN_TILES = int(_os.environ.get("SEAM_SXPC_MIN_TILES", "196"))
 SXPC_RULE = True
@@ -283,7 +285,11 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
     bn:     optional (weight, bias, running_mean, running_var) folded into the epilogue:
             FrozenBatchNorm2d [TV] / BatchNorm1d eval (ref models/match_head.py:62).
     wino:   also pack Winograd F(2x2,3x3) weights for fp32 stride-1 3x3 layers (the inference path); the grad-enabled
-            pass of the heads (autograd.py) packs per step and keeps the bit-exact fp32 fma chain of the implicit GEMM."""
+            pass of the heads (autograd.py) packs per step and keeps the bit-exact fp32 fma chain of the implicit GEMM.
+    dtype:  a tuple yields a tuple of packs of the ONE source (an exact pack and its split twin: the same shift tensor)."""
+    if isinstance(dtype, tuple):
+        return tuple(pack_conv(weight, bias, bn, stride=stride, pad=pad, cstore=cstore, transposed2x2=transposed2x2, bn_eps=bn_eps,
+                               dtype=d, wino=wino) for d in dtype)
     lib = _native.lib()
     weight = _req(weight.detach(), name="weight")
     is_linear = not transposed2x2 and weight.dim() == 2      # a Linear runs on 1x1 maps: no weight form of the map-sized pointwise kernels
@@ -325,7 +331,8 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         tmp = torch.empty((rows, kred), dtype=F32, device=weight.device)
         _native.check(lib.seam_pack_conv_weight_sx(_ptr(weight), _ptr(wp), _ptr(tmp), K, cin, R, S, cs, mode, _stream()),
                       "seam_pack_conv_weight_sx")
-        if SXPC and dtype == SX6 and conv1x1 and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K):
+        # (a 2x2 / stride-2 transposed conv is the 1x1 conv of its [4 Cout, Cin] matrix: the same form)
+        if SXPC and dtype == SX6 and (conv1x1 or (plain and transposed2x2)) and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K):
             wx = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
             _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(rows_kc()), _ptr(wx), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc")
     else:
@@ -664,10 +671,19 @@ def stem_s2d_f16(x: torch.Tensor, w_rows: torch.Tensor, scale: Optional[torch.Te
     return y
 
 
+def _sxpc_up_ok(lib, pc: "PackedConv", n, h, w, c, tn, th, tw, tk) -> bool:
+    """``conv2d_topdown`` on an SX6 pack with ``wx`` takes ``seam_conv1x1_sxpc_up``: integers, the knobs and the library's host
+    predicate only -- no tensor data, no stream."""
+    return bool(SXPC and c == pc.Cstore and pc.R == 1 and pc.S == 1 and pc.stride == 1 and pc.pad == 0 and tn == n and tk == pc.K
+                and (-(-(n * h * w) // 128) * (pc.K // 128) >= SXPC_MIN_TILES or not SXPC_RULE)
+                and lib.seam_conv1x1_sxpc_up_supported(n * h * w, n, h, w, c, pc.K, th, tw) == 1)
+
+
 def conv2d_topdown(x: torch.Tensor, pc: PackedConv, top: torch.Tensor) -> torch.Tensor:
     """FPN top-down merge [TV]: conv(x) + nearest-upsample(top) -> NHWC.  Exact-fp32 weights: ONE launch (the coarse map is
-    added in the conv epilogue, ``seam_conv2d_upres_f32``); other precisions: conv + ``upsample_add_``.  Both forms round
-    identically."""
+    added in the conv epilogue, ``seam_conv2d_upres_f32``); a split-bf16 (SX6) pack with ``wx``: ONE launch of
+    ``seam_conv1x1_sxpc_up`` when the launch has at least ``SXPC_MIN_TILES`` tiles; other precisions: conv + ``upsample_add_``.
+    The fused and un-fused forms round identically."""
     if (pc.dtype == F16 and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and _swh_ok(pc, x.shape[1], x.shape[2])
             and x.shape[1] * x.shape[2] >= 128 and top.dim() == 4 and top.shape[0] == x.shape[0] and top.shape[3] == pc.K):
         # fp16 path (round 6): the merge in the streaming pointwise kernel's epilogue -- the lateral is never written and re-read
@@ -686,6 +702,21 @@ def conv2d_topdown(x: torch.Tensor, pc: PackedConv, top: torch.Tensor) -> torch.
         if tr:
             _trace_end(tr)
         return y
+    if pc.dtype == SX6 and pc.wx is not None and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and top.dim() == 4:
+        # split-bf16 lateral: the merge in conv1x1_sxpc's epilogue (csrc/seam_pwsx.hip conv1x1_sxpc_up).  The un-fused form below
+        # gives the same bits, so the rule may look at the batch.
+        n, h, w, c = x.shape
+        if _sxpc_up_ok(_native.lib(), pc, n, h, w, c, top.shape[0], top.shape[1], top.shape[2], top.shape[3]):
+            x, top = _req(x, F32, "x"), _req(top, F32, "top")
+            y = torch.empty((n, h, w, pc.K), dtype=F32, device=x.device)
+            tr = CONV_TRACE is not None and _trace_begin(
+                "conv1x1_sxpc_up", 2.0 * n * h * w * pc.K * (pc.Cin or pc.Cstore), (n, h, w, c, pc.K, 1, 1),
+                float(4 * (x.numel() + pc.K * c + y.numel() + top.numel())))
+            _native.check(_native.lib().seam_conv1x1_sxpc_up(_ptr(x), _ptr(pc.wx), _ptr(pc.scale), _ptr(pc.shift), _ptr(top), _ptr(y), n, h, w, c,
+                                                             pc.K, top.shape[1], top.shape[2], 0, _stream()), "seam_conv1x1_sxpc_up")
+            if tr:
+                _trace_end(tr)
+            return y
     if pc.dtype != F32 or pc.K % 4:
         return upsample_add_(conv2d(x, pc), top)
     x = _req(x, None, "x")
