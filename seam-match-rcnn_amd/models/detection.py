@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import ops
+from .packed import PackedWeights
 
 RESNET50_LAYERS = ((3, 64, 1), (4, 128, 2), (6, 256, 2), (3, 512, 2))
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)
@@ -34,10 +35,6 @@ NMS_MAX_BOXES = 16384     # per-image capacity of seam_nms_sorted_f32 (csrc/seam
 
 
 import os as _os
-
-
-def _key(params, dtype=None) -> tuple:
-    return tuple((p.data_ptr(), p._version) for p in params) + (dtype,)
 
 
 def cdt(module):
@@ -76,6 +73,19 @@ def split_on(module) -> bool:
     training mode keeps the exact kernels under no_grad too: its plain forward stays the bits of its taped forward.)"""
     return (SPLIT_F32 and getattr(module, "split_f32", True) and cdt(module) == torch.float32 and not module.training
             and not torch.is_grad_enabled())
+
+
+def split_twin(module, cls) -> bool:
+    """A split twin of class ``cls`` is packed beside this module's exact pack: the pack-time half of ``split_on``, and the only
+    place that reads the compute dtype, SPLIT_F32, ``split_f32``, SPLIT_CLASSES and SPLIT_DTYPE together.  (The geometry
+    thresholds SPLIT_C3_MIN_C / SPLIT_C3DS_MIN_C are per layer and stay where the layer is packed.)"""
+    return bool(cdt(module) == torch.float32 and SPLIT_F32 and getattr(module, "split_f32", True) and cls in SPLIT_CLASSES
+                and (SPLIT_DTYPE == ops.SX6 or cls in ("c1", "c2s2", "c3")))
+
+
+def pick_pack(module, exact, twin=None):
+    """The pack a call runs on: the split twin when one was packed and ``split_on(module)`` holds, else the exact pack."""
+    return twin if twin is not None and split_on(module) else exact
 
 
 def set_split_f32(model: nn.Module, on: bool) -> nn.Module:
@@ -214,7 +224,9 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
 
-class ResNet50Body(nn.Module):
+class ResNet50Body(PackedWeights, nn.Module):
+    SPLIT_TWINS = ("c1", "c2s2", "c3", "c3ds")
+
     def __init__(self):
         super().__init__()
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
@@ -226,70 +238,60 @@ class ResNet50Body(nn.Module):
                 blocks.append(Bottleneck(inpl, planes, stride if bi == 0 else 1, bi == 0))
                 inpl = planes * 4
             setattr(self, f"layer{li}", nn.Sequential(*blocks))
-        self._pk, self._pk_key = None, None
         # opt-in: ``forward_taped`` tapes the stem (conv1 + ReLU + max-pool) when conv1.weight requires a gradient; off, such a
         # weight is refused.  The stem tape is the largest activation of the network (N x H/2 x W/2 x 64 fp32).
         self.train_stem = False
 
-    def _all(self):
-        return list(self.parameters()) + list(self.buffers())
-
     def _pack_tensors(self):
-        return self._all()
+        """Every parameter and buffer (the FrozenBN vectors), in one walk of the module tree: this runs on every forward."""
+        return [t for m in self.modules() for t in (*m._parameters.values(), *m._buffers.values()) if t is not None]
 
-    def _pack_key(self):
-        """What ``packed()`` caches under: pointer and version of every parameter and buffer, the compute dtype, the split switch."""
-        dt = cdt(self)
-        return _key(self._all(), dt) + (dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True),)
+    def _pack_switches(self):
+        return (cdt(self), SPLIT_DTYPE, FUSE_SHORTCUT, STEM_SWH) + tuple(split_twin(self, c) for c in self.SPLIT_TWINS)
 
-    def packed(self):
+    def _build_packs(self):
         dt = cdt(self)
-        sx = dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True)
-        key = self._pack_key()
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                pk = {"stem": ops.pack_conv(self.conv1.weight, None, self.bn1.tensors(), stride=2, pad=3,
-                                            cstore=8 if dt == torch.float16 else 4, bn_eps=self.bn1.eps, dtype=dt)}
-                if dt in (torch.float32, torch.float16):
-                    # w'[k, (dy*2+dx)*3 + c, r', s'] = w[k, c, 2r'+dy-1, 2s'+dx-1]  (zero where the 7x7 kernel has no tap)
-                    def s2d_weight():
-                        w8 = F.pad(self.conv1.weight.detach().to(torch.float32), (1, 0, 1, 0))      # [64,3,8,8], index 0 = tap -1
-                        return w8.view(64, 3, 4, 2, 4, 2).permute(0, 3, 5, 1, 2, 4).reshape(64, 12, 4, 4).contiguous()
-                    ws = ops.derived_source(s2d_weight, (self.conv1.weight,))
-                    pk["stem_s2d"] = ops.pack_conv(ws, None, self.bn1.tensors(), stride=1, pad=2, cstore=12 if dt == torch.float32 else 16,
-                                                   bn_eps=self.bn1.eps, wino=False, dtype=dt)
-                    if dt == torch.float16 and STEM_SWH:
-                        # the streaming form of the fp16 stem (ops.stem_s2d_f16): rows [64, (r, s, 16 channels)] of the same weights
-                        pk["stem_rows"] = F.pad(ws, (0, 0, 0, 0, 0, 4)).permute(0, 2, 3, 1).reshape(64, 256).to(torch.float16).contiguous()
-                for li in range(1, 5):
-                    for bi, b in enumerate(getattr(self, f"layer{li}")):
-                        e = {"c1": ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=dt),
-                             "c2": ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=b.stride, pad=1,
-                                                 bn_eps=b.bn2.eps, dtype=dt),
-                             "c3": ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=dt)}
-                        if b.downsample is not None:
-                            e["ds"] = ops.pack_conv(b.downsample[0].weight, None, b.downsample[1].tensors(),
-                                                    stride=b.stride, bn_eps=b.downsample[1].eps, dtype=dt)
-                            if dt in (torch.float32, torch.float16) and FUSE_SHORTCUT:     # conv3 + projection shortcut as one GEMM
-                                # (its split twin is packed beside it from the SAME folded matrix: one derived source for PackPlan)
-                                twin = (sx and "c3ds" in SPLIT_CLASSES and SPLIT_DTYPE == ops.SX6
-                                        and b.conv3.in_channels + b.downsample[0].in_channels >= SPLIT_C3DS_MIN_C)
-                                packs = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight, b.downsample[1].tensors(),
-                                                           bn_eps=b.bn3.eps, dtype=(dt, ops.SX6) if twin else (dt,))
-                                e["c3ds"] = packs[0]
-                                if twin:
-                                    e["c3dsx"] = packs[1]
-                        if sx:      # split twins of the exact packs (the exact ones stay: the switch and the grad-enabled walk use them)
-                            if "c1" in SPLIT_CLASSES:
-                                e["c1x"] = ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=SPLIT_DTYPE)
-                            if "c2s2" in SPLIT_CLASSES and b.stride == 2:
-                                e["c2x"] = ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=2, pad=1, bn_eps=b.bn2.eps,
-                                                         dtype=SPLIT_DTYPE)
-                            if "c3" in SPLIT_CLASSES and "c3ds" not in e and b.conv3.in_channels >= SPLIT_C3_MIN_C:
-                                e["c3x"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=SPLIT_DTYPE)
-                        pk[(li, bi)] = e
-            self._pk, self._pk_key = pk, key
-        return self._pk
+        c1x, c2x, c3x, c3dsx = (split_twin(self, c) for c in self.SPLIT_TWINS)
+        pk = {"stem": ops.pack_conv(self.conv1.weight, None, self.bn1.tensors(), stride=2, pad=3,
+                                    cstore=8 if dt == torch.float16 else 4, bn_eps=self.bn1.eps, dtype=dt)}
+        if dt in (torch.float32, torch.float16):
+            # w'[k, (dy*2+dx)*3 + c, r', s'] = w[k, c, 2r'+dy-1, 2s'+dx-1]  (zero where the 7x7 kernel has no tap)
+            def s2d_weight():
+                w8 = F.pad(self.conv1.weight.detach().to(torch.float32), (1, 0, 1, 0))      # [64,3,8,8], index 0 = tap -1
+                return w8.view(64, 3, 4, 2, 4, 2).permute(0, 3, 5, 1, 2, 4).reshape(64, 12, 4, 4).contiguous()
+            ws = ops.derived_source(s2d_weight, (self.conv1.weight,))
+            pk["stem_s2d"] = ops.pack_conv(ws, None, self.bn1.tensors(), stride=1, pad=2, cstore=12 if dt == torch.float32 else 16,
+                                           bn_eps=self.bn1.eps, wino=False, dtype=dt)
+            if dt == torch.float16 and STEM_SWH:
+                # the streaming form of the fp16 stem (ops.stem_s2d_f16): rows [64, (r, s, 16 channels)] of the same weights
+                pk["stem_rows"] = F.pad(ws, (0, 0, 0, 0, 0, 4)).permute(0, 2, 3, 1).reshape(64, 256).to(torch.float16).contiguous()
+        for li in range(1, 5):
+            for bi, b in enumerate(getattr(self, f"layer{li}")):
+                e = {"c1": ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=dt),
+                     "c2": ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=b.stride, pad=1,
+                                         bn_eps=b.bn2.eps, dtype=dt),
+                     "c3": ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=dt)}
+                if b.downsample is not None:
+                    e["ds"] = ops.pack_conv(b.downsample[0].weight, None, b.downsample[1].tensors(),
+                                            stride=b.stride, bn_eps=b.downsample[1].eps, dtype=dt)
+                    if dt in (torch.float32, torch.float16) and FUSE_SHORTCUT:     # conv3 + projection shortcut as one GEMM
+                        # (its split twin is packed beside it from the SAME folded matrix: one derived source for PackPlan)
+                        twin = c3dsx and b.conv3.in_channels + b.downsample[0].in_channels >= SPLIT_C3DS_MIN_C
+                        packs = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight, b.downsample[1].tensors(),
+                                                   bn_eps=b.bn3.eps, dtype=(dt, ops.SX6) if twin else (dt,))
+                        e["c3ds"] = packs[0]
+                        if twin:
+                            e["c3dsx"] = packs[1]
+                # split twins of the exact packs (the exact ones stay: the switch and the grad-enabled walk use them)
+                if c1x:
+                    e["c1x"] = ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=SPLIT_DTYPE)
+                if c2x and b.stride == 2:
+                    e["c2x"] = ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=2, pad=1, bn_eps=b.bn2.eps,
+                                             dtype=SPLIT_DTYPE)
+                if c3x and "c3ds" not in e and b.conv3.in_channels >= SPLIT_C3_MIN_C:
+                    e["c3x"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=SPLIT_DTYPE)
+                pk[(li, bi)] = e
+        return pk
 
     def forward(self, x: torch.Tensor, s2d_padded: bool = False, taped: bool = False) -> List[torch.Tensor]:
         """x NHWC4 [N,H,W,4] (or the space-to-depth frame [N,H/2,W/2,12|16]; ``s2d_padded``: the fp16 frame with its 2 + 1 zero
@@ -343,19 +345,18 @@ class ResNet50Body(nn.Module):
 
     def _run(self, x, pk, outs, s2d_padded=False):
         x = self._stem(x, pk, s2d_padded)
-        sx = split_on(self)
         feats = []
         for li in range(1, 5):
             nblk = len(getattr(self, f"layer{li}"))
             for bi in range(nblk):
                 e = pk[(li, bi)]
-                o = ops.conv2d(x, e.get("c1x", e["c1"]) if sx else e["c1"], relu=True)
-                o = ops.conv2d(o, e.get("c2x", e["c2"]) if sx else e["c2"], relu=True)
+                o = ops.conv2d(x, pick_pack(self, e["c1"], e.get("c1x")), relu=True)
+                o = ops.conv2d(o, pick_pack(self, e["c2"], e.get("c2x")), relu=True)
                 if "c3ds" in e:       # projection-shortcut block: bn3(conv3(o)) + bn_d(conv_d(x)) + ReLU in one launch
-                    x = ops.conv2d_dual(o, x, e.get("c3dsx", e["c3ds"]) if sx else e["c3ds"], getattr(self, f"layer{li}")[bi].stride, relu=True)
+                    x = ops.conv2d_dual(o, x, pick_pack(self, e["c3ds"], e.get("c3dsx")), getattr(self, f"layer{li}")[bi].stride, relu=True)
                     continue
                 idt = ops.conv2d(x, e["ds"]) if "ds" in e else x
-                x = ops.conv2d(o, e.get("c3x", e["c3"]) if sx else e["c3"], relu=True, residual=idt,   # bn3 + add + ReLU fused
+                x = ops.conv2d(o, pick_pack(self, e["c3"], e.get("c3x")), relu=True, residual=idt,   # bn3 + add + ReLU fused
                                out=outs[li - 1] if (outs is not None and bi == nblk - 1) else None)
             feats.append(x)
         return feats
@@ -450,12 +451,11 @@ def _side_stream(dev):
     return st
 
 
-class FeaturePyramidNetwork(nn.Module):
+class FeaturePyramidNetwork(PackedWeights, nn.Module):
     def __init__(self, in_channels=(256, 512, 1024, 2048), out_channels=256):
         super().__init__()
         self.inner_blocks = nn.ModuleList([nn.Conv2d(c, out_channels, 1) for c in in_channels])
         self.layer_blocks = nn.ModuleList([nn.Conv2d(out_channels, out_channels, 3, padding=1) for _ in in_channels])
-        self._pk, self._pk_key = None, None
 
     def _load_from_state_dict(self, state_dict, prefix, *a, **k):
         # torchvision >= 0.13 wraps the convs in Conv2dNormActivation: ``inner_blocks.{i}.0.weight``
@@ -465,34 +465,21 @@ class FeaturePyramidNetwork(nn.Module):
                 state_dict[prefix + ".".join((parts[0], parts[1], parts[3]))] = state_dict.pop(key)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
-    def _pack_tensors(self):
-        return list(self.parameters())
+    def _pack_switches(self):
+        return (cdt(self), split_twin(self, "lat"))
 
-    def _split_twins(self) -> bool:
-        return (cdt(self) == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True) and "lat" in SPLIT_CLASSES
-                and SPLIT_DTYPE == ops.SX6)
-
-    def _pack_key(self):
-        return _key(self.parameters(), cdt(self)) + (self._split_twins(),)
-
-    def packed(self):
+    def _build_packs(self):
         """(lateral packs, output packs, split twins of the lateral packs or None): the twins (class ``lat``) are packed beside the
         exact packs from the same parameters; ``forward`` takes them under ``split_on``, ``forward_taped`` never does."""
-        dt = cdt(self)
-        key = self._pack_key()
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                inner = [ops.pack_conv(m.weight, m.bias, dtype=(dt, ops.SX6) if self._split_twins() else (dt,)) for m in self.inner_blocks]
-                self._pk = ([p[0] for p in inner],
-                            [ops.pack_conv(m.weight, m.bias, pad=1, dtype=dt) for m in self.layer_blocks],
-                            [p[1] for p in inner] if self._split_twins() else None)
-            self._pk_key = key
-        return self._pk
+        dt, twin = cdt(self), split_twin(self, "lat")
+        inner = [ops.pack_conv(m.weight, m.bias, dtype=(dt, ops.SX6) if twin else (dt,)) for m in self.inner_blocks]
+        return ([p[0] for p in inner],
+                [ops.pack_conv(m.weight, m.bias, pad=1, dtype=dt) for m in self.layer_blocks],
+                [p[1] for p in inner] if twin else None)
 
     def forward(self, feats: List[torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
         inner, layer, twins = self.packed()
-        if twins is not None and split_on(self):
-            inner = twins
+        inner = pick_pack(self, inner, twins)
         x3 = feats[3]
         if not (LEVEL_STREAMS and x3.is_cuda):
             last = ops.conv2d(x3, inner[3])
@@ -585,14 +572,13 @@ def resnet_fpn_backbone(backbone_name="resnet50", pretrained=False, trainable_la
 
 
 # ------------------------------------------------------------------------------ RPN (a5)
-class RPNHead(nn.Module):
+class RPNHead(PackedWeights, nn.Module):
     def __init__(self, in_channels=256, num_anchors=3):
         super().__init__()
         self.conv = nn.Conv2d(in_channels, in_channels, 3, padding=1)
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, 1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, 1)
         self.num_anchors = num_anchors
-        self._pk, self._pk_key = None, None
 
     def _load_from_state_dict(self, state_dict, prefix, *a, **k):
         old = prefix + "conv.0.0."           # torchvision >= 0.13 layout
@@ -601,25 +587,14 @@ class RPNHead(nn.Module):
                 state_dict[prefix + "conv." + s] = state_dict.pop(old + s)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
-    def _pack_tensors(self):
-        return list(self.parameters())
-
-    def _pack_key(self):
-        return _key(self.parameters(), cdt(self))
-
-    def packed(self):
+    def _build_packs(self):
         dt = cdt(self)
-        key = self._pack_key()
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                # A + 4A rows, one launch
-                w = ops.derived_source(lambda: torch.cat([self.cls_logits.weight, self.bbox_pred.weight], 0).detach(),
-                                       (self.cls_logits.weight, self.bbox_pred.weight))
-                b = ops.derived_source(lambda: torch.cat([self.cls_logits.bias, self.bbox_pred.bias], 0).detach(),
-                                       (self.cls_logits.bias, self.bbox_pred.bias))
-                self._pk = (ops.pack_conv(self.conv.weight, self.conv.bias, pad=1, dtype=dt), ops.pack_conv(w, b, dtype=dt))
-            self._pk_key = key
-        return self._pk
+        # A + 4A rows, one launch
+        w = ops.derived_source(lambda: torch.cat([self.cls_logits.weight, self.bbox_pred.weight], 0).detach(),
+                               (self.cls_logits.weight, self.bbox_pred.weight))
+        b = ops.derived_source(lambda: torch.cat([self.cls_logits.bias, self.bbox_pred.bias], 0).detach(),
+                               (self.cls_logits.bias, self.bbox_pred.bias))
+        return ops.pack_conv(self.conv.weight, self.conv.bias, pad=1, dtype=dt), ops.pack_conv(w, b, dtype=dt)
 
     def forward(self, feats: Sequence[torch.Tensor]):
         """-> per level ([N,H,W,A] objectness, [N,H,W,4A] deltas), NHWC == torchvision's
@@ -939,23 +914,17 @@ class MultiScaleRoIAlign(nn.Module):
 
 
 # ------------------------------------------------------------------------------ box branch (a6)
-class TwoMLPHead(nn.Module):
+class TwoMLPHead(PackedWeights, nn.Module):
     def __init__(self, in_channels=256 * 7 * 7, representation_size=1024):
         super().__init__()
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
-        self._pk, self._pk_key = None, None
 
-    def packed(self):
+    def _build_packs(self):
         dt = cdt(self)
-        key = _key(self.parameters(), dt)
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                # fc6 over flatten(C,7,7) == a 7x7 valid conv over the NHWC ROI tile
-                w6 = self.fc6.weight.view(self.fc6.out_features, 256, 7, 7)
-                self._pk = (ops.pack_conv(w6, self.fc6.bias, dtype=dt), ops.pack_conv(self.fc7.weight, self.fc7.bias, dtype=dt))
-            self._pk_key = key
-        return self._pk
+        # fc6 over flatten(C,7,7) == a 7x7 valid conv over the NHWC ROI tile
+        w6 = self.fc6.weight.view(self.fc6.out_features, 256, 7, 7)
+        return ops.pack_conv(w6, self.fc6.bias, dtype=dt), ops.pack_conv(self.fc7.weight, self.fc7.bias, dtype=dt)
 
     def forward(self, x):                        # NHWC [K,7,7,256] -> [K,1024]
         fc6, fc7 = self.packed()
@@ -963,28 +932,24 @@ class TwoMLPHead(nn.Module):
         return ops.linear(x, fc7, relu=True)
 
 
-class FastRCNNPredictor(nn.Module):
+class FastRCNNPredictor(PackedWeights, nn.Module):
     def __init__(self, in_channels=1024, num_classes=91):
         super().__init__()
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
         self.num_classes = num_classes
-        self._pk, self._pk_key = None, None
+
+    def _build_packs(self):
+        return ops.pack_conv(torch.cat([self.cls_score.weight, self.bbox_pred.weight], 0),
+                             torch.cat([self.cls_score.bias, self.bbox_pred.bias], 0), dtype=cdt(self))
 
     def forward(self, x):
-        dt = cdt(self)
-        key = _key(self.parameters(), dt)
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                self._pk = ops.pack_conv(torch.cat([self.cls_score.weight, self.bbox_pred.weight], 0),
-                                         torch.cat([self.cls_score.bias, self.bbox_pred.bias], 0), dtype=dt)
-            self._pk_key = key
-        o = ops.linear(x, self._pk, out_f32=True)
+        o = ops.linear(x, self.packed(), out_f32=True)
         return o[:, :self.num_classes], o[:, self.num_classes:]
 
 
 # ------------------------------------------------------------------------------ mask branch (a8)
-class MaskRCNNHeads(nn.Module):
+class MaskRCNNHeads(PackedWeights, nn.Module):
     def __init__(self, in_channels=256, layers=(256, 256, 256, 256)):
         super().__init__()
         c = in_channels
@@ -993,7 +958,6 @@ class MaskRCNNHeads(nn.Module):
             setattr(self, f"relu{i}", nn.ReLU(inplace=True))
             c = l
         self.n = len(layers)
-        self._pk, self._pk_key = None, None
 
     def _load_from_state_dict(self, state_dict, prefix, *a, **k):
         for i in range(self.n):              # torchvision >= 0.13: ``mask_head.{i}.0.weight``
@@ -1003,44 +967,41 @@ class MaskRCNNHeads(nn.Module):
                     state_dict[f"{prefix}mask_fcn{i + 1}.{s}"] = state_dict.pop(old)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
+    def _build_packs(self):
+        return [ops.pack_conv(getattr(self, f"mask_fcn{i}").weight, getattr(self, f"mask_fcn{i}").bias, pad=1,
+                              dtype=cdt(self)) for i in range(1, self.n + 1)]
+
     def forward(self, x):                        # NHWC [K,14,14,256]
-        dt = cdt(self)
-        key = _key(self.parameters(), dt)
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                self._pk = [ops.pack_conv(getattr(self, f"mask_fcn{i}").weight, getattr(self, f"mask_fcn{i}").bias, pad=1,
-                                          dtype=dt) for i in range(1, self.n + 1)]
-            self._pk_key = key
-        for pc in self._pk:
+        for pc in self.packed():
             x = ops.conv2d(x, pc, relu=True)
         return x
 
 
-class MaskRCNNPredictor(nn.Module):
+class MaskRCNNPredictor(PackedWeights, nn.Module):
     def __init__(self, in_channels=256, dim_reduced=256, num_classes=91):
         super().__init__()
         self.conv5_mask = nn.ConvTranspose2d(in_channels, dim_reduced, 2, 2, 0)
         self.relu = nn.ReLU(inplace=True)
         self.mask_fcn_logits = nn.Conv2d(dim_reduced, num_classes, 1, 1, 0)
         self.num_classes = num_classes
-        self._pk, self._pk_key = None, None
+
+    def _pack_switches(self):
+        return (cdt(self), split_twin(self, "mdeconv"))
+
+    def _build_packs(self):
+        """((exact pack of the transposed conv[, its split twin]), logits pack)"""
+        dt = cdt(self)
+        # (class ``mdeconv``: the split twin of the transposed conv's matrix beside its exact pack, taken under ``split_on``)
+        return (ops.pack_conv(self.conv5_mask.weight, self.conv5_mask.bias, transposed2x2=True,
+                              dtype=(dt, ops.SX6) if split_twin(self, "mdeconv") else (dt,)),
+                ops.pack_conv(self.mask_fcn_logits.weight, self.mask_fcn_logits.bias, dtype=dt))
 
     def forward(self, x):
         """NHWC [K,14,14,256] -> logits [K,14,14,4*ncls]: the 2x2/s2 transposed conv is a 1x1 conv to
         4 sub-pixel channel groups (a,b); the 1x1 logits conv commutes with the depth-to-space, so
         it runs per group and ``seam_mask_select_f32`` reads the 28x28 map straight out of it."""
-        dt = cdt(self)
-        twin = (dt == torch.float32 and SPLIT_F32 and getattr(self, "split_f32", True) and "mdeconv" in SPLIT_CLASSES
-                and SPLIT_DTYPE == ops.SX6)
-        key = _key(self.parameters(), dt) + (twin,)
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                # (class ``mdeconv``: the split twin of the transposed conv's matrix beside its exact pack, taken under ``split_on``)
-                self._pk = (ops.pack_conv(self.conv5_mask.weight, self.conv5_mask.bias, transposed2x2=True, dtype=(dt, ops.SX6) if twin else (dt,)),
-                            ops.pack_conv(self.mask_fcn_logits.weight, self.mask_fcn_logits.bias, dtype=dt))
-            self._pk_key = key
-        ups, logits = self._pk
-        up = ups[1] if twin and split_on(self) else ups[0]
+        ups, logits = self.packed()
+        up = pick_pack(self, *ups)
         k = x.shape[0]
         y = ops.conv2d(x, up, relu=True)                                  # [K,14,14,4*256]
         o = ops.linear(y.view(k * 14 * 14 * 4, -1), logits)              # [K*196*4, ncls]

@@ -25,6 +25,7 @@ from torch import nn
 
 from .. import ops
 from .nlb import NONLocalBlock1D
+from .packed import PackedWeights
 
 
 def _wants_tape(module: nn.Module, *tensors) -> bool:
@@ -100,7 +101,7 @@ def device_plan(types_c: torch.Tensor, ids_c: torch.Tensor, dev: torch.device):
     return plan
 
 
-class MatchPredictor(nn.Module):
+class MatchPredictor(PackedWeights, nn.Module):
     def __init__(self):
         super().__init__()
         self.conv_seq = nn.Sequential(nn.Conv2d(256, 256, 3), nn.ReLU(),
@@ -110,23 +111,22 @@ class MatchPredictor(nn.Module):
         self.pool = nn.Sequential(nn.AvgPool2d((6, 6)), nn.ReLU())
         self.linear = nn.Sequential(nn.Linear(1024, 256), nn.BatchNorm1d(256))
         self.last = nn.Linear(256, 2)
-        self._trunk_pk = None
-        self._trunk_key = None
 
-    # ---- trunk: conv_seq -> pool -> linear(+BN) ---------------------------------------------------
-    def _packed_trunk(self):
+    # ---- trunk: conv_seq -> pool -> linear(+BN); the packs are the trunk's alone (``last`` and a subclass's heads read their own) ----
+    def _pack_tensors(self):
         bn = self.linear[1]
-        ps = [self.conv_seq[i].weight for i in (0, 2, 4, 6)] + [self.conv_seq[i].bias for i in (0, 2, 4, 6)] + [
+        return [self.conv_seq[i].weight for i in (0, 2, 4, 6)] + [self.conv_seq[i].bias for i in (0, 2, 4, 6)] + [
             self.linear[0].weight, self.linear[0].bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+
+    def _build_packs(self):
+        bn = self.linear[1]
         dt = getattr(self, "compute_dtype", torch.float32)      # fp32 (exact) | fp16 MFMA trunk (config 5)
-        key = tuple((p.data_ptr(), p._version) for p in ps) + (dt,)
-        if self._trunk_pk is None or key != self._trunk_key:
-            with torch.no_grad():
-                convs = [ops.pack_conv(self.conv_seq[i].weight, self.conv_seq[i].bias, dtype=dt) for i in (0, 2, 4, 6)]
-                lin = ops.pack_conv(self.linear[0].weight, self.linear[0].bias,
-                                    (bn.weight, bn.bias, bn.running_mean, bn.running_var), bn_eps=bn.eps, dtype=dt)
-            self._trunk_pk, self._trunk_key = (convs, lin), key
-        return self._trunk_pk
+        convs = [ops.pack_conv(self.conv_seq[i].weight, self.conv_seq[i].bias, dtype=dt) for i in (0, 2, 4, 6)]
+        lin = ops.pack_conv(self.linear[0].weight, self.linear[0].bias,
+                            (bn.weight, bn.bias, bn.running_mean, bn.running_var), bn_eps=bn.eps, dtype=dt)
+        return convs, lin
+
+    _packed_trunk = PackedWeights.packed
 
     def trunk_nhwc(self, x: torch.Tensor) -> torch.Tensor:
         """x NHWC [K,14,14,256] -> x3 [K,256]   (ref :67-69 / :93-95)."""

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from .packed import PackedWeights
 
 
 class _ForwardOnly(torch.autograd.Function):
@@ -31,7 +32,7 @@ class _ForwardOnly(torch.autograd.Function):
                                   "(seam_nlb_block_bwd_f32 keeps a sequence in LDS); the forward result is valid")
 
 
-class _NonLocalBlockND(nn.Module):
+class _NonLocalBlockND(PackedWeights, nn.Module):
     def __init__(self, in_channels, inter_channels=None, dimension=3, sub_sample=True, bn_layer=True):
         super().__init__()
         assert dimension in [1, 2, 3]
@@ -56,32 +57,30 @@ class _NonLocalBlockND(nn.Module):
         self.theta = nn.Conv1d(in_channels, ic, 1)
         self.phi = nn.Conv1d(in_channels, ic, 1)
         self.concat_project = nn.Sequential(nn.Conv2d(ic * 2, 1, 1, 1, 0, bias=False), nn.ReLU())
-        self._pk = None
-        self._pk_key = None
 
     # ---- packed weights (rebuilt when a parameter is replaced or modified in place) -------------
     def packed(self, scorer: "nn.Linear | None" = None) -> ops.PackedNLB:
-        ps = [self.theta.weight, self.theta.bias, self.phi.weight, self.phi.bias, self.g.weight, self.g.bias,
-              self.W.weight, self.W.bias, self.concat_project[0].weight]
+        return super().packed(scorer)
+
+    def _pack_tensors(self, scorer):
+        return list(self.parameters()) + ([scorer.weight, scorer.bias] if scorer is not None else [])
+
+    def _pack_switches(self):
+        return ()       # the kernel is fp32 whatever the model's compute dtype
+
+    def _build_packs(self, scorer) -> ops.PackedNLB:
+        dev = self.W.weight.device
         if scorer is not None:
-            ps += [scorer.weight, scorer.bias]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._pk is None or key != self._pk_key:
-            with torch.no_grad():
-                dev = self.W.weight.device
-                if scorer is not None:
-                    wa, ba = scorer.weight.reshape(256).contiguous(), scorer.bias.reshape(1).contiguous()
-                else:
-                    wa, ba = torch.zeros(256, device=dev), torch.zeros(1, device=dev)
-                self._pk = ops.PackedNLB(
-                    w_proj_t=torch.cat([self.theta.weight[:, :, 0], self.phi.weight[:, :, 0], self.g.weight[:, :, 0]], 0)
-                    .t().contiguous(),
-                    b_proj=torch.cat([self.theta.bias, self.phi.bias, self.g.bias]).contiguous(),
-                    w_cat=self.concat_project[0].weight.reshape(256).contiguous(),
-                    w_out_t=self.W.weight[:, :, 0].t().contiguous(),
-                    b_out=self.W.bias.contiguous(), w_att=wa, b_att=ba)
-            self._pk_key = key
-        return self._pk
+            wa, ba = scorer.weight.reshape(256).contiguous(), scorer.bias.reshape(1).contiguous()
+        else:
+            wa, ba = torch.zeros(256, device=dev), torch.zeros(1, device=dev)
+        return ops.PackedNLB(
+            w_proj_t=torch.cat([self.theta.weight[:, :, 0], self.phi.weight[:, :, 0], self.g.weight[:, :, 0]], 0)
+            .t().contiguous(),
+            b_proj=torch.cat([self.theta.bias, self.phi.bias, self.g.bias]).contiguous(),
+            w_cat=self.concat_project[0].weight.reshape(256).contiguous(),
+            w_out_t=self.W.weight[:, :, 0].t().contiguous(),
+            b_out=self.W.bias.contiguous(), w_att=wa, b_att=ba)
 
     def forward(self, x):
         """x: (b, 256, t) -> z: (b, 256, t)      (ref models/nlb.py:66-101)"""

@@ -14,6 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _native
+from .models.packed import PackedWeights
 
 F32 = torch.float32
 F16 = torch.float16
@@ -2791,9 +2792,10 @@ class PackPlan:
 
     Built once: every covered module repacks by its own ``packed()`` under ``record_packs``, which yields, per pack, the source (a
     parameter, or a ``derived_source``) and the destination buffers.  ``rebuilds`` counts every later build.  ``refresh(updated)``
-      * checks on the host that the plan still describes the model (the same ``_pk`` objects, the same parameter / buffer pointers,
-        versions that moved by exactly the optimizer's one bump and only on updated parameters, the same compute dtype / split
-        switch); otherwise it drops everything and rebuilds by the modules' own route -- it never writes through a stale pointer;
+      * checks on the host that the plan still describes the model, by the two parts of ``models.packed.PackedWeights._pack_key``
+        (the same ``_pk`` objects; tensors: the same parameter / buffer pointers, versions that moved by exactly the optimizer's
+        one bump and only on updated parameters; switches: equal); otherwise it drops everything and rebuilds by the modules' own
+        route -- it never writes through a stale pointer;
       * recomputes the derived sources whose parameters moved (torch; counted in ``fallback_calls``);
       * rewrites every weight-dependent buffer of every pack whose source moved in ONE ``seam_repack_many_f32`` launch on the
         current stream (``launches_per_refresh``); epilogue vectors of a frozen BN and packs of frozen layers are not touched;
@@ -2810,7 +2812,7 @@ class PackPlan:
                 m = getattr(m, part, None)
                 if m is None:
                     break
-            if m is not None and hasattr(m, "packed") and hasattr(m, "_pack_key"):
+            if isinstance(m, PackedWeights):
                 self.modules.append((path, m))
         if not self.modules:
             raise ValueError("PackPlan: the model has none of " + ", ".join(self.COVERED))
@@ -2897,16 +2899,11 @@ class PackPlan:
         for (path, m), pk, old in zip(self.modules, self._pk, self._keys):
             if m._pk is not pk:
                 return False
-            new = m._pack_key()
-            if len(new) != len(old):
+            (old_tensors, old_switches), (new_tensors, new_switches) = old, m._pack_key()
+            if new_switches != old_switches or len(new_tensors) != len(old_tensors):      # compute dtype, split twins, pack-time knobs
                 return False
-            tensors = m._pack_tensors()
-            for i, (a, b) in enumerate(zip(old, new)):
-                if i >= len(tensors):
-                    if a != b:              # compute dtype, split switch
-                        return False
-                    continue
-                bump = 1 if id(tensors[i]) in updated else 0
+            for t, a, b in zip(m._pack_tensors(), old_tensors, new_tensors):
+                bump = 1 if id(t) in updated else 0
                 if a[0] != b[0] or a[1] + bump != b[1]:
                     return False
         return True

@@ -210,6 +210,39 @@ def test_switch_restores_the_exact_kernels():
         assert torch.equal(a, c) and torch.equal(b, c)
 
 
+@gpu
+def test_the_body_repacks_when_a_pack_time_knob_moves():
+    """Packs only, no forward: ``packed()`` follows SPLIT_CLASSES and FUSE_SHORTCUT by its key, nobody drops ``_pk`` by hand."""
+    from seam_match_rcnn_amd.models import detection as det
+    body = det.ResNet50Body().to(DEV).eval()
+    blocks = lambda pk: {key: e for key, e in pk.items() if isinstance(key, tuple)}
+    having = lambda pk, name: [key for key, e in blocks(pk).items() if name in e]
+    classes, fuse = det.SPLIT_CLASSES, det.FUSE_SHORTCUT
+    assert {"c1", "c2s2", "c3", "c3ds"} <= classes and fuse
+    try:
+        first = body.packed()
+        assert "c1x" in first[(2, 1)] and "c3ds" in first[(2, 0)] and "c3dsx" in first[(2, 0)]
+        c3x, c2x = having(first, "c3x"), having(first, "c2x")
+        assert c3x and c2x
+        det.SPLIT_CLASSES = classes - {"c1"}
+        without = body.packed()
+        assert without is not first and not having(without, "c1x")
+        assert having(without, "c3x") == c3x and having(without, "c2x") == c2x
+        det.SPLIT_CLASSES = classes
+        again = body.packed()
+        assert again is not without and "c1x" in again[(2, 1)] and len(having(again, "c1x")) == 16
+        det.FUSE_SHORTCUT = False
+        unfused = body.packed()
+        assert unfused is not again and not having(unfused, "c3ds") and not having(unfused, "c3dsx")
+        assert "ds" in unfused[(2, 0)] and "c1x" in unfused[(2, 1)]
+        det.FUSE_SHORTCUT = fuse
+        fused = body.packed()
+        assert fused is not unfused and "c3ds" in fused[(2, 0)] and "c3dsx" in fused[(2, 0)]
+        assert body.packed() is fused
+    finally:
+        det.SPLIT_CLASSES, det.FUSE_SHORTCUT = classes, fuse
+
+
 def test_header_exports_and_signatures_agree():
     from seam_match_rcnn_amd import _native
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "seam_hip.h")).read(), flags=re.S)

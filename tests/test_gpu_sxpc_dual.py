@@ -371,14 +371,12 @@ def test_model_level_switches():
             ops.SXPC = flag
             assert same(on, off)
             det.SPLIT_CLASSES = classes - {"c3ds"}
-            body._pk = None
             without, trace = traced(body, x)
             assert not any("c3dsx" in e for key, e in body.packed().items() if isinstance(key, tuple))
             assert not any(t[0] == "conv1x1_sxpc_dual" for t in trace)
             assert sum(t[0].startswith("conv_igemm<float") and t[4][3] in (384, 768, 1536) for t in trace) == 3
             assert same(without, before)
             det.SPLIT_CLASSES = classes
-            body._pk = None
             det.set_split_f32(body, False)
             exact, trace = traced(body, x)
             assert not any(t[0].startswith(("conv1x1_sxpc", "conv_igemm_sx")) for t in trace)
