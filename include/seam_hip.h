@@ -194,6 +194,45 @@ int seam_conv1x1_sxpc_up_supported(long long M, int N, int Ho, int Wo, int C, in
 int seam_conv1x1_sxpc_up(const float* x, const void* w_packed, const float* scale, const float* shift, const float* top, float* y,
                          int N, int Ho, int Wo, int C, int K, int rH, int rW, int relu, seam_stream_t stream);
 
+/* conv1x1_sxpc64 (csrc/seam_pwsx.hip): the same kernel for 64 output channels -- torchvision's Bottleneck.conv1 of layer1
+ * (256 -> 64) and the base of the stem below.  A tile is 128 pixels x 64 channels; the four consumer waves own 32 channels x 64
+ * pixels each.  Arithmetic and epilogue are seam_conv1x1_sxpc's: the bits of seam_conv2d_sx with terms = 6.
+ *   _supported: 1 when K == 64, C >= 128 and a multiple of 64, M >= 1, else 0 (one chunk per tile, C == 64, is refused);
+ *   seam_pack_conv1x1_weight_sxpc64: w [64, C] fp32 row-major -> [2][C/16][3 planes][64 lanes][8 bf16], 6 K C bytes
+ *   (seam_conv1x1_sxpc_weight_bytes);
+ *   seam_conv1x1_sxpc64: y[M, 64] = act(scale * (x[M, C] . w^T) + shift + residual); relu 0 | 1; a shape that is not supported
+ *   returns hipErrorInvalidValue and launches nothing. */
+int seam_conv1x1_sxpc64_supported(long long M, int C, int K);
+int seam_pack_conv1x1_weight_sxpc64(const float* w, void* w_packed, int K, int C, seam_stream_t stream);
+int seam_conv1x1_sxpc64(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                        long long M, int C, int K, int relu, seam_stream_t stream);
+
+/* The `short` entries (csrc/seam_pwsx.hip): the kernels of seam_conv1x1_sxpc and seam_conv1x1_sxpc_dual on reductions of two
+ * chunks, which the entries above refuse: C == 128 (torchvision's Bottleneck.conv3 of layer2, 128 -> 512 + residual) and
+ * C1 == C2 == 64 on one map (layer1.0's conv3 + projection shortcut, stride2 == 1).  K a multiple of 128, M >= 1; the bits are those
+ * of seam_conv2d_sx with terms = 6 (on the concatenated rows).  The pack is seam_pack_conv1x1_weight_sxpc's layout, 6 K C bytes.
+ * Anything else returns hipErrorInvalidValue and launches nothing. */
+int seam_conv1x1_sxpc_short_supported(long long M, int C, int K);
+int seam_pack_conv1x1_weight_sxpc_short(const float* w, void* w_packed, int K, int C, seam_stream_t stream);
+int seam_conv1x1_sxpc_short(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                            long long M, int C, int K, int relu, seam_stream_t stream);
+int seam_conv1x1_sxpc_dual_short_supported(long long M, int C1, int C2, int K);
+int seam_conv1x1_sxpc_dual_short(const float* x1, const float* x2, const void* w_packed, const float* scale, const float* shift, float* y,
+                                 int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int K, int relu, seam_stream_t stream);
+
+/* stem_sxpc (csrc/seam_pwsx.hip): torchvision's ResNet stem, conv1 (7x7 / stride 2 / pad 3) + FrozenBatchNorm2d + ReLU, in its
+ * space-to-depth form -- the 4x4 / stride-1 convolution over the 12-channel frame -- as the gather form of conv1x1_sxpc64: an
+ * output pixel's reduction is its 4 x 4 window of cells, 4 tap rows of 48 contiguous floats, three chunks of 64.  xp is the frame
+ * with its zero cells, [N, Hs + 3, Ws + 3, 12] (2 before, 1 after in both directions); y [N, Hs, Ws, 64]; w_packed is
+ * seam_pack_conv1x1_weight_sxpc64 of the [64, 192] rows in (r, s, c) order.  The result is bit for bit seam_conv1x1_sxpc64 on the
+ * gathered [N Hs Ws, 192] rows.
+ *   _supported: 1 when N, Hs, Ws >= 1, N Hs Ws < 2^31, the division rules hold and the frames that one tile of 128 output pixels
+ *   touches lie within 2 GiB, else 0;
+ *   seam_stem_sxpc: a null frame, relu outside 0 | 1 or an unsupported geometry returns hipErrorInvalidValue and launches nothing. */
+int seam_stem_sxpc_supported(int N, int Hs, int Ws);
+int seam_stem_sxpc(const float* xp, const void* w_packed, const float* scale, const float* shift, float* y, int N, int Hs, int Ws,
+                   int relu, seam_stream_t stream);
+
 /* fp16 twin of seam_conv1x1_sw_f32 (csrc/seam_pwh.hip, round 6): the config-5 path's 1x1 layers [TV Bottleneck conv1 / conv3 /
  * stride-1 projection shortcut, FeaturePyramidNetwork.inner_blocks; behind models/video_matchrcnn.py:337] as a STREAMING kernel --
  * weights stationary in LDS, independent waves, 16-byte NHWC pieces in and out -- with the contract of seam_conv2d_f16 /
@@ -281,6 +320,10 @@ int seam_preprocess_s2d_batch_f16(const float* imgs, size_t img_stride, void* ou
 /* The same frame with pad_lo zero cells before and pad_hi after it in both directions: out [n, Hp/2 + pad_lo + pad_hi,
  * Wp/2 + pad_lo + pad_hi, 16] -- the input layout of seam_stem_s2d_swh_f16 (pad_lo 2, pad_hi 1: the 4x4 / pad-2 form of the stem). */
 int seam_preprocess_s2d_pad_batch_f16(const float* imgs, size_t img_stride, void* out, int n, int in_h, int in_w, int out_h,
+                                      int out_w, int Hp, int Wp, int pad_lo, int pad_hi, seam_stream_t stream);
+/* fp32 twin: out [n, Hp/2 + pad_lo + pad_hi, Wp/2 + pad_lo + pad_hi, 12] -- the input layout of seam_stem_sxpc (pad_lo 2, pad_hi 1);
+ * the interior is seam_preprocess_s2d_batch_f32's frame bit for bit. */
+int seam_preprocess_s2d_pad_batch_f32(const float* imgs, size_t img_stride, float* out, int n, int in_h, int in_w, int out_h,
                                       int out_w, int Hp, int Wp, int pad_lo, int pad_hi, seam_stream_t stream);
 
 /* Same transform fed by a uint8 HWC RGB frame [in_h,in_w,3]: fuses ToTensor (x/255, stuffs/transform.py:46-49)
@@ -1109,7 +1152,9 @@ int seam_sgd_step_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* 
  * n_blocks; it returns the launch's block count, or -(1 + k) when job k is refused.  The caller copies the table to the device
  * and passes that copy, the job count and the block count to seam_repack_many_f32. */
 enum { SEAM_REPACK_IGEMM = 0, SEAM_REPACK_WINO = 1, SEAM_REPACK_WINO24 = 2, SEAM_REPACK_PC = 3, SEAM_REPACK_SW = 4,
-       SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6, SEAM_REPACK_SXPC = 7 };
+       SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6, SEAM_REPACK_SXPC = 7,
+       SEAM_REPACK_SXPC64 = 8 /* the same item function for the shapes of seam_conv1x1_sxpc64_supported (K == 64) and of
+                                 seam_conv1x1_sxpc_short_supported (C == 128) */ };
 typedef struct {
     const float* src; void* dst; const float* scale;
     int64_t items;

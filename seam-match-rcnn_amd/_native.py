@@ -52,7 +52,7 @@ class SgdGroups(C.Structure):
     _fields_ = [("n", C.c_int), ("reserved", C.c_int * 3), ("g", SgdGroup * SGD_MAX_SLOTS)]
 
 
-REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC = range(8)     # SEAM_REPACK_*
+REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC, REPACK_SXPC64 = range(9)     # SEAM_REPACK_*
 
 
 class RepackJob(C.Structure):
@@ -86,6 +86,7 @@ SIGNATURES = {
     "seam_preprocess_s2d_batch_f32": (_i, [_p, C.c_size_t, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_preprocess_s2d_batch_f16": (_i, [_p, C.c_size_t, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_preprocess_s2d_pad_batch_f16": (_i, [_p, C.c_size_t, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_preprocess_s2d_pad_batch_f32": (_i, [_p, C.c_size_t, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv2d_dual_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv1x1_pc_supported": (_i, [C.c_longlong, _i, _i]),
     "seam_conv1x1_pc_weight_floats": (C.c_longlong, [_i, _i]),
@@ -106,6 +107,16 @@ SIGNATURES = {
     "seam_conv1x1_sxpc_dual": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv1x1_sxpc_up_supported": (_i, [C.c_longlong, _i, _i, _i, _i, _i, _i, _i]),
     "seam_conv1x1_sxpc_up": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_conv1x1_sxpc64_supported": (_i, [C.c_longlong, _i, _i]),
+    "seam_pack_conv1x1_weight_sxpc64": (_i, [_p, _p, _i, _i, _p]),
+    "seam_conv1x1_sxpc64": (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _p]),
+    "seam_conv1x1_sxpc_short_supported": (_i, [C.c_longlong, _i, _i]),
+    "seam_pack_conv1x1_weight_sxpc_short": (_i, [_p, _p, _i, _i, _p]),
+    "seam_conv1x1_sxpc_short": (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _p]),
+    "seam_conv1x1_sxpc_dual_short_supported": (_i, [C.c_longlong, _i, _i, _i]),
+    "seam_conv1x1_sxpc_dual_short": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_stem_sxpc_supported": (_i, [_i, _i, _i]),
+    "seam_stem_sxpc": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "seam_conv1x1_swh_f16": (_i, [_p, _p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_stem_s2d_swh_f16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "seam_conv2d_dual_f16": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -446,6 +446,15 @@ int seam_preprocess_s2d_batch_f32(const float* imgs, size_t img_stride, float* o
     return (int)hipGetLastError();
 }
 
+int seam_preprocess_s2d_pad_batch_f32(const float* imgs, size_t img_stride, float* out, int n, int in_h, int in_w, int out_h, int out_w,
+                                      int Hp, int Wp, int pad_lo, int pad_hi, void* stream) {
+    if (n < 1 || n > 65535 || (Hp & 1) || (Wp & 1) || pad_lo < 0 || pad_hi < 0 || pad_lo > 8 || pad_hi > 8) return (int)hipErrorInvalidValue;
+    dim3 grid((Wp / 2 + pad_lo + pad_hi + 127) / 128, Hp / 2 + pad_lo + pad_hi, n);
+    hipLaunchKernelGGL(preprocess_s2d_kernel<float>, grid, dim3(128), 0, (hipStream_t)stream, imgs, out, in_h, in_w, out_h, out_w,
+                       Hp, Wp, img_stride, pad_lo, pad_hi);
+    return (int)hipGetLastError();
+}
+
 int seam_preprocess_s2d_pad_batch_f16(const float* imgs, size_t img_stride, void* out, int n, int in_h, int in_w, int out_h, int out_w,
                                       int Hp, int Wp, int pad_lo, int pad_hi, void* stream) {
     if (n < 1 || n > 65535 || (Hp & 1) || (Wp & 1) || pad_lo < 0 || pad_hi < 0 || pad_lo > 8 || pad_hi > 8) return (int)hipErrorInvalidValue;

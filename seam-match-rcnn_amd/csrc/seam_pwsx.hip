@@ -47,6 +47,18 @@
 // descriptor is rebased per tile at the first image the tile touches (its index travels behind the table), so lane offsets stay 32-bit.
 // The bits are those of the plain kernel (scale, shift) followed by seam_upsample_add_f32 and ReLU.
 //
+// K = 64 (sxpc_body<.., NG = 2>): conv1x1_sxpc64 is the same block on tiles of 128 pixels x 64 output channels.  The consumers map two
+// by two so that all four SIMDs multiply: wave w owns channels 32 (w & 1) of pixels 64 (w >> 1), two accumulator tiles; per k-step six
+// ds_read_b128, three 1-KiB weight loads, twelve MFMAs in the same term order; the pack is the same fragment order with two n-tiles
+// (6 K C bytes); the epilogue is the same, per wave over its two pixel groups.  C is a multiple of 64 from 128 on.  stem_sxpc
+// (sxpc_body<true, false, 2, true>) is its gather form for the ResNet stem, the 4x4 / stride-1 convolution over the 12-channel
+// space-to-depth frame with its zero cells, [N, Hs + 3, Ws + 3, 12]: an output pixel's reduction is 192 = 4 tap rows x 48 contiguous
+// floats, three chunks of 64.  Only the producers differ: every chunk comes through the two-source form's second descriptor (no first
+// source); the thread's eight pixel offsets are computed once per tile as there; piece q = 16 j + (ptid & 15) of chunk j adds
+// (q / 12) row_step + (q % 12) 16, three launch invariants per lane.  The bits are those of conv1x1_sxpc64 on the gathered [M, 192] rows.
+//
+// The `short` entries launch conv1x1_sxpc / conv1x1_sxpc_dual on two chunks per tile (C = 128; C1 = C2 = 64): see sxpc_plan.
+//
 // LDS map (139264 bytes, one block per CU; the upsampled-residual form: + 1056):
 //   [0, 102400)        two chunk buffers of 128 pixel rows x 400 bytes: plane 0 | plane 1 | plane 2 (64 bf16 = 128 bytes each) | 16
 //                      bytes of padding -- 25 slots of 16 bytes, odd, so the 16 lanes of a ds_read_b128 cycle (16 consecutive
@@ -128,8 +140,13 @@ struct SxpcUp {
     unsigned img_step, row_step, px_step;      // byte steps of top per image / per coarse row (rW K 4) / per coarse pixel (K 4)
 };
 
-template <bool DUAL, bool UP = false>
+// NG: 32-pixel groups (accumulator tiles) per consumer wave.  4: the forms above, 128 output channels per tile, wave w = channels
+// 32 w of all 128 pixels.  2: the 64-output-channel forms (see "K = 64" below), wave w = channels 32 (w & 1) of pixels 64 (w >> 1).
+// STEM (with DUAL, NG = 2): every chunk comes from the second source, a 4 x 4 window of the padded space-to-depth frame.
+template <bool DUAL, bool UP = false, int NG = 4, bool STEM = false>
 __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, const SxpcUp& u = SxpcUp{}) {
+    static_assert((NG == 4 || NG == 2) && (!STEM || (DUAL && NG == 2)) && !(UP && NG != 4), "forms of sxpc_body");
+    constexpr int BN = 32 * (NG == 4 ? 4 : 2);          // output channels per tile
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -142,7 +159,7 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
     const int ntiles = xt.ntiles, S = xt.stride;
     if (ntiles == 0) return;
     const int tile0 = xt.tile0();
-    const int c1 = DUAL ? d.C1 : p.C;     // channels of a row of x
+    const int c1 = STEM ? 0 : DUAL ? d.C1 : p.C;     // channels of a row of x
     const size_t row_bytes = (size_t)c1 * 4, out_row = (size_t)p.K * 4;
     const int total_chunks = ntiles * n;
 
@@ -188,13 +205,28 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                 const unsigned nl = __umulhi(rl, d.m_howo) + rl * d.one_howo + (rl >= d.thr ? 1u : 0u);
                 const unsigned rem = rl - nl * d.HoWo;
                 const unsigned ho = __umulhi(rem, d.m_wo) + rem * d.one_wo, wo = rem - ho * d.Wo;
-                const unsigned off = nl * d.img_step + ho * d.row_step + wo * d.px_step + (unsigned)((ptid & 15) * 16);
+                const unsigned off = nl * d.img_step + ho * d.row_step + wo * d.px_step + (STEM ? 0u : (unsigned)((ptid & 15) * 16));
                 goff2[r] = row0 + (unsigned)(ptid >> 4) + 16 * r < (unsigned)p.M ? off : kOob;
             }
         };
         if (DUAL) x2_tile(tile);
+        // STEM: piece q = 16 ck + (ptid & 15) of a pixel's 192-float window lies (q / 12) frame rows down, 16 (q % 12) bytes in:
+        // three launch invariants per lane
+        unsigned tap[STEM ? 3 : 1] = {};
+        if constexpr (STEM) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const unsigned q = 16u * j + (unsigned)(ptid & 15);
+                tap[j] = (q / 12u) * d.row_step + (q % 12u) * 16u;
+            }
+        }
         auto request = [&](f32x4 (&dst)[NP]) {
-            if (!DUAL || ck < d.n1) {
+            if constexpr (STEM) {
+                const unsigned tj = ck == 0 ? tap[0] : ck == 1 ? tap[1] : tap[2];
+#pragma unroll
+                for (int r = 0; r < NP; ++r)        // (a row past M: kOob + tj stays out of every descriptor)
+                    dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs2, (SEAM_SXPC_ABL & 1) ? kOob : goff2[r] + tj, 0, 0));
+            } else if (!DUAL || ck < d.n1) {
 #pragma unroll
                 for (int r = 0; r < NP; ++r)
                     dst[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (SEAM_SXPC_ABL & 1) ? kOob : goff[r], ck * (CK * 4), 0));
@@ -273,12 +305,13 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
         }
     } else {
         // =================================================== consumer ===================================================
-        const int wn = wave;                    // this wave's 32-channel n-tile of the block's 128
-        f32x16 acc[4];
-        f32x4 af[3][4];                         // [plane][pixel group]: the A fragments of the current k-step
+        const int wn = NG == 4 ? wave : wave & 1;       // this wave's 32-channel n-tile of the block's BN
+        const int pg = NG == 4 ? 0 : wave >> 1;         // ... and (NG = 2) its half of the tile's pixels
+        f32x16 acc[NG];
+        f32x4 af[3][NG];                        // [plane][pixel group]: the A fragments of the current k-step
         f32x4 bf[RB][3];                        // [ring slot][plane]: the wave's weight fragments
         // the lane's pixel (group 0) at k-half lane >> 5, plane 0, in the chunk buffer ...; groups, planes and k-steps are immediates
-        const LDSQ char* ac = (const LDSQ char*)smem + (lane & 31) * ROWB + (lane >> 5) * 16;      // ... of the current chunk
+        const LDSQ char* ac = (const LDSQ char*)smem + (lane & 31) * ROWB + (lane >> 5) * 16 + pg * (NG * 32 * ROWB);      // ... of the current chunk
         const LDSQ char* an = ac + ABUF;                                                            // ... of the next one
         const int nsteps = p.C >> 4;
         const int wtile_bytes = nsteps * 3072;  // one n-tile's weights: C / 16 k-steps x three 1-KiB planes
@@ -294,22 +327,23 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
             tm_n = fdivu(tl, p.tiles_n, p.m_tiles_n);
             tn_n = __builtin_amdgcn_readfirstlane(tl - tm_n * p.tiles_n);
             tm_n = __builtin_amdgcn_readfirstlane(tm_n);
-            w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w + (size_t)(tn_n * 4 + wn) * wtile_bytes), 0, wtile_bytes, 0x00020000);
+            w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.w + (size_t)(tn_n * (BN / 32) + wn) * wtile_bytes), 0, wtile_bytes, 0x00020000);
 #pragma unroll
             for (int s = 0; s < RB; ++s) { SB(); load_b(s, s); }
             SB();
         };
         // The epilogue's row layout (after the wave-private transpose): lane -> pixel (lane >> 3) + 8 i of a 32-pixel group, 16-byte piece
         // (lane & 7) of the wave's 32 channels: eight lanes write one pixel's 128 bytes -- a full line per pixel.
-        const unsigned ooff = (unsigned)((lane >> 3) * p.K * 4 + (32 * wn + 4 * (lane & 7)) * 4);
-        LDSQ char* const tw = (LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane & 31) * TROW + (lane >> 5) * 16;   // accumulator layout: piece 2 qd + h
-        const LDSQ char* const tr = (const LDSQ char*)smem + TR0 + wn * (2 * TBUF) + (lane >> 3) * TROW + (lane & 7) * 16;
+        const unsigned ooff = (unsigned)(((lane >> 3) + pg * (NG * 32)) * p.K * 4 + (32 * wn + 4 * (lane & 7)) * 4);
+        LDSQ char* const tw = (LDSQ char*)smem + TR0 + wave * (2 * TBUF) + (lane & 31) * TROW + (lane >> 5) * 16;   // accumulator layout: piece 2 qd + h
+        const LDSQ char* const tr = (const LDSQ char*)smem + TR0 + wave * (2 * TBUF) + (lane >> 3) * TROW + (lane & 7) * 16;
         const int K32 = 32 * p.K * 4, K8 = 8 * p.K * 4;        // byte steps of a 32-pixel group / of 8 pixels
         const LDSQ char* const tbr = (const LDSQ char*)smem + TBL0 + (lane >> 3) * 64;       // UP: this lane's pixel row of the offset table
         int tpar = 0;                           // ... of the current tile (tile parity)
         int tile = tile0;
         ring_preload(tile);
-        f32x4 rv[4][4], sc, sh;
+        constexpr int RV = RVA < NG ? RVA : NG;      // pixel groups whose residual pieces travel under the tile's last chunk
+        f32x4 rv[NG][4], sc, sh;
         LDS_BAR();                              // P: chunk 0 is in LDS
         for (int k = 0; k < ntiles; ++k) {
             const int tm_k = tm_n, tn_k = tn_n;             // (wave-uniform by construction)
@@ -318,8 +352,8 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                 (void*)((char*)p.y + (size_t)tm_k * BM * out_row), 0, (int)(rows * out_row), 0x00020000);
             const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)((const char*)(p.res ? p.res : p.y) + (size_t)tm_k * BM * out_row), 0, (int)(rows * out_row), 0x00020000);
-            const unsigned ocol = ooff + (unsigned)(tn_k * 512);
-            const unsigned ccol = (unsigned)(tn_k * 512 + 128 * wn) + (unsigned)((lane & 7) * 16);      // UP: the lane's piece inside a coarse pixel
+            const unsigned ocol = ooff + (unsigned)(tn_k * (BN * 4));
+            const unsigned ccol = (unsigned)(tn_k * (BN * 4) + 128 * wn) + (unsigned)((lane & 7) * 16);      // UP: the lane's piece inside a coarse pixel
             __amdgpu_buffer_rsrc_t t_rsrc = y_rsrc;         // UP: the coarse map from the tile's first image on (set at the last chunk)
             // UP: pixel group m's residual pieces through the tile's offset table (rows past M: kOob, zeros)
             auto up_request = [&](const int m) {
@@ -333,14 +367,14 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-                for (int m = 0; m < 4; ++m) af[pl][m] = *reinterpret_cast<const f32x4 LDSQ*>(ac + m * (32 * ROWB) + pl * PLB);
+                for (int m = 0; m < NG; ++m) af[pl][m] = *reinterpret_cast<const f32x4 LDSQ*>(ac + m * (32 * ROWB) + pl * PLB);
             for (int t = 0; t < n; ++t) {
                 const bool last = t == n - 1;
                 if (last) {
                     // the tile's epilogue vectors (this lane's four channels in the row layout) without a branch of their own (a
                     // missing vector reads the weights instead and is replaced by 1 / 0), and the residual pieces of the first RVA
                     // pixel groups (row layout): in flight under the tile's last chunk
-                    const int ch = tn_k * 128 + 32 * wn + 4 * (lane & 7);
+                    const int ch = tn_k * BN + 32 * wn + 4 * (lane & 7);
                     const f32x4 a = *reinterpret_cast<const f32x4*>((p.scale ? p.scale : (const float*)p.w) + ch);
                     const f32x4 b = *reinterpret_cast<const f32x4*>((p.shift ? p.shift : (const float*)p.w) + ch);
                     sc = a;                     // (replaced in the epilogue: a select here would wait for the loads at once)
@@ -351,10 +385,10 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                         t_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)u.top + (size_t)n_first * u.img_bytes), 0,
                                                                    (int)(left > kOob ? kOob : (unsigned)left), 0x00020000);
 #pragma unroll
-                        for (int m = 0; m < RVA; ++m) up_request(m);
+                        for (int m = 0; m < RV; ++m) up_request(m);
                     } else if (p.res) {
 #pragma unroll
-                        for (int m = 0; m < RVA; ++m)
+                        for (int m = 0; m < RV; ++m)
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
                                 rv[m][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, ocol + m * K32 + i * K8, 0, 0));
@@ -378,11 +412,11 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                             SB();
 #if !(SEAM_SXPC_ABL & 8)
 #pragma unroll
-                            for (int m = 0; m < 4; ++m) af[2][m] = read_a(2, m, KS);
+                            for (int m = 0; m < NG; ++m) af[2][m] = read_a(2, m, KS);
 #endif
                         }
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) {
+                        for (int m = 0; m < NG; ++m) {
                             SB();
                             // roles swapped: rows = output channels (the weight fragment), columns = pixels (the activation fragment)
                             if (ks == 0 && tq == 0 && t == 0) {     // the tile's first step multiplies into a constant zero: no accumulator clears
@@ -419,7 +453,7 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                 constexpr bool RES = decltype(res_c)::value, RELU = decltype(relu_c)::value;
                 if (RES) {
 #pragma unroll
-                    for (int m = RVA; m < 4; ++m)   // the pixel groups the last chunk had no registers for
+                    for (int m = RV; m < NG; ++m)   // the pixel groups the last chunk had no registers for
                         if constexpr (UP) {
                             up_request(m);
                         } else {
@@ -429,7 +463,7 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                         }
                     // (one wait for everything that came from memory, before the first store)
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) asm volatile("" :: "v"(rv[m][0]), "v"(rv[m][1]), "v"(rv[m][2]), "v"(rv[m][3]));
+                    for (int m = 0; m < NG; ++m) asm volatile("" :: "v"(rv[m][0]), "v"(rv[m][1]), "v"(rv[m][2]), "v"(rv[m][3]));
                 }
                 // accumulator layout (lane = pixel, register quad = 4 consecutive channels) -> this wave's private [32 pixels][32 channels]
                 // rows (two buffers: group m + 1 is written before group m is read back) -> row layout: 8 lanes per pixel
@@ -441,8 +475,8 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                 };
                 put(0);
 #pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    if (m + 1 < 4) put(m + 1);
+                for (int m = 0; m < NG; ++m) {
+                    if (m + 1 < NG) put(m + 1);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         f32x4 v = *reinterpret_cast<const f32x4 LDSQ*>(tr + (m & 1) * TBUF + i * (8 * TROW));
@@ -481,8 +515,15 @@ __global__ void sxpc_pack_kernel(const float* __restrict__ w, unsigned short* __
 // (behind the pack kernel: the existing kernels keep their place in the module)
 __global__ __launch_bounds__(512, 2) void conv1x1_sxpc_up(const SxpcArgs p, const SxpcUp u) { sxpc_body<false, true>(p, SxpcDual{}, u); }
 
-int sxpc_plan(SxpcArgs& a, long long M, int C, int K) {
-    if (M <= 0 || C < 256 || (C % CK) || K < 128 || (K % 128)) return 1;
+// (behind the existing kernels, like conv1x1_sxpc_up)  K = 64: the 64-output-channel form and the stem as its gather form
+__global__ __launch_bounds__(512, 2) void conv1x1_sxpc64(const SxpcArgs p) { sxpc_body<false, false, 2>(p, SxpcDual{}); }
+__global__ __launch_bounds__(512, 2) void stem_sxpc(const SxpcArgs p, const SxpcDual d) { sxpc_body<true, false, 2, true>(p, d); }
+
+// min_c: 256 for the entries above; 128 for the `short` entries (two chunks per tile: the body's pipeline is counted in chunks
+// over the block's tiles, the weight ring's look-ahead is clamped to the tile, the residual requests go out in the last chunk
+// whichever it is -- nothing in it needs a third chunk)
+int sxpc_plan(SxpcArgs& a, long long M, int C, int K, int min_c = 256) {
+    if (M <= 0 || C < min_c || (C % CK) || K < 128 || (K % 128)) return 1;
     if ((unsigned long long)BM * C * 4 >= kOob || (unsigned long long)BM * K * 4 >= kOob) return 1;
     if ((unsigned long long)(C / 16) * 3072 >= kOob) return 1;
     const long long tiles_m = (M + BM - 1) / BM;
@@ -497,12 +538,13 @@ int sxpc_plan(SxpcArgs& a, long long M, int C, int K) {
 }
 
 // the dual form: the plain plan of (M, C1 + C2, K) and the second source's geometry
-int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long long Wo, int C1, long long H2, long long W2, int C2, int stride2, int K) {
+int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long long Wo, int C1, long long H2, long long W2, int C2, int stride2, int K,
+                   int min_c = 256) {
     if (N <= 0 || Ho <= 0 || Wo <= 0 || H2 <= 0 || W2 <= 0 || C1 < CK || C2 < CK || (C1 % CK) || (C2 % CK) || stride2 < 1) return 1;
     if (N >= (1LL << 31) || Ho >= (1LL << 31) || Wo >= (1LL << 31) || H2 >= (1LL << 31) || W2 >= (1LL << 31)) return 1;
     if ((Ho - 1) * stride2 >= H2 || (Wo - 1) * stride2 >= W2) return 1;
     if (Ho * Wo >= (1LL << 31) || N * (Ho * Wo) >= (1LL << 31)) return 1;
-    if (sxpc_plan(a, N * Ho * Wo, C1 + C2, K)) return 1;
+    if (sxpc_plan(a, N * Ho * Wo, C1 + C2, K, min_c)) return 1;
     const long long HoWo = Ho * Wo;
     if ((unsigned long long)H2 * W2 >= (1ull << 31) / ((unsigned long long)C2 * 4)) return 1;      // one image of x2 inside a descriptor
     const unsigned long long img2 = (unsigned long long)H2 * W2 * C2 * 4;
@@ -553,6 +595,45 @@ int sxpc_up_plan(SxpcArgs& a, SxpcUp& u, long long N, long long Ho, long long Wo
     u.img_step = (unsigned)img;
     u.row_step = (unsigned)((unsigned long long)rW * K * 4);
     u.px_step = (unsigned)((unsigned long long)K * 4);
+    return 0;
+}
+
+// the 64-output-channel form: one n-tile of 64 channels, two chunks per tile at the least (one chunk is refused: untested, unused)
+int sxpc64_plan(SxpcArgs& a, long long M, int C, int K) {
+    if (M <= 0 || K != 64 || C < 2 * CK || (C % CK)) return 1;
+    if ((unsigned long long)BM * C * 4 >= kOob || (unsigned long long)(C / 16) * 3072 >= kOob) return 1;
+    const long long total = (M + BM - 1) / BM;
+    if (total >= (1LL << 24) || M >= (1LL << 31)) return 1;
+    a.M = (int)M; a.C = C; a.K = K;
+    a.tiles_n = 1; a.nchunks = C / CK; a.total_tiles = (int)total;
+    a.m_tiles_n = 0;        // (fdivu's d == 1 branch)
+    return 0;
+}
+
+// the stem: sxpc64_plan of (N Hs Ws, 192, 64) and the padded frame [N, Hs + 3, Ws + 3, 12] as SxpcDual's second source (no first one)
+int stem_sxpc_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Hs, long long Ws) {
+    if (N <= 0 || Hs <= 0 || Ws <= 0 || N >= (1LL << 31) || Hs >= (1LL << 31) - 3 || Ws >= (1LL << 31) - 3) return 1;
+    if (Hs * Ws >= (1LL << 31) || N * (Hs * Ws) >= (1LL << 31)) return 1;
+    if (sxpc64_plan(a, N * Hs * Ws, 192, 64)) return 1;
+    const long long HoWo = Hs * Ws;
+    if ((unsigned long long)(Hs + 3) * (Ws + 3) >= (1ull << 31) / 48) return 1;      // one frame inside a descriptor
+    const unsigned long long img = (unsigned long long)(Hs + 3) * (Ws + 3) * 48;
+    // a tile's 128 rows touch at most this many frames; their windows are addressed from the first one's start with 32-bit offsets
+    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
+    if (imgs * img > kOob) return 1;
+    const bool mid = HoWo >= 2 && HoWo < BM;
+    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
+    if (!seam_fastdiv::exact((unsigned long long)Ws, (unsigned long long)HoWo)) return 1;
+    d.img2_bytes = img;
+    d.N = (int)N; d.C1 = 0; d.n1 = 0; d.HoWo = (unsigned)HoWo; d.Wo = (unsigned)Ws;
+    d.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
+    d.one_howo = HoWo == 1 ? 1u : 0u;
+    d.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
+    d.m_wo = seam_fastdiv::magic((unsigned long long)Ws);
+    d.one_wo = Ws == 1 ? 1u : 0u;
+    d.img_step = (unsigned)img;
+    d.row_step = (unsigned)((Ws + 3) * 48);
+    d.px_step = 48u;
     return 0;
 }
 
@@ -641,6 +722,109 @@ int seam_conv1x1_sxpc_up(const float* x, const void* w_packed, const float* scal
     if (e != hipSuccess) return (int)e;
     const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
     hipLaunchKernelGGL(conv1x1_sxpc_up, dim3(grid), dim3(512), LDS_UP_BYTES, (hipStream_t)stream, a, u);
+    return (int)hipGetLastError();
+}
+
+/* The `short` entries: conv1x1_sxpc / conv1x1_sxpc_dual on two-chunk reductions, C == 128 / C1 == C2 == 64 with stride2 == 1 */
+int seam_conv1x1_sxpc_short_supported(long long M, int C, int K) {
+    SxpcArgs a;
+    return C == 2 * CK && sxpc_plan(a, M, C, K, 2 * CK) == 0 ? 1 : 0;
+}
+
+int seam_pack_conv1x1_weight_sxpc_short(const float* w, void* w_packed, int K, int C, void* stream) {
+    if (!seam_conv1x1_sxpc_short_supported(1, C, K)) return (int)hipErrorInvalidValue;
+    const size_t total = (size_t)K * C / 8;
+    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(seam_launch::grid256(total)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
+    return (int)hipGetLastError();
+}
+
+int seam_conv1x1_sxpc_short(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                            long long M, int C, int K, int relu, void* stream) {
+    SxpcArgs a;
+    if ((relu != 0 && relu != 1) || C != 2 * CK || sxpc_plan(a, M, C, K, 2 * CK)) return (int)hipErrorInvalidValue;
+    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int seam_conv1x1_sxpc_dual_short_supported(long long M, int C1, int C2, int K) {
+    SxpcArgs a;
+    return C1 == CK && C2 == CK && sxpc_plan(a, M, C1 + C2, K, 2 * CK) == 0 ? 1 : 0;
+}
+
+int seam_conv1x1_sxpc_dual_short(const float* x1, const float* x2, const void* w_packed, const float* scale, const float* shift, float* y,
+                                 int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int K, int relu, void* stream) {
+    SxpcArgs a;
+    SxpcDual d;
+    if ((relu != 0 && relu != 1) || !x2 || C1 != CK || C2 != CK || sxpc_dual_plan(a, d, N, Ho, Wo, C1, H2, W2, C2, 1, K, 2 * CK))
+        return (int)hipErrorInvalidValue;
+    a.x = x1; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    d.x2 = x2;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_dual>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc_dual, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
+    return (int)hipGetLastError();
+}
+
+/* 1 when seam_conv1x1_sxpc64 takes this layer (1x1 / stride 1 / pad 0; K == 64; C >= 128 and a multiple of 64; M >= 1), else 0 */
+int seam_conv1x1_sxpc64_supported(long long M, int C, int K) {
+    SxpcArgs a;
+    return sxpc64_plan(a, M, C, K) == 0 ? 1 : 0;
+}
+
+/* w: [64, C] fp32 row-major -> the three bf16 planes in seam_conv1x1_sxpc's fragment order with two 32-channel n-tiles: 6 K C bytes */
+int seam_pack_conv1x1_weight_sxpc64(const float* w, void* w_packed, int K, int C, void* stream) {
+    SxpcArgs a;
+    if (sxpc64_plan(a, 1, C, K)) return (int)hipErrorInvalidValue;
+    const size_t total = (size_t)K * C / 8;
+    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(seam_launch::grid256(total)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
+    return (int)hipGetLastError();
+}
+
+/* y[M, 64] = act(scale * (x[M, C] . w^T) + shift + residual): seam_conv1x1_sxpc's arithmetic (the bits of seam_conv2d_sx with
+ * terms = 6) for 64 output channels; w_packed: seam_pack_conv1x1_weight_sxpc64; relu 0 | 1 */
+int seam_conv1x1_sxpc64(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
+                        long long M, int C, int K, int relu, void* stream) {
+    SxpcArgs a;
+    if ((relu != 0 && relu != 1) || sxpc64_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
+    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<conv1x1_sxpc64>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(conv1x1_sxpc64, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+/* 1 when seam_stem_sxpc takes the frame geometry (N frames of Hs x Ws space-to-depth cells), else 0 */
+int seam_stem_sxpc_supported(int N, int Hs, int Ws) {
+    SxpcArgs a;
+    SxpcDual d;
+    return stem_sxpc_plan(a, d, N, Hs, Ws) == 0 ? 1 : 0;
+}
+
+/* The ResNet stem as the 4x4 / stride-1 convolution over the space-to-depth frame: xp [N, Hs + 3, Ws + 3, 12] fp32 is the frame
+ * with its zero cells (2 before, 1 after, both directions), y [N, Hs, Ws, 64] = act(scale * (window . w^T) + shift) with the window
+ * of an output pixel its 4 x 4 cells in (r, s, c) order: the bits of seam_conv1x1_sxpc64 on the gathered [N Hs Ws, 192] rows.
+ * w_packed: seam_pack_conv1x1_weight_sxpc64 of the [64, 192] rows; relu 0 | 1 */
+int seam_stem_sxpc(const float* xp, const void* w_packed, const float* scale, const float* shift, float* y, int N, int Hs, int Ws,
+                   int relu, void* stream) {
+    SxpcArgs a;
+    SxpcDual d;
+    if ((relu != 0 && relu != 1) || !xp || stem_sxpc_plan(a, d, N, Hs, Ws)) return (int)hipErrorInvalidValue;
+    a.x = xp; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    d.x2 = xp;
+    int ncu;
+    const hipError_t e = seam_launch::prepare<stem_sxpc>(LDS_BYTES, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(stem_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
     return (int)hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 // job's items with the item functions of seam_pack_items.h -- the functions the per-layer pack kernels run, so the bytes written
 // are those of the per-layer ABI calls.  The three-plane split twin (SEAM_REPACK_SPLIT3) computes each value of the exact pack
 // from the source and splits it, so it does not wait for another job of the same launch; the fragment-order split form of
-// conv1x1_sxpc (SEAM_REPACK_SXPC) reads the row-major source itself.
+// conv1x1_sxpc (SEAM_REPACK_SXPC; SEAM_REPACK_SXPC64: its 64-row and two-chunk forms) reads the row-major source itself.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "seam_device.h"
@@ -50,6 +50,7 @@ __global__ __launch_bounds__(256) void repack_many_kernel(const seam_repack_job_
         for (size_t i = i0; i < total; i += step) seam_pack::pwpc_item(src, (float*)j.dst, i, j.Cstore);
         break;
     case SEAM_REPACK_SXPC:
+    case SEAM_REPACK_SXPC64:
         for (size_t i = i0; i < total; i += step) seam_pack::sxpc_item(src, (unsigned short*)j.dst, i, j.Cstore);
         break;
     case SEAM_REPACK_SW:
@@ -87,6 +88,9 @@ long long job_items(seam_repack_job_t& j) {
         return (long long)j.K * j.Cstore / 4;
     case SEAM_REPACK_SXPC:
         if (!plain || !seam_conv1x1_sxpc_supported(1, j.Cstore, j.K)) return 0;
+        return (long long)j.K * j.Cstore / 8;
+    case SEAM_REPACK_SXPC64:
+        if (!plain || !(seam_conv1x1_sxpc64_supported(1, j.Cstore, j.K) || seam_conv1x1_sxpc_short_supported(1, j.Cstore, j.K))) return 0;
         return (long long)j.K * j.Cstore / 8;
     case SEAM_REPACK_SW:
         if (!plain) return 0;

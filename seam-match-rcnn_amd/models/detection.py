@@ -17,6 +17,7 @@ Activations are NHWC fp32 device tensors internally.  Modules hold parameters on
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from collections import OrderedDict
 from typing import List, Sequence, Tuple
@@ -26,7 +27,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import ops
+from .. import _native, ops
 from .packed import PackedWeights
 
 RESNET50_LAYERS = ((3, 64, 1), (4, 128, 2), (6, 256, 2), (3, 512, 2))
@@ -54,18 +55,21 @@ def adt(module) -> torch.dtype:
 # product, where the exact kernels are one rounding of each partial sum away.  The module attribute ``split_f32`` (set for a whole
 # model with ``set_split_f32``; SEAM_SPLIT_F32=0 for the process) switches it off and restores the exact-fp32 kernels bit for bit.
 # Classes: c1 = bottleneck 1x1 reductions, c3 = 1x1 expansions with their residual (C >= SPLIT_C3_MIN_C), c2s2 = the three
-# stride-2 3x3s, c3ds = the two-source shortcut GEMMs of layer2.0 / layer3.0 / layer4.0 (C1 + C2 >= SPLIT_C3DS_MIN_C: layer1.0, 64 + 64 on
-# one map, stays on conv1x1_sw), lat = the FPN's four lateral 1x1s (inner_blocks: 256 / 512 / 1024 / 2048 -> 256, three of them with
+# stride-2 3x3s, c3ds = the two-source shortcut GEMMs of layer2.0 / layer3.0 / layer4.0 (C1 + C2 >= SPLIT_C3DS_MIN_C) and, on the
+# two-chunk entries of ops.SXPC_SHORT, layer1.0's (64 + 64 on one map), lat = the FPN's four lateral 1x1s (inner_blocks: 256 / 512 / 1024 / 2048 -> 256, three of them with
 # the nearest top-down merge), mdeconv = the mask head's 2x2 / stride-2 transposed conv as the 1x1 conv of its [1024, 256] matrix.
 # The long 1x1 layers of c1 / c3 / lat / mdeconv (C >= 256, K % 128 == 0) run their SX6 packs on the producer / consumer kernel
 # conv1x1_sxpc, c3ds on its two-source form conv1x1_sxpc_dual, the three merging laterals on its upsampled-residual form
 # conv1x1_sxpc_up (ops.SXPC; each the bits of conv_igemm_sx -- on the concatenated rows / followed by upsample_add_), the others on
 # conv_igemm_sx.  lat and mdeconv need SPLIT_DTYPE == SX6 (the only split form of those kernels).
+# stem = the ResNet stem in its space-to-depth form on stem_sxpc (ops.stem_s2d_sx: SX6, ops.SXPC, maps of >= 128 cells); the
+# transform then writes the fp32 frame with its zero cells, and a padded frame that meets a call the split kernels do not serve
+# runs the exact implicit GEMM over it as a valid convolution -- the bits of the unpadded frame's exact stem.
 SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
 SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
-SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; the short reductions of layer1 / layer2 (C = 64, 128) are faster on conv1x1_sw
+SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; layer2's (C = 128) have a twin of their own on ops.SXPC_SHORT, layer1's (C = 64) stay on conv1x1_sw
 SPLIT_C3DS_MIN_C = 384    # C1 + C2 of the served shortcut GEMMs: a rule on the layer's geometry alone, never on the batch
-SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds,lat,mdeconv").split(",") if c)
+SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds,lat,mdeconv,stem").split(",") if c)
 
 
 def split_on(module) -> bool:
@@ -162,8 +166,12 @@ class GeneralizedRCNNTransform(nn.Module):
         # fp32 / fp16 paths with float images: space-to-depth layout for the 4x4 / stride-1 form of the stem (STEM_S2D)
         s2d = STEM_S2D and cdt(self) in (torch.float32, torch.float16) and all(i.dtype == torch.float32 for i in images)
         # fp16 path: the frame comes with the zero cells the streaming stem kernel wants around it (2 before, 1 after); the caller
-        # tells the backbone (``s2d_padded``) by comparing the frame's height with the padded size returned here
+        # tells the backbone (``s2d_padded``) by comparing the frame's height with the padded size returned here.  fp32 path: the
+        # same, when the split stem will run (``split_on``: eval mode, no gradient tape; class ``stem``; a map it serves)
         pad = (2, 1) if (s2d and STEM_SWH and adt(self) == torch.float16) else (0, 0)
+        if (s2d and adt(self) == torch.float32 and split_twin(self, "stem") and split_on(self) and ops.SXPC
+                and (hp // 2) * (wp // 2) >= 128 and _native.lib().seam_stem_sxpc_supported(len(images), hp // 2, wp // 2) == 1):
+            pad = (2, 1)
         return ops.preprocess(images, sizes, hp, wp, adt(self), s2d=s2d, s2d_pad=pad), sizes, orig, (hp, wp)
 
     @staticmethod
@@ -225,7 +233,7 @@ class Bottleneck(nn.Module):
 
 
 class ResNet50Body(PackedWeights, nn.Module):
-    SPLIT_TWINS = ("c1", "c2s2", "c3", "c3ds")
+    SPLIT_TWINS = ("c1", "c2s2", "c3", "c3ds", "stem")
 
     def __init__(self):
         super().__init__()
@@ -251,7 +259,7 @@ class ResNet50Body(PackedWeights, nn.Module):
 
     def _build_packs(self):
         dt = cdt(self)
-        c1x, c2x, c3x, c3dsx = (split_twin(self, c) for c in self.SPLIT_TWINS)
+        c1x, c2x, c3x, c3dsx, stemx = (split_twin(self, c) for c in self.SPLIT_TWINS)
         pk = {"stem": ops.pack_conv(self.conv1.weight, None, self.bn1.tensors(), stride=2, pad=3,
                                     cstore=8 if dt == torch.float16 else 4, bn_eps=self.bn1.eps, dtype=dt)}
         if dt in (torch.float32, torch.float16):
@@ -262,6 +270,10 @@ class ResNet50Body(PackedWeights, nn.Module):
             ws = ops.derived_source(s2d_weight, (self.conv1.weight,))
             pk["stem_s2d"] = ops.pack_conv(ws, None, self.bn1.tensors(), stride=1, pad=2, cstore=12 if dt == torch.float32 else 16,
                                            bn_eps=self.bn1.eps, wino=False, dtype=dt)
+            if stemx:
+                # the split twin (ops.stem_s2d_sx): rows [64, (r, s, 12 channels)] of the same weights as a 1x1 layer's SX6 pack
+                rows = ops.derived_source(lambda: s2d_weight().permute(0, 2, 3, 1).reshape(64, 192, 1, 1).contiguous(), (self.conv1.weight,))
+                pk["stem_x"] = ops.pack_conv(rows, None, self.bn1.tensors(), bn_eps=self.bn1.eps, dtype=ops.SX6)
             if dt == torch.float16 and STEM_SWH:
                 # the streaming form of the fp16 stem (ops.stem_s2d_f16): rows [64, (r, s, 16 channels)] of the same weights
                 pk["stem_rows"] = F.pad(ws, (0, 0, 0, 0, 0, 4)).permute(0, 2, 3, 1).reshape(64, 256).to(torch.float16).contiguous()
@@ -277,11 +289,13 @@ class ResNet50Body(PackedWeights, nn.Module):
                     if dt in (torch.float32, torch.float16) and FUSE_SHORTCUT:     # conv3 + projection shortcut as one GEMM
                         # (its split twin is packed beside it from the SAME folded matrix: one derived source for PackPlan)
                         twin = c3dsx and b.conv3.in_channels + b.downsample[0].in_channels >= SPLIT_C3DS_MIN_C
+                        # (64 + 64 on one map, layer1.0: the two-chunk twin of ops.SXPC_SHORT, under a key of its own)
+                        short = (c3dsx and not twin and b.stride == 1 and b.conv3.in_channels == 64 and b.downsample[0].in_channels == 64)
                         packs = ops.pack_conv_dual(b.conv3.weight, b.bn3.tensors(), b.downsample[0].weight, b.downsample[1].tensors(),
-                                                   bn_eps=b.bn3.eps, dtype=(dt, ops.SX6) if twin else (dt,))
+                                                   bn_eps=b.bn3.eps, dtype=(dt, ops.SX6) if twin or short else (dt,))
                         e["c3ds"] = packs[0]
-                        if twin:
-                            e["c3dsx"] = packs[1]
+                        if twin or short:
+                            e["c3dsx" if twin else "c3dsxs"] = packs[1]
                 # split twins of the exact packs (the exact ones stay: the switch and the grad-enabled walk use them)
                 if c1x:
                     e["c1x"] = ops.pack_conv(b.conv1.weight, None, b.bn1.tensors(), bn_eps=b.bn1.eps, dtype=SPLIT_DTYPE)
@@ -290,6 +304,9 @@ class ResNet50Body(PackedWeights, nn.Module):
                                              dtype=SPLIT_DTYPE)
                 if c3x and "c3ds" not in e and b.conv3.in_channels >= SPLIT_C3_MIN_C:
                     e["c3x"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=SPLIT_DTYPE)
+                if c3x and "c3ds" not in e and b.conv3.in_channels == 128 and SPLIT_DTYPE == ops.SX6:
+                    # layer2's 128 -> 512 expansions: the two-chunk twin (ops.SXPC_SHORT), picked per map in _run
+                    e["c3xs"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=ops.SX6)
                 pk[(li, bi)] = e
         return pk
 
@@ -328,15 +345,26 @@ class ResNet50Body(PackedWeights, nn.Module):
             return outs
         return self._run(x, pk, None, s2d_padded)
 
-    def _stem(self, x, pk, s2d_padded=False, pool=True):
-        """Stem conv (either input form) + FrozenBN + ReLU + the 3x3 / stride-2 max-pool (``pool=False``: the pool's input)."""
+    def _stem(self, x, pk, s2d_padded=False, pool=True, exact=False):
+        """Stem conv (either input form) + FrozenBN + ReLU + the 3x3 / stride-2 max-pool (``pool=False``: the pool's input).
+        ``exact``: never the split twin (the taped forward, whose stem runs under no_grad all the same)."""
         if x.shape[-1] in (12, 16):    # space-to-depth input [N,H/2,W/2,12] (fp16: 16): the stem as a 4x4 / stride-1 conv, output grid = input grid
             streaming = ("stem_rows" in pk and x.dtype == torch.float16 and x.shape[-1] == 16
                          and (x.shape[1] - (3 if s2d_padded else 0)) * (x.shape[2] - (3 if s2d_padded else 0)) >= 128)
-            if s2d_padded and not streaming:      # (cannot happen through the transform: it pads only when the kernel will run)
+            spad = 3 if s2d_padded else 0
+            split = (x.dtype == torch.float32 and x.shape[-1] == 12 and not exact and split_on(self)
+                     and ops.stem_sx_ok(_native.lib(), pk.get("stem_x"), x.shape[0], x.shape[1] - spad, x.shape[2] - spad))
+            if s2d_padded and x.dtype == torch.float16 and not streaming:      # (cannot happen through the transform: it pads only when the kernel will run)
                 x = x[:, 2:-1, 2:-1].contiguous()
             if streaming:
                 x = ops.stem_s2d_f16(x, pk["stem_rows"], pk["stem_s2d"].scale, pk["stem_s2d"].shift, relu=True, padded=s2d_padded)
+            elif split:
+                x = ops.stem_s2d_sx(x, pk["stem_x"], relu=True, padded=s2d_padded)
+            elif s2d_padded:
+                # the fp32 frame with its zero cells on a call the split stem does not serve (a gradient tape, training mode, the
+                # switches): the exact implicit GEMM as a valid convolution over it -- the padding's products are the zeros the
+                # pad-2 form never forms, so the bits are those of the line below on the unpadded frame
+                x = ops.conv2d(x, dataclasses.replace(pk["stem_s2d"], pad=0), relu=True)
             else:
                 x = ops.conv2d(x, pk["stem_s2d"], relu=True, out_hw=(x.shape[1], x.shape[2]))
         else:
@@ -353,10 +381,12 @@ class ResNet50Body(PackedWeights, nn.Module):
                 o = ops.conv2d(x, pick_pack(self, e["c1"], e.get("c1x")), relu=True)
                 o = ops.conv2d(o, pick_pack(self, e["c2"], e.get("c2x")), relu=True)
                 if "c3ds" in e:       # projection-shortcut block: bn3(conv3(o)) + bn_d(conv_d(x)) + ReLU in one launch
-                    x = ops.conv2d_dual(o, x, pick_pack(self, e["c3ds"], e.get("c3dsx")), getattr(self, f"layer{li}")[bi].stride, relu=True)
+                    twin = e.get("c3dsx") or (e.get("c3dsxs") if ops.SXPC_SHORT else None)
+                    x = ops.conv2d_dual(o, x, pick_pack(self, e["c3ds"], twin), getattr(self, f"layer{li}")[bi].stride, relu=True)
                     continue
                 idt = ops.conv2d(x, e["ds"]) if "ds" in e else x
-                x = ops.conv2d(o, pick_pack(self, e["c3"], e.get("c3x")), relu=True, residual=idt,   # bn3 + add + ReLU fused
+                twin = e.get("c3x") or (e.get("c3xs") if ops.sxpc_short_map_ok(o.shape[1], o.shape[2], e["c3"].K) else None)
+                x = ops.conv2d(o, pick_pack(self, e["c3"], twin), relu=True, residual=idt,   # bn3 + add + ReLU fused
                                out=outs[li - 1] if (outs is not None and bi == nblk - 1) else None)
             feats.append(x)
         return feats
@@ -388,11 +418,11 @@ class ResNet50Body(PackedWeights, nn.Module):
         if stem:
             weights = [self.conv1.weight] + [w for _, _, b in blocks for w in block_weights(b)]
             meta = [(pk[(li, bi)], b.stride, b.downsample is not None, bi == len(getattr(self, f"layer{li}")) - 1) for li, bi, b in blocks]
-            stem_fwd = (lambda f: self._stem(f, pk, s2d_padded, pool=False), pk["stem"].scale)
+            stem_fwd = (lambda f: self._stem(f, pk, s2d_padded, pool=False, exact=True), pk["stem"].scale)
             return list(BodyFunction.apply(meta, stem_fwd, x, *weights))
         start = next((i for i, (_, _, b) in enumerate(blocks) if any(p.requires_grad for p in b.parameters())), len(blocks))
         with torch.no_grad():
-            x = self._stem(x.detach(), pk, s2d_padded)
+            x = self._stem(x.detach(), pk, s2d_padded, exact=True)
             feats = []
             for li, bi, b in blocks[:start]:
                 x = body_block(x, pk[(li, bi)], b.stride)[0]

@@ -261,11 +261,12 @@ class MatchRCNN(VideoMatchRCNN):
         if body_learns or fpn_learns:
             with torch.no_grad():
                 x, sizes, orig, padded = self.transform(det.image_list(images))
+            spad = x.shape[-1] == 12 and x.shape[1] == padded[0] // 2 + 3      # (training mode: the transform does not pad; told all the same)
             if body_learns:                 # the body through BodyFunction; a frozen FPN still passes its gradient to C2..C5
-                c = body(x, taped=True)
+                c = body(x, spad, taped=True)
             else:                           # body without a tape, the pyramid through FPNFunction
                 with torch.no_grad():
-                    c = body(x)             # fp32: never the padded space-to-depth frame of the fp16 path
+                    c = body(x, spad)
             feats = self.backbone.fpn.forward_taped(c)
         else:
             with torch.no_grad():

@@ -277,7 +277,7 @@ class VideoMatchRCNN(nn.Module):
     # ---- stages ------------------------------------------------------------------------------------
     def extract_features(self, images: Sequence[torch.Tensor]):
         x, sizes, orig, padded = self.transform(images)
-        s2d_padded = x.shape[-1] == 16 and x.shape[1] == padded[0] // 2 + 3        # fp16 path: zero cells around the space-to-depth frame
+        s2d_padded = x.shape[-1] in (12, 16) and x.shape[1] == padded[0] // 2 + 3      # zero cells around the space-to-depth frame (fp16 path; fp32: the split stem)
         return self.backbone(x, s2d_padded), sizes, orig, padded
 
     def postprocess(self, result, sizes, orig):

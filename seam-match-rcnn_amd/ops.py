@@ -69,6 +69,8 @@ class PackedConv:
     wsh: Optional[torch.Tensor] = None  # fp16 1x1 / stride-1 layers (C multiple of 64, <= 512): row-major fp16 [K, C] weights of seam_conv1x1_swh_f16
     wph: Optional[torch.Tensor] = None  # fp16 1x1 / stride-1 layers with C >= 512 (a multiple of 256), K a multiple of 128: fragment-order weights of seam_conv1x1_f16pc
     wx: Optional[torch.Tensor] = None   # SX6 1x1 / stride-1 layers with C >= 256 (a multiple of 64), K a multiple of 128: three bf16 planes in fragment order (seam_conv1x1_sxpc)
+    wxs: Optional[torch.Tensor] = None  # SX6 1x1 / stride-1 layers with C == 128, K a multiple of 128: the same planes (seam_conv1x1_sxpc_short, seam_conv1x1_sxpc_dual_short)
+    wx64: Optional[torch.Tensor] = None  # SX6 1x1 / stride-1 layers with K == 64, C >= 128 (a multiple of 64): the same planes, two n-tiles (seam_conv1x1_sxpc64, seam_stem_sxpc)
 
 
 BX3 = "bf16x3"      # fp32 activations, split-bf16 operands (3 bf16 MFMAs per product, fp32 accumulate)
@@ -107,6 +109,16 @@ PWHPC_MIN_C = int(_os.environ.get("SEAM_PWHPC_MIN_C", "1024"))  # reductions fro
 SXPC = _os.environ.get("SEAM_SXPC", "1") != "0"
 SXPC_MIN_TILES = int(_os.environ.get("SEAM_SXPC_MIN_TILES", "196"))
 SXPC_RULE = True
+# The 64-output-channel form (conv1x1_sxpc64) behind ``conv2d``: layer1's two 256 -> 64 reductions.  Off by default: at a step's
+# shape the kernel is level with conv_igemm_sx on them (profiles/stem_sxpc_layer_ab.txt); the form serves the stem
+# (``stem_s2d_sx``), which does not look at this knob.  SEAM_SXPC64=1 routes them (same bits; tile rule as above, 64-channel tiles).
+SXPC64 = _os.environ.get("SEAM_SXPC64", "0") != "0"
+# The two-chunk reductions (C == 128: layer2's 128 -> 512 expansions with their residual; 64 + 64: layer1.0's shortcut GEMM) on
+# conv1x1_sxpc / conv1x1_sxpc_dual through the `short` entries.  These layers' alternative is the EXACT conv1x1_sw, which rounds
+# differently, so the body picks their twin by the map alone (``sxpc_short_map_ok``: an image's result never depends on the batch it
+# rides in); on a twin, ``conv2d`` / ``conv2d_dual`` take the kernel by the usual rules and conv_igemm_sx (the same bits) otherwise.
+# SEAM_SXPC_SHORT=0: the exact kernels, as before the entries existed.
+SXPC_SHORT = _os.environ.get("SEAM_SXPC_SHORT", "1") != "0"
 F16PC_RULE = True      # dispatch by seam_conv3x3_f16pc_pays (False: every supported shape -- tests, tools/f16pc_ab.py)
 
 
@@ -184,6 +196,11 @@ def _wino_form(lib, pc: "PackedConv", n, h, w, c, pad) -> int:
     return 2 if pc.u24 is not None and WINOGRAD24 and _wino24_pays(lib, n, h, w, c, pc.K, pad) else 1
 
 
+def sxpc_short_map_ok(h: int, w: int, k: int) -> bool:
+    """A two-chunk expansion with K outputs on an h x w map runs its split twin: ONE image fills SXPC_MIN_TILES tiles."""
+    return bool(SXPC_SHORT and (-(-(h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE))
+
+
 def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out_f32) -> str:
     """The kernel one ``conv2d`` launch takes.  First match wins; this order IS the precedence.  Integers, bools, which pack fields
     exist, the knobs above (read now: tests and tools assign them) and the library's host predicates -- no tensor data, no stream."""
@@ -191,6 +208,12 @@ def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out
     if (dt == SX6 and pc.wx is not None and SXPC and not cropped and relu in (0, 1, False, True)
             and (-(-(n * h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_supported(n * h * w, c, k) == 1):
         return "sxpc"
+    if (dt == SX6 and pc.wx64 is not None and SXPC and SXPC64 and not cropped and relu in (0, 1, False, True)
+            and (-(-(n * h * w) // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc64_supported(n * h * w, c, k) == 1):
+        return "sxpc64"
+    if (dt == SX6 and pc.wxs is not None and SXPC and SXPC_SHORT and not cropped and relu in (0, 1, False, True)
+            and (-(-(n * h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_short_supported(n * h * w, c, k) == 1):
+        return "sxpc_short"
     f16k = dt == F16 and not out_f32 and relu in (0, 1, False, True)      # what the fp16 routes below need: fp16 out, ReLU a flag
     if f16k and not cropped:
         if (pc.wph is not None and PWHPC and not has_residual and c >= PWHPC_MIN_C and h * w >= SW_MIN_HW
@@ -217,7 +240,7 @@ def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out
 
 
 # routes of one instantiation: their CONV_TRACE labels
-_ROUTE_LABEL = {"sxpc": "conv1x1_sxpc", "pwhpc": "conv1x1_f16pc", "narrow": "linear_narrow", "pwpc": "conv1x1_pc", "f16pc": "conv3x3_f16pc"}
+_ROUTE_LABEL = {"sxpc": "conv1x1_sxpc", "sxpc64": "conv1x1_sxpc64", "sxpc_short": "conv1x1_sxpc_short", "pwhpc": "conv1x1_f16pc", "narrow": "linear_narrow", "pwpc": "conv1x1_pc", "f16pc": "conv3x3_f16pc"}
 
 
 def _conv_variant(lib, route: str, pc: "PackedConv", n, h, w, ho, wo) -> str:
@@ -312,7 +335,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
     conv1x1 = plain and mode == 0 and not is_linear
     # the weight as a row-major fp32 [K, Cin] matrix, made on first use; of a Conv2d / Linear weight it is a view: the SAME storage
     rows_kc = functools.cache(lambda: (weight.permute(2, 3, 1, 0).reshape(K, cin) if transposed2x2 else weight.reshape(K, cin)).to(F32).contiguous())
-    u = u24 = wh = wx = wn = ws = shift_sw = wq = wsh = wph = None      # the optional forms: each set below where the layer is eligible
+    u = u24 = wh = wx = wxs = wx64 = wn = ws = shift_sw = wq = wsh = wph = None      # the optional forms: each set below where the layer is eligible
     if dtype == F32:
         kred = lib.seam_conv_kred(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F32, device=weight.device)
@@ -336,6 +359,12 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         if SXPC and dtype == SX6 and (conv1x1 or (plain and transposed2x2)) and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K):
             wx = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
             _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(rows_kc()), _ptr(wx), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc")
+        if SXPC and dtype == SX6 and conv1x1 and lib.seam_conv1x1_sxpc_short_supported(1 << 20, cs, K):
+            wxs = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
+            _native.check(lib.seam_pack_conv1x1_weight_sxpc_short(_ptr(rows_kc()), _ptr(wxs), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc_short")
+        if SXPC and dtype == SX6 and conv1x1 and lib.seam_conv1x1_sxpc64_supported(1 << 20, cs, K):
+            wx64 = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
+            _native.check(lib.seam_pack_conv1x1_weight_sxpc64(_ptr(rows_kc()), _ptr(wx64), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc64")
     else:
         kred = lib.seam_conv_kred_f16(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F16, device=weight.device)
@@ -376,7 +405,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         wph = torch.empty((int(lib.seam_conv1x1_f16pc_weight_halves(K, cs)),), dtype=F16, device=weight.device)
         _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(rows_kc()), _ptr(wph), K, cs, _stream()), "seam_pack_conv1x1_weight_f16pc")
     pc = PackedConv(wp, scale, shift, K, cs, R, S, stride=stride, pad=pad, Cin=cin, dtype=dtype, u=u, u24=u24, wn=wn, ws=ws,
-                    shift_sw=shift_sw, wq=wq, wh=wh, wsh=wsh, wph=wph, wx=wx)
+                    shift_sw=shift_sw, wq=wq, wh=wh, wsh=wsh, wph=wph, wx=wx, wxs=wxs, wx64=wx64)
     if _PACK_RECORDER is not None:
         _PACK_RECORDER.records.append((weight, bias, bn, mode, pc))
     return pc
@@ -600,6 +629,12 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
     if route == "sxpc":
         _native.check(lib.seam_conv1x1_sxpc(_ptr(x), _ptr(pc.wx), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y), n * h * w, c, pc.K,
                                             1 if relu else 0, _stream()), "seam_conv1x1_sxpc")
+    elif route == "sxpc_short":
+        _native.check(lib.seam_conv1x1_sxpc_short(_ptr(x), _ptr(pc.wxs), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y), n * h * w, c, pc.K,
+                                                  1 if relu else 0, _stream()), "seam_conv1x1_sxpc_short")
+    elif route == "sxpc64":
+        _native.check(lib.seam_conv1x1_sxpc64(_ptr(x), _ptr(pc.wx64), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y), n * h * w, c, pc.K,
+                                              1 if relu else 0, _stream()), "seam_conv1x1_sxpc64")
     elif route == "pwhpc":
         _native.check(lib.seam_conv1x1_f16pc(_ptr(x), _ptr(pc.wph), _ptr(pc.scale), _ptr(pc.shift), None, _ptr(y), n * h * w, c, pc.K,
                                              1 if relu else 0, _stream()), "seam_conv1x1_f16pc")
@@ -667,6 +702,37 @@ def stem_s2d_f16(x: torch.Tensor, w_rows: torch.Tensor, scale: Optional[torch.Te
                                                  float(2 * (xp.numel() + w_rows.numel() + y.numel())))
     _native.check(_native.lib().seam_stem_s2d_swh_f16(_ptr(xp), _ptr(w_rows), _ptr(scale), _ptr(shift), _ptr(y), n, h2, w2,
                                                       1 if relu else 0, _stream()), "seam_stem_s2d_swh_f16")
+    if tr:
+        _trace_end(tr)
+    return y
+
+
+def stem_sx_ok(lib, pc: Optional["PackedConv"], n: int, hs: int, ws: int) -> bool:
+    """``stem_s2d_sx`` serves N frames of hs x ws space-to-depth cells on this pack: the twin of the [64, 192] rows with its
+    ``wx64``, ops.SXPC, a map of at least 128 output pixels (a rule on the map alone: a frame's result never depends on the batch it
+    rides in) and the library's geometry rule.  Integers, the knob and the host predicate only."""
+    return bool(pc is not None and pc.wx64 is not None and SXPC and pc.K == 64 and pc.Cstore == 192 and hs * ws >= 128
+                and lib.seam_stem_sxpc_supported(n, hs, ws) == 1)
+
+
+def stem_s2d_sx(x: torch.Tensor, pc: "PackedConv", relu: bool = True, padded: bool = False) -> torch.Tensor:
+    """ResNet stem of the fp32 path's split class ``stem`` on the space-to-depth frame ``x`` [N,Hs,Ws,12]: the 4x4 / stride-1
+    convolution as six-term split-bf16 products on the gather form of conv1x1_sxpc64 (``seam_stem_sxpc``).  ``padded``: ``x`` is the
+    frame with its zero cells already, [N,Hs+3,Ws+3,12] (``preprocess(..., s2d_pad=(2, 1))``), else one padding copy is made.
+    ``pc``: the SX6 pack of the [64, 192] rows in (r, s, c) order (``wx64``, scale, shift).  -> NHWC [N,Hs,Ws,64] fp32."""
+    x = _req(x, F32, "x")
+    n, hs, ws, c = x.shape
+    if padded:
+        hs, ws = hs - 3, ws - 3
+    lib = _native.lib()
+    if c != 12 or hs < 1 or ws < 1 or not stem_sx_ok(lib, pc, n, hs, ws):
+        raise ValueError("stem_s2d_sx: x must be [N,Hs,Ws,12] fp32 (padded: +3 cells per direction) on a served map, pc the twin of the [64,192] rows")
+    xp = x if padded else torch.nn.functional.pad(x, (0, 0, 2, 1, 2, 1))
+    y = torch.empty((n, hs, ws, 64), dtype=F32, device=x.device)
+    tr = CONV_TRACE is not None and _trace_begin("stem_sxpc", 2.0 * n * hs * ws * 64 * 16 * 12, (n, hs, ws, 12, 64, 4, 1),
+                                                 float(4 * (xp.numel() + y.numel()) + pc.wx64.numel()))
+    _native.check(lib.seam_stem_sxpc(_ptr(xp), _ptr(pc.wx64), _ptr(pc.scale), _ptr(pc.shift), _ptr(y), n, hs, ws, 1 if relu else 0,
+                                     _stream()), "seam_stem_sxpc")
     if tr:
         _trace_end(tr)
     return y
@@ -803,6 +869,17 @@ def conv2d_dual(x1: torch.Tensor, x2: torch.Tensor, pc: PackedConv, stride2: int
             if tr:
                 _trace_end(tr)
             return y
+        if (SXPC and SXPC_SHORT and pc.wxs is not None and stride2 == 1 and relu in (0, 1, False, True)
+                and lib.seam_conv1x1_sxpc_dual_short_supported(n * ho * wo, c1, c2, pc.K) == 1 and _sxpc_dual_map_ok(n, ho, wo, h2, w2, c2)):
+            y = torch.empty((n, ho, wo, pc.K), dtype=F32, device=x1.device)
+            tr = CONV_TRACE is not None and _trace_begin(
+                "conv1x1_sxpc_dual_short", 2.0 * n * ho * wo * pc.K * (c1 + c2), (n, ho, wo, c1 + c2, pc.K, 1, 1),
+                float(x1.element_size() * (x1.numel() + n * ho * wo * c2 + pc.K * (c1 + c2) + y.numel())))
+            _native.check(lib.seam_conv1x1_sxpc_dual_short(_ptr(x1), _ptr(x2), _ptr(pc.wxs), _ptr(pc.scale), _ptr(pc.shift), _ptr(y), n, ho, wo,
+                                                           c1, h2, w2, c2, pc.K, 1 if relu else 0, _stream()), "seam_conv1x1_sxpc_dual_short")
+            if tr:
+                _trace_end(tr)
+            return y
         return conv2d(torch.cat([x1, x2[:, :(ho - 1) * stride2 + 1:stride2, :(wo - 1) * stride2 + 1:stride2]], -1), pc, relu=relu)
     y = torch.empty((n, ho, wo, pc.K), dtype=dt, device=x1.device)
     same = stride2 == 1 and (h2, w2) == (ho, wo)      # the pointwise kernels read both inputs on the output grid
@@ -866,8 +943,8 @@ def preprocess(images: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, 
                s2d_pad: tuple = (0, 0)) -> torch.Tensor:
     """normalise + resize + pad + CHW->NHWC for a list of fp32 images -> [N,hp,wp,4] fp32 / [N,hp,wp,8] fp16.
     ``s2d`` (fp32 [3,H,W] images only): the space-to-depth layout [N,hp/2,wp/2,12] of ``seam_preprocess_s2d_batch_f32``
-    (fp16: [N,hp/2,wp/2,16], four zero channels, ``_f16``); ``s2d_pad`` = (lo, hi) (fp16 only): zero cells before / after the frame
-    in both directions -- [N, hp/2 + lo + hi, wp/2 + lo + hi, 16], the input of ``stem_s2d_f16(..., padded=True)``."""
+    (fp16: [N,hp/2,wp/2,16], four zero channels, ``_f16``); ``s2d_pad`` = (lo, hi): zero cells before / after the frame in both
+    directions -- [N, hp/2 + lo + hi, wp/2 + lo + hi, 12 | 16], the input of ``stem_s2d_sx`` / ``stem_s2d_f16`` with ``padded=True``."""
     lib = _native.lib()
     # device check FIRST, for every image and every branch below: a CPU tensor must raise SeamNativeError, never reach a
     # kernel as a raw host pointer (the one-launch batch branches take data_ptr() of the views directly)
@@ -878,13 +955,15 @@ def preprocess(images: Sequence[torch.Tensor], sizes: Sequence[tuple], hp: int, 
         if dtype not in (F32, F16) or hp % 2 or wp % 2 or any(i.dtype != F32 or i.dim() != 3 or i.shape[0] != 3 for i in images):
             raise ValueError("preprocess(s2d=True): fp32 [3,H,W] images and an even padded size")
         n = len(images)
-        plo, phi = (int(s2d_pad[0]), int(s2d_pad[1])) if dtype == F16 else (0, 0)
+        plo, phi = int(s2d_pad[0]), int(s2d_pad[1])
         out = torch.empty((n, hp // 2 + plo + phi, wp // 2 + plo + phi, 12 if dtype == F32 else 16), dtype=dtype, device=images[0].device)
-        if dtype == F32:
+        if dtype == F32 and not (plo or phi):
             s2d_fn = lib.seam_preprocess_s2d_batch_f32
         else:
+            pad_fn = lib.seam_preprocess_s2d_pad_batch_f32 if dtype == F32 else lib.seam_preprocess_s2d_pad_batch_f16
+
             def s2d_fn(src, stride, dst, cnt, ih, iw, oh, ow, hpp, wpp, st):
-                return lib.seam_preprocess_s2d_pad_batch_f16(src, stride, dst, cnt, ih, iw, oh, ow, hpp, wpp, plo, phi, st)
+                return pad_fn(src, stride, dst, cnt, ih, iw, oh, ow, hpp, wpp, plo, phi, st)
         same = n <= 65535 and all(i.shape == images[0].shape and i.is_contiguous() for i in images) \
             and all(tuple(z) == tuple(sizes[0]) for z in sizes)
         p0 = images[0].data_ptr()
@@ -2876,6 +2955,10 @@ class PackPlan:
             jobs = [job(N.REPACK_SPLIT3, pc.w, pc.R, pc.S, md=mode)]
             if pc.wx is not None:
                 jobs.append(job(N.REPACK_SXPC, pc.wx))
+            if pc.wxs is not None:
+                jobs.append(job(N.REPACK_SXPC64, pc.wxs))
+            if pc.wx64 is not None:
+                jobs.append(job(N.REPACK_SXPC64, pc.wx64))
             return jobs
         if pc.dtype != F32 or pc.wh is not None or pc.wsh is not None or pc.wph is not None:
             raise NotImplementedError(f"PackPlan: {path}: only fp32 packs are refreshed in place (pass refresh_packs=False)")

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Timing-only builds of conv1x1_sxpc (csrc/seam_pwsx.hip) with parts of its work compiled out (SEAM_SXPC_ABL bits: 1 no row staging,
 # 2 no in-loop weight loads, 4 no split VALU, 8 no in-loop A-fragment reads), one small library each under tools/experiments/_lib/
-# (kept out of git).  Their outputs are wrong by construction; tools/sxpc_ab.py --abl name=lib times them beside the shipped kernel.
+# (kept out of git).  Their outputs are wrong by construction; tools/sxpc_ab.py --abl name=lib times them beside the shipped kernel
+# (tools/sxpc64_ab.py --abl: the stem kernel of the same file).
 # usage: tools/sxpc_abl_build.sh      (on any machine with hipcc; no GPU needed)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
