@@ -1135,13 +1135,49 @@ int seam_rle_bits_area(const int* obj_hw_host, const int* obj_hw, const int64_t*
  * 0..SEAM_SGD_MAX_SLOTS, a NULL table with n_chunks > 0.  n_chunks == 0: no-op. */
 #define SEAM_SGD_MAX_SLOTS 32
 #define SEAM_SGD_FP_SLOTS 64
-typedef struct { float* p; const float* g; float* buf; int64_t numel; int group; int reserved; } seam_sgd_tensor_t;
+typedef struct { float* p; const float* g; float* buf; int64_t numel; int group; int slot; } seam_sgd_tensor_t;   /* slot: the clipped step's pending_first index; 0 elsewhere */
 typedef struct { int tensor; int count; int64_t offset; } seam_sgd_chunk_t;
 typedef struct { float lr, momentum, one_minus_dampening, weight_decay; int nesterov, maximize, first, reserved; } seam_sgd_group_t;
 typedef struct { int n; int reserved[3]; seam_sgd_group_t g[SEAM_SGD_MAX_SLOTS]; } seam_sgd_groups_t;
 int seam_sgd_chunk_elems(void);
 int seam_sgd_step_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* chunks, int n_chunks,
                       const seam_sgd_groups_t* groups, unsigned long long* fingerprint, seam_stream_t stream);
+
+/* ---- Gradient clipping by global norm and non-finite steps (torch.nn.utils.clip_grad_norm_; ref stuffs/engine.py:176-181) --------
+ * All entries walk the tensor and chunk tables of seam_sgd_step_f32 and use no float atomics.
+ * seam_clip_record_t (DEVICE, 8-byte aligned): what the norm leaves for the launches behind it.
+ *   total_norm  the global norm over every element of every tensor's g, rounded to fp32 once
+ *   clip_coef   clip ? min(1, reciprocal(total_norm + 1e-6f) * max_norm) : 1 -- torch's max_norm / (total_norm + 1e-6) is
+ *               Tensor.__rtruediv__, a reciprocal and a multiply, each rounded to fp32; the clamp keeps NaN (total NaN -> NaN,
+ *               total inf -> 0)
+ *   finite      0 when total_norm is inf or NaN
+ *   nonfinite_steps   keep_count ? previous value + !finite : !finite
+ * seam_grad_norm_f32: two launches.  Stage 1 (the grid of seam_sgd_step_f32): one fp64 partial per chunk in `workspace`
+ *   (seam_grad_norm_workspace_bytes(n_chunks) bytes, 8-byte aligned): norm_inf == 0 the sum of the exact fp64 squares, lane sums in
+ *   index order and a fixed tree over lanes and waves; norm_inf != 0 max |g|, NaN if any element is NaN (an explicit flag).  Stage 2
+ *   (one block): the partials in chunk order per lane, the same fixed tree, sqrt in fp64 (norm 2), the record.  Two calls on the
+ *   same data at the same addresses give the same bits.  Reads nothing outside [g, g + numel); p and buf are not touched.
+ *   n_chunks == 0: total_norm 0.
+ * seam_grad_scale_f32: g *= record->clip_coef in place (one rounded multiply per element), nothing else written.
+ * seam_sgd_step_clip_f32: seam_sgd_step_f32 on g' = g * record->clip_coef (one rounded multiply, what g.mul_(clip_coef) stores; g
+ *   itself is only read).  skip_nonfinite != 0 and record->finite == 0: neither p nor buf is written and both fingerprint sums are
+ *   the "as read" one.  pending_in / pending_out: two distinct DEVICE int arrays indexed by tensors[t].slot (the caller keeps every
+ *   slot inside them).  A tensor is "first" (buf written, not read) when its group slot's `first` is set or pending_in[slot] != 0;
+ *   pending_out[slot] = 1 when the launch skipped and the tensor has a buffer and is first, else 0 -- the same value from every
+ *   chunk of the tensor.  The caller swaps the two arrays after each call, so a buffer created on a skipped step is written
+ *   (buf = g') by the first applied step, whatever dampening and nesterov say.
+ * Refused: what seam_sgd_step_f32 refuses; a NULL record / workspace / pending array, pending_in == pending_out, a workspace that
+ *   is too small or either pointer not 8-byte aligned. */
+typedef struct { float total_norm; float clip_coef; int finite; int reserved; unsigned long long nonfinite_steps; } seam_clip_record_t;
+int64_t seam_grad_norm_workspace_bytes(int n_chunks);
+int seam_grad_norm_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* chunks, int n_chunks, int norm_inf, int clip,
+                       float max_norm, int keep_count, void* workspace, int64_t workspace_bytes, seam_clip_record_t* record,
+                       seam_stream_t stream);
+int seam_grad_scale_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* chunks, int n_chunks,
+                        const seam_clip_record_t* record, seam_stream_t stream);
+int seam_sgd_step_clip_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chunk_t* chunks, int n_chunks,
+                           const seam_sgd_groups_t* groups, unsigned long long* fingerprint, const seam_clip_record_t* record,
+                           int skip_nonfinite, const int* pending_in, int* pending_out, seam_stream_t stream);
 
 /* seam_repack_many_f32: the fp32 weight packs of a list of (layer, form) jobs in one launch, each job's bytes equal to its
  * per-layer entry's: IGEMM = seam_pack_conv_weight_f32 (modes 0, 1, 2), SPLIT3 = seam_pack_conv_weight_sx (computed from the

@@ -33,7 +33,7 @@ SGD_FP_SLOTS = 64       # SEAM_SGD_FP_SLOTS
 
 class SgdTensor(C.Structure):
     """seam_sgd_tensor_t of include/seam_hip.h."""
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("numel", C.c_int64), ("group", C.c_int), ("reserved", C.c_int)]
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("numel", C.c_int64), ("group", C.c_int), ("slot", C.c_int)]
 
 
 class SgdChunk(C.Structure):
@@ -50,6 +50,12 @@ class SgdGroup(C.Structure):
 class SgdGroups(C.Structure):
     """seam_sgd_groups_t of include/seam_hip.h."""
     _fields_ = [("n", C.c_int), ("reserved", C.c_int * 3), ("g", SgdGroup * SGD_MAX_SLOTS)]
+
+
+class ClipRecord(C.Structure):
+    """seam_clip_record_t of include/seam_hip.h (six int32 words on the device: norm, coefficient, finite, pad, 64-bit count)."""
+    _fields_ = [("total_norm", C.c_float), ("clip_coef", C.c_float), ("finite", C.c_int), ("reserved", C.c_int),
+                ("nonfinite_steps", C.c_uint64)]
 
 
 REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC, REPACK_SXPC64 = range(9)     # SEAM_REPACK_*
@@ -253,6 +259,10 @@ SIGNATURES = {
     "seam_rle_bits_area": (_i, [_p, _p, _p, _p, _i64, _i, _p, _p]),
     "seam_sgd_chunk_elems": (_i, []),
     "seam_sgd_step_f32": (_i, [_p, _p, _i, C.POINTER(SgdGroups), _p, _p]),
+    "seam_sgd_step_clip_f32": (_i, [_p, _p, _i, C.POINTER(SgdGroups), _p, _p, _i, _p, _p, _p]),
+    "seam_grad_norm_workspace_bytes": (_i64, [_i]),
+    "seam_grad_norm_f32": (_i, [_p, _p, _i, _i, _i, C.c_float, _i, _p, _i64, _p, _p]),
+    "seam_grad_scale_f32": (_i, [_p, _p, _i, _p, _p]),
     "seam_repack_layout": (C.c_longlong, [C.POINTER(RepackJob), _i]),
     "seam_repack_many_f32": (_i, [_p, _i, C.c_longlong, _p]),
 }
