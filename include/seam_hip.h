@@ -666,6 +666,21 @@ int seam_conv3x3_wino24_f32(const float* x, const float* u_packed, const float* 
                             const float* residual, float* y, int N, int H, int W, int C, int K, int pad, int relu,
                             seam_stream_t stream);
 
+/* conv3x3_wino24sx (csrc/seam_wino24sx.hip): the same F(2x4,3x3) convolution with its 24 position GEMMs as six-term split-bf16
+ * products on the bf16 matrix pipe -- V in fp32 by seam_conv3x3_wino24_f32's transform, cut into three bf16 pieces; U cut at pack
+ * time from the fp32 value seam_pack_conv_weight_wino24_f32 writes; the products (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) per k-step of 16
+ * channels accumulated in fp32.  Results differ from seam_conv3x3_wino24_f32's in the last bits (measured against float64: within 3x
+ * its error).  Shapes: C and K multiples of 64 from 64 on, stride 1, pad 0 | 1, any batch; _supported returns 1 for them, else 0, and
+ * the launcher returns hipErrorInvalidValue with nothing launched.
+ *   u_packed: seam_wino24sx_weight_bytes(K, Cstore) = 144 K Cstore bytes from seam_pack_conv_weight_wino24_sx
+ *   ([K/32][Cstore/16][24 positions][3 planes][64 lanes][8 bf16]; mode as seam_pack_conv_weight_wino24_f32). */
+long long seam_wino24sx_weight_bytes(int K, int Cstore);
+int seam_pack_conv_weight_wino24_sx(const float* w, void* u_packed, int K, int Cin, int Cstore, int mode, seam_stream_t stream);
+int seam_conv3x3_wino24sx_supported(int N, int H, int W, int C, int K, int pad, int stride);
+long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pad);   /* blocks of the launch; 0 = unsupported */
+int seam_conv3x3_wino24sx_f32(const float* x, const void* u_packed, const float* scale, const float* shift, const float* residual,
+                              float* y, int N, int H, int W, int C, int K, int pad, int stride, int relu, seam_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * 3x3 / stride-1 convolution, fp16 operands / fp32 accumulation, producer / consumer form (csrc/seam_f16pc.hip, round 5): the
  * config-5 path's 3x3 layers (ResNet / FPN / RPN / mask head / match trunk; ref models/video_matchrcnn.py:337-338,
@@ -1190,7 +1205,8 @@ int seam_sgd_step_clip_f32(const seam_sgd_tensor_t* tensors, const seam_sgd_chun
 enum { SEAM_REPACK_IGEMM = 0, SEAM_REPACK_WINO = 1, SEAM_REPACK_WINO24 = 2, SEAM_REPACK_PC = 3, SEAM_REPACK_SW = 4,
        SEAM_REPACK_SPLIT3 = 5, SEAM_REPACK_NARROW = 6, SEAM_REPACK_SXPC = 7,
        SEAM_REPACK_SXPC64 = 8 /* the same item function for the shapes of seam_conv1x1_sxpc64_supported (K == 64) and of
-                                 seam_conv1x1_sxpc_short_supported (C == 128) */ };
+                                 seam_conv1x1_sxpc_short_supported (C == 128) */,
+       SEAM_REPACK_W24SX = 9 /* seam_pack_conv_weight_wino24_sx (R = S = 3, modes 0 and 2) */ };
 typedef struct {
     const float* src; void* dst; const float* scale;
     int64_t items;

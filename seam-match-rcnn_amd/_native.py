@@ -58,7 +58,7 @@ class ClipRecord(C.Structure):
                 ("nonfinite_steps", C.c_uint64)]
 
 
-REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC, REPACK_SXPC64 = range(9)     # SEAM_REPACK_*
+REPACK_IGEMM, REPACK_WINO, REPACK_WINO24, REPACK_PC, REPACK_SW, REPACK_SPLIT3, REPACK_NARROW, REPACK_SXPC, REPACK_SXPC64, REPACK_W24SX = range(10)     # SEAM_REPACK_*
 
 
 class RepackJob(C.Structure):
@@ -143,6 +143,11 @@ SIGNATURES = {
     "seam_wino24_weight_floats": (C.c_longlong, [_i, _i]),
     "seam_pack_conv_weight_wino24_f32": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "seam_conv3x3_wino24_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "seam_wino24sx_weight_bytes": (C.c_longlong, [_i, _i]),
+    "seam_pack_conv_weight_wino24_sx": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "seam_conv3x3_wino24sx_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "seam_conv3x3_wino24sx_blocks": (C.c_longlong, [_i, _i, _i, _i, _i, _i]),
+    "seam_conv3x3_wino24sx_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv3x3_wino_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv3x3_f16pc_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "seam_conv3x3_f16pc_pays": (_i, [_i, _i, _i, _i, _i, _i]),

@@ -114,6 +114,16 @@ __device__ __forceinline__ void wino_item(const float* __restrict__ w, float* __
     }
 }
 
+// one row of (G g) times G4t: the six F(4,3) weight points of F(2x4,3x3), in fp64
+__device__ __forceinline__ void wino24_g4(double a0, double a1, double a2, double uu[6]) {
+    uu[0] = a0 / 4.0;
+    uu[1] = -(a0 + a1 + a2) / 6.0;
+    uu[2] = -(a0 - a1 + a2) / 6.0;
+    uu[3] = a0 / 24.0 + a1 / 12.0 + a2 / 6.0;
+    uu[4] = a0 / 24.0 - a1 / 12.0 + a2 / 6.0;
+    uu[5] = a2;
+}
+
 // F(2x4,3x3): item i = (tn, chunk, lane) of [K/32][Cstore/8][24][64][4]; fp64 arithmetic, one rounding
 __device__ __forceinline__ void wino24_item(const float* __restrict__ w, float* __restrict__ out, size_t i, int K, int Cin, int nch, int mode) {
     const int lane = (int)(i & 63);
@@ -130,15 +140,46 @@ __device__ __forceinline__ void wino24_item(const float* __restrict__ w, float* 
         for (int q = 0; q < 4; ++q) {
             const double a0 = gg[q][0], a1 = gg[q][1], a2 = gg[q][2];
             double uu[6];
-            uu[0] = a0 / 4.0;
-            uu[1] = -(a0 + a1 + a2) / 6.0;
-            uu[2] = -(a0 - a1 + a2) / 6.0;
-            uu[3] = a0 / 24.0 + a1 / 12.0 + a2 / 6.0;
-            uu[4] = a0 / 24.0 - a1 / 12.0 + a2 / 6.0;
-            uu[5] = a2;
+            wino24_g4(a0, a1, a2, uu);
             const size_t base = ((((size_t)tn * nch + chunk) * 24 + q * 6) * 64 + lane) * 4 + e;
 #pragma unroll
             for (int nu = 0; nu < 6; ++nu) out[base + (size_t)nu * 256] = (float)uu[nu];
+        }
+    }
+}
+
+// split F(2x4,3x3) form (conv3x3_wino24sx): item i = (tn, k-step, lane) of [K/32][C/16][24 positions][3 planes][64 lanes][8 bf16].
+// k slot e of lane (n, h = lane >> 5) is channel 16 step + 4 h + e (e < 4) or 16 step + 8 + 4 h + (e - 4): the two 8-channel chunks
+// of the k-step side by side, as the kernel's lanes hold them.  Each value is wino24_item's (fp64 arithmetic, one rounding to fp32)
+// cut into its three bf16 pieces (the truncation split of split3_bf16): the planes sum back to it bit for bit.
+__device__ __forceinline__ void wino24sx_item(const float* __restrict__ w, unsigned short* __restrict__ out, size_t i, int K, int Cin, int nks, int mode) {
+    const int lane = (int)(i & 63);
+    const size_t rest = i >> 6;
+    const int step = (int)(rest % nks);
+    const int tn = (int)(rest / nks);
+    const int n = tn * 32 + (lane & 31);
+    unsigned short* o = out + ((size_t)tn * nks + step) * (24 * 3 * 512) + lane * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = step * 16 + (e >> 2) * 8 + (lane >> 5) * 4 + (e & 3);
+        double gg[4][3];
+        wino_gg(w, n, c, K, Cin, mode, gg);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            double uu[6];
+            wino24_g4(gg[q][0], gg[q][1], gg[q][2], uu);
+#pragma unroll
+            for (int nu = 0; nu < 6; ++nu) {
+                const float x = (float)uu[nu];
+                const float x0 = top16(x);
+                const float r = x - x0;
+                const float y0 = top16(r);
+                const float s = r - y0;
+                unsigned short* d = o + (size_t)(q * 6 + nu) * 1536 + e;
+                d[0] = (unsigned short)(__builtin_bit_cast(unsigned, x0) >> 16);
+                d[512] = (unsigned short)(__builtin_bit_cast(unsigned, y0) >> 16);
+                d[1024] = (unsigned short)(__builtin_bit_cast(unsigned, s) >> 16);
+            }
         }
     }
 }

@@ -46,6 +46,9 @@ __global__ __launch_bounds__(256) void repack_many_kernel(const seam_repack_job_
     case SEAM_REPACK_WINO24:
         for (size_t i = i0; i < total; i += step) seam_pack::wino24_item(src, (float*)j.dst, i, j.K, j.Cin, j.Cstore / 8, j.mode);
         break;
+    case SEAM_REPACK_W24SX:
+        for (size_t i = i0; i < total; i += step) seam_pack::wino24sx_item(src, (unsigned short*)j.dst, i, j.K, j.Cin, j.Cstore / 16, j.mode);
+        break;
     case SEAM_REPACK_PC:
         for (size_t i = i0; i < total; i += step) seam_pack::pwpc_item(src, (float*)j.dst, i, j.Cstore);
         break;
@@ -83,6 +86,9 @@ long long job_items(seam_repack_job_t& j) {
         if (j.R != 3 || j.S != 3 || (j.mode != 0 && j.mode != 2) || !seam_wino_supported(j.Cstore, j.K, 3, 3, 1)) return 0;
         if ((j.K % 32) || (j.Cstore % 8)) return 0;
         return (long long)(j.K / 32) * (j.Cstore / 8) * 64;
+    case SEAM_REPACK_W24SX:
+        if (j.R != 3 || j.S != 3 || (j.mode != 0 && j.mode != 2) || !seam_conv3x3_wino24sx_supported(1, 16, 16, j.Cstore, j.K, 1, 1)) return 0;
+        return (long long)(j.K / 32) * (j.Cstore / 16) * 64;
     case SEAM_REPACK_PC:
         if (!plain || (j.K % 128) || (j.Cstore % 128) || (((uintptr_t)j.src | (uintptr_t)j.dst) & 15)) return 0;
         return (long long)j.K * j.Cstore / 4;

@@ -65,11 +65,18 @@ def adt(module) -> torch.dtype:
 # stem = the ResNet stem in its space-to-depth form on stem_sxpc (ops.stem_s2d_sx: SX6, ops.SXPC, maps of >= 128 cells); the
 # transform then writes the fp32 frame with its zero cells, and a padded frame that meets a call the split kernels do not serve
 # runs the exact implicit GEMM over it as a valid convolution -- the bits of the unpadded frame's exact stem.
+# c2 / fpn3 / rpn3 / mask3 = the stride-1 3x3 layers that run F(2x4,3x3) -- the body's conv2s, the FPN's four output convs, the RPN
+# head's conv, the mask head's four convs -- on conv3x3_wino24sx (``w24sx_twin`` / ``pick_w24sx``: SX6 twins with ``u24x``; a call
+# takes the twin by ``ops.w24sx_map_ok``, the map geometry alone, and the exact pack elsewhere).  fpn3 and rpn3 are on by default: their 200^2 and 100^2 maps meet the
+# rule (ops.W24SX_MIN_BLOCKS).  c2 and mask3 are packed on request (SEAM_SPLIT_CLASSES): none of their maps in a step meets it
+# (100^2 x 128 and smaller; 14^2 ROI maps), so they move only with the knob lowered -- 1.10-1.30x at a step's batch, slower on a few
+# images.  The match trunks' valid 3x3s run inside seam_match_trunk_f32 and stay on the
+# fp32 kernels.
 SPLIT_F32 = _os.environ.get("SEAM_SPLIT_F32", "1") != "0"
 SPLIT_DTYPE = {"6": ops.SX6, "9": ops.SX9}[_os.environ.get("SEAM_SPLIT_TERMS", "6")]
 SPLIT_C3_MIN_C = 256      # the expansions of layer3 / layer4; layer2's (C = 128) have a twin of their own on ops.SXPC_SHORT, layer1's (C = 64) stay on conv1x1_sw
 SPLIT_C3DS_MIN_C = 384    # C1 + C2 of the served shortcut GEMMs: a rule on the layer's geometry alone, never on the batch
-SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds,lat,mdeconv,stem").split(",") if c)
+SPLIT_CLASSES = frozenset(c for c in _os.environ.get("SEAM_SPLIT_CLASSES", "c1,c3,c2s2,c3ds,lat,mdeconv,stem,fpn3,rpn3").split(",") if c)
 
 
 def split_on(module) -> bool:
@@ -90,6 +97,22 @@ def split_twin(module, cls) -> bool:
 def pick_pack(module, exact, twin=None):
     """The pack a call runs on: the split twin when one was packed and ``split_on(module)`` holds, else the exact pack."""
     return twin if twin is not None and split_on(module) else exact
+
+
+def w24sx_twin(module, cls, weight, bias=None, bn=None, pad=1, bn_eps=1e-5):
+    """The conv3x3_wino24sx twin (class ``cls``) of a stride-1 3x3 layer beside its exact pack, or None where none is packed."""
+    if not (split_twin(module, cls) and ops.W24SX) or weight.shape[1] < ops.W24SX_MIN_C:      # (shorter reductions never take it)
+        return None
+    pc = ops.pack_conv(weight, bias, bn, pad=pad, bn_eps=bn_eps, dtype=ops.SX6, w24sx=True)
+    return pc if pc.u24x is not None else None
+
+
+def pick_w24sx(module, exact, twin, x):
+    """The pack a stride-1 3x3 call on the NHWC map ``x`` runs on: the twin where one was packed, ``split_on(module)`` holds and
+    the map's geometry sends the layer to conv3x3_wino24sx (``ops.w24sx_map_ok``: never the batch), else the exact pack."""
+    if twin is not None and split_on(module) and ops.w24sx_map_ok(x.shape[1], x.shape[2], exact.Cstore, exact.K, exact.pad):
+        return twin
+    return exact
 
 
 def set_split_f32(model: nn.Module, on: bool) -> nn.Module:
@@ -255,7 +278,7 @@ class ResNet50Body(PackedWeights, nn.Module):
         return [t for m in self.modules() for t in (*m._parameters.values(), *m._buffers.values()) if t is not None]
 
     def _pack_switches(self):
-        return (cdt(self), SPLIT_DTYPE, FUSE_SHORTCUT, STEM_SWH) + tuple(split_twin(self, c) for c in self.SPLIT_TWINS)
+        return (cdt(self), SPLIT_DTYPE, FUSE_SHORTCUT, STEM_SWH, ops.W24SX, split_twin(self, "c2")) + tuple(split_twin(self, c) for c in self.SPLIT_TWINS)
 
     def _build_packs(self):
         dt = cdt(self)
@@ -302,6 +325,10 @@ class ResNet50Body(PackedWeights, nn.Module):
                 if c2x and b.stride == 2:
                     e["c2x"] = ops.pack_conv(b.conv2.weight, None, b.bn2.tensors(), stride=2, pad=1, bn_eps=b.bn2.eps,
                                              dtype=SPLIT_DTYPE)
+                if b.stride == 1:      # class c2: the F(2x4,3x3) layers on conv3x3_wino24sx, picked per map in _run
+                    tw = w24sx_twin(self, "c2", b.conv2.weight, None, b.bn2.tensors(), pad=1, bn_eps=b.bn2.eps)
+                    if tw is not None:
+                        e["c2w"] = tw
                 if c3x and "c3ds" not in e and b.conv3.in_channels >= SPLIT_C3_MIN_C:
                     e["c3x"] = ops.pack_conv(b.conv3.weight, None, b.bn3.tensors(), bn_eps=b.bn3.eps, dtype=SPLIT_DTYPE)
                 if c3x and "c3ds" not in e and b.conv3.in_channels == 128 and SPLIT_DTYPE == ops.SX6:
@@ -379,7 +406,8 @@ class ResNet50Body(PackedWeights, nn.Module):
             for bi in range(nblk):
                 e = pk[(li, bi)]
                 o = ops.conv2d(x, pick_pack(self, e["c1"], e.get("c1x")), relu=True)
-                o = ops.conv2d(o, pick_pack(self, e["c2"], e.get("c2x")), relu=True)
+                c2 = pick_w24sx(self, e["c2"], e["c2w"], o) if "c2w" in e else pick_pack(self, e["c2"], e.get("c2x"))
+                o = ops.conv2d(o, c2, relu=True)
                 if "c3ds" in e:       # projection-shortcut block: bn3(conv3(o)) + bn_d(conv_d(x)) + ReLU in one launch
                     twin = e.get("c3dsx") or (e.get("c3dsxs") if ops.SXPC_SHORT else None)
                     x = ops.conv2d_dual(o, x, pick_pack(self, e["c3ds"], twin), getattr(self, f"layer{li}")[bi].stride, relu=True)
@@ -496,13 +524,15 @@ class FeaturePyramidNetwork(PackedWeights, nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
     def _pack_switches(self):
-        return (cdt(self), split_twin(self, "lat"))
+        return (cdt(self), split_twin(self, "lat"), split_twin(self, "fpn3"), ops.W24SX)
 
     def _build_packs(self):
         """(lateral packs, output packs, split twins of the lateral packs or None): the twins (class ``lat``) are packed beside the
         exact packs from the same parameters; ``forward`` takes them under ``split_on``, ``forward_taped`` never does."""
         dt, twin = cdt(self), split_twin(self, "lat")
         inner = [ops.pack_conv(m.weight, m.bias, dtype=(dt, ops.SX6) if twin else (dt,)) for m in self.inner_blocks]
+        # class fpn3: the conv3x3_wino24sx twins of the output convs, kept beside the tuple (built and dropped with it)
+        self._out_twins = [w24sx_twin(self, "fpn3", m.weight, m.bias, pad=1) for m in self.layer_blocks]
         return ([p[0] for p in inner],
                 [ops.pack_conv(m.weight, m.bias, pad=1, dtype=dt) for m in self.layer_blocks],
                 [p[1] for p in inner] if twin else None)
@@ -510,13 +540,14 @@ class FeaturePyramidNetwork(PackedWeights, nn.Module):
     def forward(self, feats: List[torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
         inner, layer, twins = self.packed()
         inner = pick_pack(self, inner, twins)
+        out_pack = lambda i, x: pick_w24sx(self, layer[i], self._out_twins[i], x)
         x3 = feats[3]
         if not (LEVEL_STREAMS and x3.is_cuda):
             last = ops.conv2d(x3, inner[3])
-            outs = [None, None, None, ops.conv2d(last, layer[3])]
+            outs = [None, None, None, ops.conv2d(last, out_pack(3, last))]
             for i in (2, 1, 0):
                 last = ops.conv2d_topdown(feats[i], inner[i], last)      # lateral 1x1 + nearest top-down merge, one launch
-                outs[i] = ops.conv2d(last, layer[i])
+                outs[i] = ops.conv2d(last, out_pack(i, last))
             od = OrderedDict((str(i), o) for i, o in enumerate(outs))
             od["pool"] = ops.maxpool2d(outs[3], 1, 2, 0)          # LastLevelMaxPool
             return od
@@ -539,11 +570,11 @@ class FeaturePyramidNetwork(PackedWeights, nn.Module):
                 keep.append(last)
                 last = ops.conv2d_topdown(feats[i], inner[i], last)
             if i == 0:
-                ops.conv2d(last, layer[0], out=outs[0])
+                ops.conv2d(last, out_pack(0, last), out=outs[0])
                 break
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                ops.conv2d(last, layer[i], out=outs[i])
+                ops.conv2d(last, out_pack(i, last), out=outs[i])
                 if i == 3:
                     pool = ops.maxpool2d(outs[3], 1, 2, 0)      # LastLevelMaxPool
         cur.wait_stream(side)
@@ -624,7 +655,12 @@ class RPNHead(PackedWeights, nn.Module):
                                (self.cls_logits.weight, self.bbox_pred.weight))
         b = ops.derived_source(lambda: torch.cat([self.cls_logits.bias, self.bbox_pred.bias], 0).detach(),
                                (self.cls_logits.bias, self.bbox_pred.bias))
+        # class rpn3: the conv3x3_wino24sx twin of the head conv, kept beside the pair (built and dropped with it)
+        self._conv_twin = w24sx_twin(self, "rpn3", self.conv.weight, self.conv.bias, pad=1)
         return ops.pack_conv(self.conv.weight, self.conv.bias, pad=1, dtype=dt), ops.pack_conv(w, b, dtype=dt)
+
+    def _pack_switches(self):
+        return (cdt(self), split_twin(self, "rpn3"), ops.W24SX)
 
     def forward(self, feats: Sequence[torch.Tensor]):
         """-> per level ([N,H,W,A] objectness, [N,H,W,4A] deltas), NHWC == torchvision's
@@ -634,18 +670,19 @@ class RPNHead(PackedWeights, nn.Module):
 
     def fused(self, feats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
         """-> per level the fused head output [N,H,W,A+4A] fp32 (objectness logits | deltas of each pixel)."""
-        conv, heads = self.packed()
+        conv0, heads = self.packed()
+        conv = lambda f: pick_w24sx(self, conv0, self._conv_twin, f)
         feats = list(feats)
         if not (LEVEL_STREAMS and len(feats) > 1 and feats[0].is_cuda):
-            return [ops.conv2d(ops.conv2d(f, conv, relu=True), heads, out_f32=True) for f in feats]     # logits/deltas leave in fp32
+            return [ops.conv2d(ops.conv2d(f, conv(f), relu=True), heads, out_f32=True) for f in feats]     # logits/deltas leave in fp32
         # level 0 on the calling stream, the smaller levels on the side stream (see LEVEL_STREAMS)
         cur, side = torch.cuda.current_stream(), _side_stream(feats[0].device)
         outs = [torch.empty(tuple(f.shape[:3]) + (heads.K,), dtype=torch.float32, device=f.device) for f in feats]
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             for f, o in zip(feats[1:], outs[1:]):       # (the caller's `feats` outlive the join below: no record_stream, see FPN.forward)
-                ops.conv2d(ops.conv2d(f, conv, relu=True), heads, out=o, out_f32=True)
-        ops.conv2d(ops.conv2d(feats[0], conv, relu=True), heads, out=outs[0], out_f32=True)
+                ops.conv2d(ops.conv2d(f, conv(f), relu=True), heads, out=o, out_f32=True)
+        ops.conv2d(ops.conv2d(feats[0], conv(feats[0]), relu=True), heads, out=outs[0], out_f32=True)
         cur.wait_stream(side)
         return outs
 
@@ -997,13 +1034,19 @@ class MaskRCNNHeads(PackedWeights, nn.Module):
                     state_dict[f"{prefix}mask_fcn{i + 1}.{s}"] = state_dict.pop(old)
         super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
+    def _pack_switches(self):
+        return (cdt(self), split_twin(self, "mask3"), ops.W24SX)
+
     def _build_packs(self):
+        # class mask3: the conv3x3_wino24sx twins, kept beside the list (built and dropped with it)
+        self._twins = [w24sx_twin(self, "mask3", getattr(self, f"mask_fcn{i}").weight, getattr(self, f"mask_fcn{i}").bias, pad=1)
+                       for i in range(1, self.n + 1)]
         return [ops.pack_conv(getattr(self, f"mask_fcn{i}").weight, getattr(self, f"mask_fcn{i}").bias, pad=1,
                               dtype=cdt(self)) for i in range(1, self.n + 1)]
 
     def forward(self, x):                        # NHWC [K,14,14,256]
-        for pc in self.packed():
-            x = ops.conv2d(x, pc, relu=True)
+        for pc, tw in zip(self.packed(), self._twins):
+            x = ops.conv2d(x, pick_w24sx(self, pc, tw, x), relu=True)
         return x
 
 

@@ -70,6 +70,7 @@ class PackedConv:
     wph: Optional[torch.Tensor] = None  # fp16 1x1 / stride-1 layers with C >= 512 (a multiple of 256), K a multiple of 128: fragment-order weights of seam_conv1x1_f16pc
     wx: Optional[torch.Tensor] = None   # SX6 1x1 / stride-1 layers with C >= 256 (a multiple of 64), K a multiple of 128: three bf16 planes in fragment order (seam_conv1x1_sxpc)
     wxs: Optional[torch.Tensor] = None  # SX6 1x1 / stride-1 layers with C == 128, K a multiple of 128: the same planes (seam_conv1x1_sxpc_short, seam_conv1x1_sxpc_dual_short)
+    u24x: Optional[torch.Tensor] = None  # SX6 stride-1 3x3 layers (C, K multiples of 64): F(2x4,3x3) weights as three bf16 planes (seam_pack_conv_weight_wino24_sx)
     wx64: Optional[torch.Tensor] = None  # SX6 1x1 / stride-1 layers with K == 64, C >= 128 (a multiple of 64): the same planes, two n-tiles (seam_conv1x1_sxpc64, seam_stem_sxpc)
 
 
@@ -119,6 +120,17 @@ SXPC64 = _os.environ.get("SEAM_SXPC64", "0") != "0"
 # rides in); on a twin, ``conv2d`` / ``conv2d_dual`` take the kernel by the usual rules and conv_igemm_sx (the same bits) otherwise.
 # SEAM_SXPC_SHORT=0: the exact kernels, as before the entries existed.
 SXPC_SHORT = _os.environ.get("SEAM_SXPC_SHORT", "1") != "0"
+# split-bf16 path (SX6): the stride-1 3x3 layers that run F(2x4,3x3) through conv3x3_wino24sx (csrc/seam_wino24sx.hip), the Winograd
+# position GEMMs as six-term split-bf16 products.  Its bits differ from conv3x3_wino24's, so a layer takes it by the map geometry
+# alone (``w24sx_map_ok``), at every batch size.  The rule: reductions from W24SX_MIN_C channels on (at C = 64 the kernel is level
+# with conv3x3_wino24pc), and maps on which ONE image is at least W24SX_MIN_BLOCKS blocks -- the kernel runs one block per CU and
+# wins from a single image on there (1 x 100^2 x 256 -> 256, 160 blocks: 1.32x; 1 x 200^2: 1.19x), while on smaller maps it wins at
+# a step's batch (1.10-1.30x at 40 / 80 frames) and loses 9-18 % on one or two images (80 blocks and fewer), so those stay on
+# the fp32 kernel unless the knob is lowered (profiles/w24sx_layer_ab.txt).  SEAM_W24SX=0 / W24SX = False: the fp32 kernels, as
+# before the kernel existed.
+W24SX = _os.environ.get("SEAM_W24SX", "1") != "0"
+W24SX_MIN_C = int(_os.environ.get("SEAM_W24SX_MIN_C", "128"))
+W24SX_MIN_BLOCKS = int(_os.environ.get("SEAM_W24SX_MIN_BLOCKS", "128"))
 F16PC_RULE = True      # dispatch by seam_conv3x3_f16pc_pays (False: every supported shape -- tests, tools/f16pc_ab.py)
 
 
@@ -201,10 +213,24 @@ def sxpc_short_map_ok(h: int, w: int, k: int) -> bool:
     return bool(SXPC_SHORT and (-(-(h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE))
 
 
+def w24sx_map_ok(h: int, w: int, c: int, k: int, pad: int) -> bool:
+    """A stride-1 3x3 layer (c -> k channels, ``pad``) on an h x w map runs its split twin on conv3x3_wino24sx: the kernel serves
+    the shape, the reduction is long enough and one image is enough blocks to win, and the exact pack would run F(2x4,3x3) there (``_wino_pays`` /
+    ``_wino24_pays``: where F(2x2) or the implicit GEMM issues less work, the layer stays on it).  The map geometry alone -- an
+    image's result never depends on the batch it rides in."""
+    lib = _native.lib()
+    return bool(W24SX and WINOGRAD and WINOGRAD24 and c >= W24SX_MIN_C and lib.seam_conv3x3_wino24sx_supported(1, h, w, c, k, pad, 1) == 1
+                and lib.seam_conv3x3_wino24sx_blocks(1, h, w, c, k, pad) >= max(W24SX_MIN_BLOCKS, 1)
+                and _wino_pays(lib, 1, h, w, c, k, pad) and _wino24_pays(lib, 1, h, w, c, k, pad))
+
+
 def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out_f32) -> str:
     """The kernel one ``conv2d`` launch takes.  First match wins; this order IS the precedence.  Integers, bools, which pack fields
     exist, the knobs above (read now: tests and tools assign them) and the library's host predicates -- no tensor data, no stream."""
     c, k, dt = pc.Cstore, pc.K, pc.dtype
+    if (dt == SX6 and pc.u24x is not None and not cropped and relu in (0, 1, False, True) and pc.stride == 1
+            and w24sx_map_ok(h, w, c, k, pc.pad)):
+        return "wino24sx"
     if (dt == SX6 and pc.wx is not None and SXPC and not cropped and relu in (0, 1, False, True)
             and (-(-(n * h * w) // 128) * (k // 128) >= SXPC_MIN_TILES or not SXPC_RULE) and lib.seam_conv1x1_sxpc_supported(n * h * w, c, k) == 1):
         return "sxpc"
@@ -240,7 +266,7 @@ def _conv_route(lib, pc: "PackedConv", n, h, w, relu, has_residual, cropped, out
 
 
 # routes of one instantiation: their CONV_TRACE labels
-_ROUTE_LABEL = {"sxpc": "conv1x1_sxpc", "sxpc64": "conv1x1_sxpc64", "sxpc_short": "conv1x1_sxpc_short", "pwhpc": "conv1x1_f16pc", "narrow": "linear_narrow", "pwpc": "conv1x1_pc", "f16pc": "conv3x3_f16pc"}
+_ROUTE_LABEL = {"wino24sx": "conv3x3_wino24sx", "sxpc": "conv1x1_sxpc", "sxpc64": "conv1x1_sxpc64", "sxpc_short": "conv1x1_sxpc_short", "pwhpc": "conv1x1_f16pc", "narrow": "linear_narrow", "pwpc": "conv1x1_pc", "f16pc": "conv3x3_f16pc"}
 
 
 def _conv_variant(lib, route: str, pc: "PackedConv", n, h, w, ho, wo) -> str:
@@ -302,7 +328,7 @@ def _trace_end(tr) -> None:
 
 def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None, *, stride: int = 1,
               pad: int = 0, cstore: Optional[int] = None, transposed2x2: bool = False,
-              bn_eps: float = 1e-5, dtype: torch.dtype = F32, wino: bool = True) -> PackedConv:
+              bn_eps: float = 1e-5, dtype: torch.dtype = F32, wino: bool = True, w24sx: bool = False) -> PackedConv:
     """Pack a PyTorch-layout weight for ``conv2d``.
 
     weight: Conv2d [K,Cin,R,S] | Linear [K,Cin] | (transposed2x2) ConvTranspose2d [Cin,Cout,2,2]
@@ -310,10 +336,12 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
             FrozenBatchNorm2d [TV] / BatchNorm1d eval (ref models/match_head.py:62).
     wino:   also pack Winograd F(2x2,3x3) weights for fp32 stride-1 3x3 layers (the inference path); the grad-enabled
             pass of the heads (autograd.py) packs per step and keeps the bit-exact fp32 fma chain of the implicit GEMM.
+    w24sx:  an SX6 pack of a stride-1 3x3 layer also gets the planes of conv3x3_wino24sx (``u24x``): the twin of a layer whose exact
+            pack runs F(2x4,3x3); ``conv2d`` on it takes that kernel where ``w24sx_map_ok`` holds and conv_igemm_sx elsewhere.
     dtype:  a tuple yields a tuple of packs of the ONE source (an exact pack and its split twin: the same shift tensor)."""
     if isinstance(dtype, tuple):
         return tuple(pack_conv(weight, bias, bn, stride=stride, pad=pad, cstore=cstore, transposed2x2=transposed2x2, bn_eps=bn_eps,
-                               dtype=d, wino=wino) for d in dtype)
+                               dtype=d, wino=wino, w24sx=w24sx) for d in dtype)
     lib = _native.lib()
     weight = _req(weight.detach(), name="weight")
     is_linear = not transposed2x2 and weight.dim() == 2      # a Linear runs on 1x1 maps: no weight form of the map-sized pointwise kernels
@@ -335,7 +363,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
     conv1x1 = plain and mode == 0 and not is_linear
     # the weight as a row-major fp32 [K, Cin] matrix, made on first use; of a Conv2d / Linear weight it is a view: the SAME storage
     rows_kc = functools.cache(lambda: (weight.permute(2, 3, 1, 0).reshape(K, cin) if transposed2x2 else weight.reshape(K, cin)).to(F32).contiguous())
-    u = u24 = wh = wx = wxs = wx64 = wn = ws = shift_sw = wq = wsh = wph = None      # the optional forms: each set below where the layer is eligible
+    u = u24 = u24x = wh = wx = wxs = wx64 = wn = ws = shift_sw = wq = wsh = wph = None      # the optional forms: each set below where the layer is eligible
     if dtype == F32:
         kred = lib.seam_conv_kred(cs, R, S)
         wp = torch.empty((rows, kred), dtype=F32, device=weight.device)
@@ -359,6 +387,10 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         if SXPC and dtype == SX6 and (conv1x1 or (plain and transposed2x2)) and lib.seam_conv1x1_sxpc_supported(1 << 20, cs, K):
             wx = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
             _native.check(lib.seam_pack_conv1x1_weight_sxpc(_ptr(rows_kc()), _ptr(wx), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc")
+        if (w24sx and W24SX and dtype == SX6 and mode == 0 and R == 3 and S == 3 and stride == 1 and cs == cin
+                and lib.seam_conv3x3_wino24sx_supported(1, 16, 16, cs, K, 1, 1)):
+            u24x = torch.empty((int(lib.seam_wino24sx_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
+            _native.check(lib.seam_pack_conv_weight_wino24_sx(_ptr(weight), _ptr(u24x), K, cin, cs, 0, _stream()), "seam_pack_conv_weight_wino24_sx")
         if SXPC and dtype == SX6 and conv1x1 and lib.seam_conv1x1_sxpc_short_supported(1 << 20, cs, K):
             wxs = torch.empty((int(lib.seam_conv1x1_sxpc_weight_bytes(K, cs)),), dtype=torch.uint8, device=weight.device)
             _native.check(lib.seam_pack_conv1x1_weight_sxpc_short(_ptr(rows_kc()), _ptr(wxs), K, cs, _stream()), "seam_pack_conv1x1_weight_sxpc_short")
@@ -405,7 +437,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None
         wph = torch.empty((int(lib.seam_conv1x1_f16pc_weight_halves(K, cs)),), dtype=F16, device=weight.device)
         _native.check(lib.seam_pack_conv1x1_weight_f16pc(_ptr(rows_kc()), _ptr(wph), K, cs, _stream()), "seam_pack_conv1x1_weight_f16pc")
     pc = PackedConv(wp, scale, shift, K, cs, R, S, stride=stride, pad=pad, Cin=cin, dtype=dtype, u=u, u24=u24, wn=wn, ws=ws,
-                    shift_sw=shift_sw, wq=wq, wh=wh, wsh=wsh, wph=wph, wx=wx, wxs=wxs, wx64=wx64)
+                    shift_sw=shift_sw, wq=wq, wh=wh, wsh=wsh, wph=wph, wx=wx, wxs=wxs, wx64=wx64, u24x=u24x)
     if _PACK_RECORDER is not None:
         _PACK_RECORDER.records.append((weight, bias, bn, mode, pc))
     return pc
@@ -650,6 +682,9 @@ def conv2d(x: torch.Tensor, pc: PackedConv, relu: bool = False, residual: Option
     elif route == "pwpc":
         _native.check(lib.seam_conv1x1_pc_f32(_ptr(x), _ptr(pc.wq), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                               n * h * w, c, pc.K, int(relu), _stream()), "seam_conv1x1_pc_f32")
+    elif route == "wino24sx":
+        _native.check(lib.seam_conv3x3_wino24sx_f32(_ptr(x), _ptr(pc.u24x), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
+                                                    n, h, w, c, pc.K, pc.pad, 1, int(relu), _stream()), "seam_conv3x3_wino24sx_f32")
     elif route == "wino24":
         _native.check(lib.seam_conv3x3_wino24_f32(_ptr(x), _ptr(pc.u24), _ptr(pc.scale), _ptr(pc.shift), _ptr(residual), _ptr(y),
                                                   n, h, w, c, pc.K, pc.pad, int(relu), _stream()), "seam_conv3x3_wino24_f32")
@@ -2959,6 +2994,8 @@ class PackPlan:
                 jobs.append(job(N.REPACK_SXPC64, pc.wxs))
             if pc.wx64 is not None:
                 jobs.append(job(N.REPACK_SXPC64, pc.wx64))
+            if pc.u24x is not None:
+                jobs.append(job(N.REPACK_W24SX, pc.u24x, 3, 3, md=mode))
             return jobs
         if pc.dtype != F32 or pc.wh is not None or pc.wsh is not None or pc.wph is not None:
             raise NotImplementedError(f"PackPlan: {path}: only fp32 packs are refreshed in place (pass refresh_packs=False)")
