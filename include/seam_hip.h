@@ -458,6 +458,25 @@ int seam_match_scores_f32(const float* logits, float* score, int64_t n_pairs, se
 int seam_host_build_tracklets(const float* blocks, const int64_t* seg, const int64_t* imgs, const double* scores, int n_seg,
                               double threshold, int32_t* members_out, int32_t* track_len_out, int32_t* n_tracks_out);
 
+/* DEVICE twin of seam_host_build_tracklets (device pointers, one launch for all segments, one block per segment; no host
+ * synchronisation): blocks / block_off (int64 [n_seg + 1]) / seg (int32 [n_seg + 1]) exactly as seam_pair_scores_blockdiag_f32 takes
+ * and writes them; imgs int32 [rows] the frame label of every detection (compared for equality only: need be neither dense nor
+ * sorted), scores fp32 [rows] the confidences; max_rows >= every n_s.  Out, int32, in the host helper's layout: members [rows],
+ * track_len [rows] (entries from n_tracks[s] on are written as 0), n_tracks [n_seg], and track_of [rows], the tracklet number of every
+ * detection; every element of those ranges is written.  Same decisions as the host helper on finite inputs (seed = most confident
+ * free detection, lowest index among equals; candidate = first maximum of members x candidates in row-major order, members in
+ * ascending detection order; sim[member][candidate] is read, the matrix need not be symmetric), except that the link test is
+ * (double)value > threshold in fp64, where the host helper compares with (float)threshold: float(0.3) links at 0.3 here.
+ * Comparisons only, no float atomics: exact and deterministic.  NaN inputs: unspecified decisions, but the kernel terminates and
+ * writes a partition.  seam_build_tracklets_max_rows(): the largest n_s served (the state lives in LDS).  Refused with
+ * hipErrorInvalidValue, nothing launched or written: n_seg < 0, max_rows < 0 or above the cap, a NULL block_off / seg / n_tracks, and
+ * any other NULL pointer when max_rows > 0.  n_seg == 0: no-op.  An empty segment: n_tracks[s] = 0.  A segment longer than
+ * max_rows: untouched except n_tracks[s] = -1. */
+int seam_build_tracklets_max_rows(void);
+int seam_build_tracklets_f32(const float* blocks, const int64_t* block_off, const int* seg, const int* imgs, const float* scores,
+                             int n_seg, int max_rows, double threshold, int32_t* members, int32_t* track_len, int32_t* n_tracks,
+                             int32_t* track_of, seam_stream_t stream);
+
 /* Block-diagonal self-similarity for the evaluator's tracking step (`compute_selfdist` once per product,
  * evaluate_movingfashion.py:102-121,165-176) in ONE launch: x [rows, Dd] holds the detections' descriptors grouped by product,
  * seg int32 [n_seg + 1] the group boundaries (row offsets), out_off int64 [n_seg + 1] the running sum of n_s^2; for every group

@@ -174,6 +174,33 @@ def build_tracklets_batch(blocks: np.ndarray, seg: np.ndarray, imgs_all: np.ndar
     return out
 
 
+def average_sequences(rows: torch.Tensor, seg_d: torch.Tensor) -> torch.Tensor:
+    """AVG DESC (evaluate_movingfashion.py:279-291): the mean descriptor of every sequence, ``rows`` [Q,256] holding the sequences
+    one after another and ``seg_d`` int32 [P + 1] (device) their boundaries -> [P,256].  Shared by ``evaluate_tables`` and
+    ``retrieval.retrieve``."""
+    return ops.score_reduce_segments(rows, seg_d, "mean")
+
+
+def aggregate_sequences(temporal_aggregator, rows: torch.Tensor, seg: np.ndarray, x3_2: torch.Tensor) -> torch.Tensor:
+    """AGGR DESC (evaluate_movingfashion.py:250-276): NLB Mode B over P sequences of aggregator descriptors in one call -- ``rows``
+    [Q,256] holds the sequences one after another (each in the order it is to be aggregated in), ``seg`` [P + 1] (host) their
+    boundaries, ``x3_2`` the shop rows Mode B wants next to them -> [P,256].  Shared by ``evaluate_tables`` and
+    ``retrieval.retrieve``."""
+    dev = rows.device
+    lens = np.diff(seg)
+    P, tmax = len(lens), int(lens.max())
+
+    def idx(a):
+        return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int64, device=dev)
+
+    seq = torch.zeros((1 + tmax, P, rows.shape[1]), device=dev)
+    trow = np.concatenate([1 + np.arange(n) for n in lens])
+    tcol = np.repeat(np.arange(P), lens)
+    seq[idx(trow), idx(tcol)] = rows
+    mask = torch.as_tensor(np.arange(1 + tmax)[None, :] > lens[:, None], device=dev)
+    return temporal_aggregator(None, None, None, x3_1_seq=seq, x3_1_mask=mask, x3_2=x3_2)[0][:P]
+
+
 @dataclass
 class RetrievalReport:
     k_thresholds: Sequence[int]
@@ -352,17 +379,11 @@ def evaluate_tables(t: DescriptorTables, temporal_aggregator, k_thresholds: Sequ
         del logits
         seg_d = torch.as_tensor(seg, dtype=torch.int32, device=dev)
         # AVG DESC (:279-291), AVG & MAX DISTANCE (:293-315): segment reductions, then one rank launch each
-        avg_rank_d = ops.rank_of(ops.pair_logits(ops.score_reduce_segments(queries, seg_d, "mean"), t.shop_mat, t.w, t.b), target_p)
+        avg_rank_d = ops.rank_of(ops.pair_logits(average_sequences(queries, seg_d), t.shop_mat, t.w, t.b), target_p)
         both = torch.cat([ops.score_reduce_segments(distances, seg_d, "mean"), ops.score_reduce_segments(distances, seg_d, "max")])
         dist_rank_d = ops.rank_of_scores(both, target_p.repeat(2))
         # AGGR DESC (:250-276): Mode B over the tracked frames' aggregator descriptors, S = #products sequences
-        tmax = int(np.diff(seg).max())
-        seq = torch.zeros((1 + tmax, P, t.street_aggr.shape[1]), device=dev)
-        trow = np.concatenate([1 + np.arange(len(m)) for m in chosen])
-        tcol = np.repeat(np.arange(P), np.diff(seg))
-        seq[idx(trow), idx(tcol)] = t.street_aggr[dets_d[q_d]]
-        mask = torch.as_tensor(np.arange(1 + tmax)[None, :] > np.diff(seg)[:, None], device=dev)
-        desc = temporal_aggregator(None, None, None, x3_1_seq=seq, x3_1_mask=mask, x3_2=t.shop_aggr[:1])[0][:P]
+        desc = aggregate_sequences(temporal_aggregator, t.street_aggr[dets_d[q_d]], seg, t.shop_aggr[:1])
         aggr_rank_d = ops.rank_of(ops.pair_logits(desc.contiguous(), t.shop_aggr, aggr_w, aggr_b), target_p)
         ranks = torch.cat([frame_rank_d, avg_rank_d, dist_rank_d, aggr_rank_d]).cpu().numpy()      # copy 3
         frame_rank_all, avg_rank = ranks[:Q], ranks[Q:Q + P]

@@ -1469,6 +1469,85 @@ def pair_scores_blockdiag(x: torch.Tensor, seg, w: torch.Tensor, bias: torch.Ten
     return out
 
 
+def blockdiag_offsets(seg, device):
+    """The two offset tables ``seam_pair_scores_blockdiag_f32`` and ``seam_build_tracklets_f32`` share, from host row offsets
+    ``seg`` [n_seg + 1]: (seg int32 [n_seg + 1], out_off int64 [n_seg + 1] = running sum of n_s^2) on ``device``."""
+    import numpy as np
+    seg = np.asarray(seg, dtype=np.int64)
+    n = np.diff(seg)
+    off = np.concatenate([[0], np.cumsum(n * n)])
+    return torch.as_tensor(seg, dtype=torch.int32, device=device), torch.as_tensor(off, dtype=torch.int64, device=device)
+
+
+def pair_scores_blockdiag_device(x: torch.Tensor, seg: torch.Tensor, out_off: torch.Tensor, n_out: int, max_rows: int,
+                                 w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``pair_scores_blockdiag`` with the offset tables already on the device (int32 ``seg``, int64 ``out_off``, as
+    ``blockdiag_offsets`` forms them) and nothing read back: ``n_out`` floats are allocated (>= out_off[-1]; what lies behind
+    out_off[-1] is not written) and ``max_rows`` bounds every group from above."""
+    x = _req(x, name="x")
+    seg, out_off = _req(seg, torch.int32, "seg"), _req(out_off, torch.int64, "out_off")
+    out = torch.empty((int(n_out),), dtype=F32, device=x.device)
+    if seg.numel() > 1 and max_rows > 0:
+        _native.check(_native.lib().seam_pair_scores_blockdiag_f32(_ptr(x), _ptr(seg), _ptr(out_off), _ptr(_req(w, name="w")),
+                                                                   _ptr(_req(bias, name="bias")), _ptr(out), seg.numel() - 1,
+                                                                   int(max_rows), x.shape[1], _stream()),
+                      "seam_pair_scores_blockdiag_f32")
+    return out
+
+
+def build_tracklets_max_rows() -> int:
+    return int(_native.lib().seam_build_tracklets_max_rows())
+
+
+def build_tracklets(blocks: torch.Tensor, out_off, seg, imgs: torch.Tensor, scores: torch.Tensor, threshold: float,
+                    max_rows: Optional[int] = None):
+    """Greedy tracklet linking of every segment in one launch (``seam_build_tracklets_f32``; the device twin of
+    ``evaluator.build_tracklets_batch``): ``blocks`` as ``pair_scores_blockdiag`` returns them, ``imgs`` int32 [rows] frame labels
+    (compared for equality only), ``scores`` fp32 [rows] confidences, all on the device.
+    -> (members, track_len, n_tracks, track_of) int32 device tensors in the host helper's layout ([rows], [rows], [n_seg], [rows]).
+
+    ``seg`` / ``out_off``: the host row offsets ``pair_scores_blockdiag`` took (``out_off`` may then be None: it is their running
+    sum of squares), or the device tables of ``blockdiag_offsets``.  With device tables nothing here knows the segment sizes, so
+    ``max_rows`` (an upper bound of every segment) must be passed; a longer segment then comes back with n_tracks[s] = -1.  With
+    host offsets an oversized segment raises ValueError before anything is launched.  No host synchronisation either way."""
+    import numpy as np
+    cap = build_tracklets_max_rows()
+    blocks, imgs, scores = _req(blocks, name="blocks"), _req(imgs, torch.int32, "imgs"), _req(scores, name="scores")
+    dev = blocks.device
+    if isinstance(seg, torch.Tensor) and seg.is_cuda:
+        if max_rows is None or not isinstance(out_off, torch.Tensor):
+            raise ValueError("build_tracklets: device offset tables need out_off on the device and max_rows (reading the segment "
+                             "sizes back would be a host synchronisation)")
+        seg_d, off_d = _req(seg, torch.int32, "seg"), _req(out_off, torch.int64, "out_off")
+        max_rows = int(max_rows)
+    else:
+        seg_h = np.asarray(seg.numpy() if isinstance(seg, torch.Tensor) else seg, dtype=np.int64)
+        n = np.diff(seg_h)
+        if len(seg_h) < 1 or (len(n) and (seg_h[0] != 0 or (n < 0).any())):
+            raise ValueError("build_tracklets: seg must be non-decreasing row offsets starting at 0")
+        if len(n) and int(seg_h[-1]) != imgs.numel():
+            raise ValueError(f"build_tracklets: seg ends at {int(seg_h[-1])} but imgs holds {imgs.numel()} detections")
+        max_rows = int(n.max()) if len(n) else 0
+        seg_d, off_d = blockdiag_offsets(seg_h, dev)
+        if isinstance(out_off, torch.Tensor) and out_off.is_cuda:
+            off_d = _req(out_off, torch.int64, "out_off")
+        if len(n) and blocks.numel() != int((n * n).sum()):
+            raise ValueError(f"build_tracklets: blocks holds {blocks.numel()} scores, the segments need {int((n * n).sum())}")
+    if max_rows > cap:
+        raise ValueError(f"build_tracklets: a segment of {max_rows} detections exceeds the linker's cap of {cap} "
+                         "(seam_build_tracklets_max_rows())")
+    rows, n_seg = imgs.numel(), seg_d.numel() - 1
+    if scores.numel() != rows:
+        raise ValueError("build_tracklets: scores must hold one confidence per detection")
+    out = torch.empty((3 * rows + max(n_seg, 0),), dtype=torch.int32, device=dev)
+    members, track_len, track_of, n_tracks = out[:rows], out[rows:2 * rows], out[2 * rows:3 * rows], out[3 * rows:]
+    if n_seg > 0:
+        _native.check(_native.lib().seam_build_tracklets_f32(_ptr(blocks), _ptr(off_d), _ptr(seg_d), _ptr(imgs), _ptr(scores), n_seg,
+                                                             max_rows, float(threshold), _ptr(members), _ptr(track_len), _ptr(n_tracks),
+                                                             _ptr(track_of), _stream()), "seam_build_tracklets_f32")
+    return members, track_len, n_tracks, track_of
+
+
 def rank_of(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """logits [Q,G,2], target int64 [Q] -> rank int64 [Q] of the target product in each query's ranking."""
     logits, target = _req(logits), _req(target, torch.int64, "target")
