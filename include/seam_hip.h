@@ -696,7 +696,12 @@ int seam_conv3x3_wino24_f32(const float* x, const float* u_packed, const float* 
 long long seam_wino24sx_weight_bytes(int K, int Cstore);
 int seam_pack_conv_weight_wino24_sx(const float* w, void* u_packed, int K, int Cin, int Cstore, int mode, seam_stream_t stream);
 int seam_conv3x3_wino24sx_supported(int N, int H, int W, int C, int K, int pad, int stride);
-long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pad);   /* blocks of the launch; 0 = unsupported */
+long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pad);   /* tiles of the launch (independent of the forced split); 0 = unsupported */
+/* The XCD groups conv3x3_wino24sx splits its n-tiles over, process-wide: 0 (default) the launcher's rule, 1 | 2 | 4 | 8 forced (reduced
+ * until it divides the n-tiles); set returns hipErrorInvalidValue for any other value and leaves the setting.  Same bits under every
+ * value; for the parity test and the A/B tools. */
+int seam_conv3x3_wino24sx_set_nsplit(int nsplit);
+int seam_conv3x3_wino24sx_get_nsplit(void);
 int seam_conv3x3_wino24sx_f32(const float* x, const void* u_packed, const float* scale, const float* shift, const float* residual,
                               float* y, int N, int H, int W, int C, int K, int pad, int stride, int relu, seam_stream_t stream);
 

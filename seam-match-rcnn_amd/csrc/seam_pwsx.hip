@@ -279,7 +279,7 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
                     q0[0] = __builtin_bit_cast(unsigned, src[r][0]); q0[1] = __builtin_bit_cast(unsigned, src[r][1]);
                     q1[0] = __builtin_bit_cast(unsigned, src[r][2]); q1[1] = __builtin_bit_cast(unsigned, src[r][3]); q2 = q0;
                 } else {
-                    split3_bf16(src[r], q0, q1, q2);
+                    split3_bf16_single(src[r], q0, q1, q2);    // producer waves beside the consumers' MFMAs: nothing packed
                 }
                 *reinterpret_cast<u32x2 LDSQ*>(lp[r] + buf * ABUF) = q0;
                 *reinterpret_cast<u32x2 LDSQ*>(lp[r] + buf * ABUF + PLB) = q1;

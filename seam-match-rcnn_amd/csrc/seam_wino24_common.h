@@ -853,7 +853,10 @@ inline bool wino24_pc(const Wino24Args& a) {
 }
 
 // force_nt: 0 = the n-tiles per block by wino24_nt's rule, 1 | 2 = that form (conv3x3_wino24sx is always the two n-tile block)
-inline int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, long& blocks, int force_nt = 0) {
+// nsplit_rule: the XCD groups wanted for (C, K, patch blocks); the fp32 kernels keep wino24_nsplit, conv3x3_wino24sx brings its own
+// tiles: if given, the tiles of the launch (patch blocks x n-tiles) -- `blocks` is the grid, which an n-tile split pads
+inline int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, long& blocks, int force_nt = 0,
+                       int (*nsplit_rule)(int, int, long) = wino24_nsplit, long* tiles = nullptr) {
     if (!wino_ok(C, K, 3, 3, 1) || N <= 0) return (int)hipErrorInvalidValue;
     a.N = N; a.H = H; a.W = W; a.C = C; a.K = K;
     a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2; a.pad = pad;
@@ -872,8 +875,9 @@ inline int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad
         a.TX[r] = pp.TX[q]; a.TY[r] = pp.TY[q]; a.bx[r] = pp.bx[q]; a.by[r] = pp.by[q];
     }
     blocks = pp.blocks * a.tiles_n;
+    if (tiles) *tiles = blocks;
     {
-        int ns = wino24_nsplit(C, K, pp.blocks);
+        int ns = nsplit_rule(C, K, pp.blocks);
         while (ns > 1 && (a.tiles_n % ns || 8 % ns)) ns >>= 1;
         a.nsplit = ns < 1 ? 1 : ns;
         a.tns = a.tiles_n / a.nsplit;

@@ -34,6 +34,7 @@
 #include "seam_device.h"
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include "seam_fastdiv.h"
 #include "seam_launch.h"
 #include "seam_opts.h"
@@ -66,9 +67,24 @@ inline bool wino24sx_ok(int C, int K, int stride, int pad) {
     return stride == 1 && (pad == 0 || pad == 1) && C >= 64 && C % 64 == 0 && K >= 64 && K % 64 == 0 && (long long)K * C * 144 < (1ll << 31);
 }
 
-int wino24sx_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, int stride, long& blocks) {
+// XCD groups the n-tiles are split over (w24_tile's decode; every value gives the same bits).  seam_conv3x3_wino24sx_set_nsplit(1 |
+// 2 | 4 | 8) forces one (a process-wide int of this launcher, like the selectors of seam_opts.h; it is not one of them because their
+// number is pinned); wino24_plan reduces it until it divides the n-tiles.  The rule is 1 everywhere: measured with 1 / 2 / 4 on the ten
+// shapes of a step at 80 and 40 frames and on one and two images, no shape wins beyond its spreads (80 x 200^2 x 256 -> 256: 9544 ->
+// 9557 -> 9517 us), although two groups take a fifth of the L2 misses and of the fetched bytes away: seven of eight requests hit
+// already (profiles/w24sx_l2_layer_ab.txt, profiles/w24sx_l2_pmc.txt).
+std::atomic<int> g_force_nsplit{0};          // 0: the rule
+int wino24sx_nsplit(int C, int K, long patch_blocks) {
+    const int force = g_force_nsplit.load(std::memory_order_relaxed);
+    if (force > 0) return force;
+    (void)C; (void)K; (void)patch_blocks;
+    return 1;
+}
+
+// blocks: the grid (with the padding blocks of an n-tile split); tiles: patch blocks x n-tiles, whatever the split
+int wino24sx_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad, int stride, long& blocks, long* tiles = nullptr) {
     if (!wino24sx_ok(C, K, stride, pad)) return (int)hipErrorInvalidValue;
-    return wino24_plan(a, N, H, W, C, K, pad, blocks, 2);
+    return wino24_plan(a, N, H, W, C, K, pad, blocks, 2, wino24sx_nsplit, tiles);
 }
 
 }  // namespace
@@ -91,11 +107,21 @@ int seam_conv3x3_wino24sx_supported(int N, int H, int W, int C, int K, int pad, 
     return wino24sx_plan(a, N, H, W, C, K, pad, stride, blocks) == 0 ? 1 : 0;
 }
 
-/* blocks of the launch (one per CU at a time); 0 = unsupported.  ops.w24sx_map_ok asks it for ONE image. */
+/* XCD groups of the n-tile split: 0 = the launcher's rule (default), 1 | 2 | 4 | 8 forced; any other value is refused */
+int seam_conv3x3_wino24sx_set_nsplit(int nsplit) {
+    if (nsplit != 0 && nsplit != 1 && nsplit != 2 && nsplit != 4 && nsplit != 8) return (int)hipErrorInvalidValue;
+    g_force_nsplit.store(nsplit, std::memory_order_relaxed);
+    return 0;
+}
+
+int seam_conv3x3_wino24sx_get_nsplit(void) { return g_force_nsplit.load(std::memory_order_relaxed); }
+
+/* tiles of the launch (one block each, one per CU at a time; the padding blocks of an n-tile split are not counted, so the number
+   does not depend on the forced split); 0 = unsupported.  ops.w24sx_map_ok asks it for ONE image. */
 long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pad) {
     Wino24Args a;
-    long blocks;
-    return wino24sx_plan(a, N, H, W, C, K, pad, 1, blocks) == 0 ? (long long)blocks : 0;
+    long blocks, work = 0;
+    return wino24sx_plan(a, N, H, W, C, K, pad, 1, blocks, &work) == 0 ? (long long)work : 0;
 }
 
 int seam_conv3x3_wino24sx_f32(const float* x, const void* u_packed, const float* scale, const float* shift, const float* residual,

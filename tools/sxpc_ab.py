@@ -53,7 +53,7 @@ def med_spread(v):
 
 
 hdr = f"{'layer':>13} {'N,H,W,C,K,res,relu':>24} {'igemm_sx us':>11} {'spread':>6} {'sxpc us':>8} {'spread':>6} {'TF/s':>6} {'x':>5} {'same bits':>9}"
-print(hdr + "".join(f" {n + ' us':>12}" for n, _ in abl))
+print(hdr + "".join(f" {n + ' us':>12} {'spread':>6}" for n, _ in abl))
 for label, s in shapes:
     n, h, w, c, k, res, relu = map(int, s.split(","))
     g = torch.Generator(device=dev)
@@ -107,4 +107,4 @@ for label, s in shapes:
     mb, sb = med_spread(tb)
     fl = 2.0 * n * h * w * c * k
     print(f"{label:>13} {s:>24} {ma:11.1f} {sa:6.3f} {mb:8.1f} {sb:6.3f} {fl / mb / 1e6:6.1f} {ma / mb:5.2f} {str(same):>9}"
-          + "".join(f" {statistics.median(v):12.1f}" for v in tx), flush=True)
+          + "".join(f" {med_spread(v)[0]:12.1f} {med_spread(v)[1]:6.3f}" for v in tx), flush=True)

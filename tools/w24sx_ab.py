@@ -7,7 +7,10 @@ drifting clock moves all of them alike.  Reported per shape: the median over the
 either kernel, the ratio of the medians, and the largest difference of the two outputs over the output's largest value.
 `--abl name=lib.so ...` adds timing-only builds of the new kernel (tools/w24sx_abl_build.sh: SEAM_W24SX_ABL bits) -- their
 outputs are wrong by construction and are not compared.  `--frames F` scales the batches (80 frames / 2560 ROIs) to F frames.
-usage: w24sx_ab.py [--frames F] [--abl name=path ...] [N,H,W,C,K,pad ...]"""
+`--nsplit 1,2,4` adds the tree's kernel with seam_conv3x3_wino24sx_set_nsplit forcing each value, in the same rounds: median, spread,
+and whether its output is the `w24sx` column's bit for bit (that column runs under 0, the launcher's rule, unless W24SX_NSPLIT in
+the environment names a forced value for the whole run).
+usage: w24sx_ab.py [--frames F] [--nsplit a,b,..] [--abl name=path ...] [N,H,W,C,K,pad ...]"""
 import ctypes as C
 import os
 import statistics
@@ -25,9 +28,12 @@ ROUNDS, REPS = 5, 5
 args = sys.argv[1:]
 frames = 80
 abl = []
-while args and args[0] in ("--abl", "--frames"):
+forced = []
+while args and args[0] in ("--abl", "--frames", "--nsplit"):
     if args[0] == "--frames":
         frames = int(args[1])
+    elif args[0] == "--nsplit":
+        forced = [int(v) for v in args[1].split(",")]
     else:
         name, path = args[1].split("=", 1)
         lib = C.CDLL(os.path.abspath(path))
@@ -38,6 +44,9 @@ while args and args[0] in ("--abl", "--frames"):
 shapes = [("", a) for a in args] or DEFAULT
 dev = torch.device("cuda:0")
 lib0 = _native.lib()
+BASE_NSPLIT = int(os.environ.get("W24SX_NSPLIT", "0"))          # for a counter pass over one forced value (tools/pmc_w24.sh)
+if BASE_NSPLIT:
+    _native.check(lib0.seam_conv3x3_wino24sx_set_nsplit(BASE_NSPLIT), "set_nsplit")
 P = ops._ptr
 
 
@@ -57,7 +66,7 @@ def med_spread(v):
 
 
 print(f"{'layer':>16} {'N,H,W,C,K,pad':>22} {'wino24 us':>10} {'spread':>6} {'w24sx us':>9} {'spread':>6} {'TF/s':>6} {'x':>5} {'max diff':>9}"
-      + "".join(f" {n + ' us':>14}" for n, _ in abl))
+      + "".join(f" {'ns=%d us' % v:>9} {'spread':>6} {'bits':>4}" for v in forced) + "".join(f" {n + ' us':>14} {'spread':>6}" for n, _ in abl))
 for label, s in shapes:
     n, h, w, c, k, pad = map(int, s.split(","))
     n = max(1, n * frames // 80)
@@ -81,20 +90,35 @@ for label, s in shapes:
     def run_b(lib=lib0, y=yb):
         _native.check(lib.seam_conv3x3_wino24sx_f32(P(x), P(ux), None, P(sh), None, P(y), n, h, w, c, k, pad, 1, 1, ops._stream()), "wino24sx")
 
+    def run_ns(v, y=yc):
+        _native.check(lib0.seam_conv3x3_wino24sx_set_nsplit(v), "set_nsplit")
+        try:
+            run_b(lib0, y)
+        finally:
+            lib0.seam_conv3x3_wino24sx_set_nsplit(BASE_NSPLIT)
+
     run_a(); run_b()
+    same = []
+    for v in forced:
+        yc.fill_(float("nan"))
+        run_ns(v)
+        same.append(bool(torch.equal(yb.view(torch.int32), yc.view(torch.int32))))
     for _, lib in abl:
         run_b(lib, yc)
     torch.cuda.synchronize()
     diff = float((ya - yb).abs().max()) / float(ya.abs().max())
-    ta, tb, tx = [], [], [[] for _ in abl]
+    ta, tb, tx, tn = [], [], [[] for _ in abl], [[] for _ in forced]
     for _ in range(ROUNDS):
         ta.append(timed(run_a))
         tb.append(timed(run_b))
+        for i, v in enumerate(forced):
+            tn[i].append(timed(lambda: run_ns(v)))
         for i, (_, lib) in enumerate(abl):
             tx[i].append(timed(lambda: run_b(lib, yc)))
     ma, sa = med_spread(ta)
     mb, sb = med_spread(tb)
     fl = 2.0 * n * ho * wo * c * k * 9
     print(f"{label:>16} {n:>6},{h},{w},{c},{k},{pad:<2} {ma:10.1f} {sa:6.3f} {mb:9.1f} {sb:6.3f} {fl / mb / 1e6:6.1f} {ma / mb:5.2f} {diff:9.2e}"
-          + "".join(f" {statistics.median(v):14.1f}" for v in tx), flush=True)
+          + "".join(f" {med_spread(v)[0]:9.1f} {med_spread(v)[1]:6.3f} {'same' if ok else 'DIFF':>4}" for v, ok in zip(tn, same))
+          + "".join(f" {med_spread(v)[0]:14.1f} {med_spread(v)[1]:6.3f}" for v in tx), flush=True)
     del x, ya, yb, yc
