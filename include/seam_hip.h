@@ -702,6 +702,15 @@ long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pa
  * value; for the parity test and the A/B tools. */
 int seam_conv3x3_wino24sx_set_nsplit(int nsplit);
 int seam_conv3x3_wino24sx_get_nsplit(void);
+/* The block layout of a launch of the F(2x4) kernels, read from the arguments the launcher would launch with (host only, nothing is
+ * launched): sx = 0 the plan of seam_conv3x3_wino24_f32, sx = 1 that of seam_conv3x3_wino24sx_f32 (two n-tiles per block, its own
+ * acceptance rule, the currently forced split).  out[24], in this order: nreg (1..3 regions: main, right strip, bottom strip), stack
+ * (1: TY[0] consecutive tile rows of the whole batch per block), G (images a block's patch spans), PH (patch rows, stacked form),
+ * nt, tiles_n, nsplit, per_img (patch blocks of one image), TX[3], TY[3] (tiles per block patch; the kernel's LDS stride class is
+ * HS = (TX + 1) | 1: 9, 5, 3 compiled, anything else the run-time form), bx[3], by[3] (blocks of a region), patch blocks (all
+ * images, one n-tile), grid blocks (x n-tiles, plus the padding blocks of an n-tile split); out[22..23] = 0.  Regions past nreg
+ * are 0.  Returns 0, or hipErrorInvalidValue with nothing written for a shape the launcher refuses. */
+int seam_wino24_layout(int N, int H, int W, int C, int K, int pad, int sx, int* out);
 int seam_conv3x3_wino24sx_f32(const float* x, const void* u_packed, const float* scale, const float* shift, const float* residual,
                               float* y, int N, int H, int W, int C, int K, int pad, int stride, int relu, seam_stream_t stream);
 

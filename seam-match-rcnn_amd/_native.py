@@ -149,6 +149,7 @@ SIGNATURES = {
     "seam_conv3x3_wino24sx_blocks": (C.c_longlong, [_i, _i, _i, _i, _i, _i]),
     "seam_conv3x3_wino24sx_set_nsplit": (_i, [_i]),
     "seam_conv3x3_wino24sx_get_nsplit": (_i, []),
+    "seam_wino24_layout": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "seam_conv3x3_wino24sx_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv3x3_wino_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "seam_conv3x3_f16pc_supported": (_i, [_i, _i, _i, _i, _i, _i]),

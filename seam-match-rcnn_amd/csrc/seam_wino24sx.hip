@@ -124,6 +124,32 @@ long long seam_conv3x3_wino24sx_blocks(int N, int H, int W, int C, int K, int pa
     return wino24sx_plan(a, N, H, W, C, K, pad, 1, blocks, &work) == 0 ? (long long)work : 0;
 }
 
+/* The block layout of a launch, read from the Wino24Args the launcher would launch with (sx = 0: seam_conv3x3_wino24_f32's plan,
+   sx = 1: this file's, under the currently forced split).  out[24]: nreg, stack, G, PH, nt, tiles_n, nsplit, per_img, TX[3], TY[3],
+   bx[3], by[3], patch blocks (all images, per n-tile), grid blocks (patch blocks x n-tiles plus the padding blocks of an n-tile
+   split; the producer / consumer form walks that many tiles with a persistent grid).  Regions past nreg are 0.  Returns
+   hipErrorInvalidValue, writing nothing, for a shape the launcher refuses. */
+int seam_wino24_layout(int N, int H, int W, int C, int K, int pad, int sx, int* out) {
+    Wino24Args a;
+    long blocks;
+    if (!out || (sx != 0 && sx != 1)) return (int)hipErrorInvalidValue;
+    const int rc = sx ? wino24sx_plan(a, N, H, W, C, K, pad, 1, blocks) : wino24_plan(a, N, H, W, C, K, pad, blocks);
+    if (rc) return rc;
+    const int head[8] = {a.nreg, a.stack, a.G, a.PH, a.nt, a.tiles_n, a.nsplit, a.per_img};
+    for (int i = 0; i < 8; ++i) out[i] = head[i];
+    for (int r = 0; r < 3; ++r) {
+        const bool used = r < a.nreg;
+        out[8 + r] = used ? a.TX[r] : 0;
+        out[11 + r] = used ? a.TY[r] : 0;
+        out[14 + r] = used ? a.bx[r] : 0;
+        out[17 + r] = used ? a.by[r] : 0;
+    }
+    out[20] = (8 / a.nsplit) * a.part_q + a.part_r;
+    out[21] = (int)blocks;
+    out[22] = out[23] = 0;
+    return 0;
+}
+
 int seam_conv3x3_wino24sx_f32(const float* x, const void* u_packed, const float* scale, const float* shift, const float* residual,
                               float* y, int N, int H, int W, int C, int K, int pad, int stride, int relu, void* stream) {
     Wino24Args a;

@@ -7,7 +7,10 @@ output of nsplit = 1 byte for byte, and that one passes the float64 gates of tes
 Shapes: the smallest that reach each branch of the decode (C = 64 is four k-steps).  With `parts` = 8 / nsplit partitions of the
 patch blocks, part_q = blocks // parts and part_r = blocks % parts:
   * 1 x 8 x 8, 64 -> 256, pad 1: one patch block, four n-tiles; part_q = 0, so all but one partition are padding blocks that return.
-  * 3 x 20 x 36, 64 -> 128, pad 1: main region plus right and bottom strips; two n-tiles, so a forced 4 is reduced to 2.
+  * 3 x 20 x 36, 64 -> 128, pad 1: one uniform region (TX 3, TY 10) of three blocks per image; two n-tiles, so a forced 4 is
+    reduced to 2.
+  * 1 x 25 x 70, 128 -> 128, pad 1 (``r3-9-3-rt-100sq-c128`` of tests/w24_layout_cases.py, the layout of the 100 x 100 maps): a main
+    region plus a right and a bottom strip, eight patch blocks whose region decode follows the split's renumbering.
   * 5 x 14 x 14, 64 -> 256, pad 0: stacked mode, 3 patch blocks over 4 and over 2 partitions.
   * 2 x 40 x 40, 128 -> 256, pad 1, residual + ReLU: part_r != 0 with part_q > 0.
   * 2 x 9 x 11, 64 -> 64: one n-tile, every forced value falls back to 1."""
@@ -16,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 import test_gpu_w24sx as W
+import w24_layout_cases as T
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +28,7 @@ FORCED = (1, 2, 4)
 CASES = [
     pytest.param((1, 8, 8, 64, 256, 1, ""), id="one-patch-block-1x8x8-64-256"),
     pytest.param((3, 20, 36, 64, 128, 1, ""), id="regions-3x20x36-64-128"),
+    pytest.param(tuple(T.BY_ID["r3-9-3-rt-100sq-c128"][1:7]) + ("",), id="three-regions-1x25x70-128-128"),
     pytest.param((5, 14, 14, 64, 256, 0, ""), id="stacked-5x14x14-64-256-pad0"),
     pytest.param((2, 40, 40, 128, 256, 1, "residual_relu"), id="part_r-2x40x40-128-256-residual-relu"),
     pytest.param((2, 9, 11, 64, 64, 1, ""), id="one-n-tile-2x9x11-64-64"),
@@ -41,6 +46,8 @@ def env():
 def test_forced_split_is_bit_identical(env, case):
     ops, lib, dev = env
     n, h, w, c, k, pad, mode = case
+    if (n, h, w) == (1, 25, 70):          # the case this file names as main region + both strips really is one
+        assert T.signature(T.query(lib, n, h, w, c, k, pad), n, h, w, pad)["strips"] == "RB"
     p = W.problem(env, n, h, w, c, k, pad)
     ref, y24, yex, resd, relu = p["y64"], p["y24"], p["yex"], None, 0
     if mode:

@@ -75,6 +75,41 @@ def test_block_rule_is_one_image_alone(ops):
     assert route(ops, pc, 1, 50, 50) == "wino24sx"
 
 
+def test_layout_query_on_the_pinned_shapes():
+    """seam_wino24_layout on the five maps of the block rule above, 256 -> 256, one image: the per-image patch blocks behind the
+    pinned tile counts (x 4 n-tiles) and the regions they come from -- (TX, TY, bx, by) per region, zeros past nreg."""
+    import w24_layout_cases as T
+    L = lib()
+    want = {
+        (100, 100): dict(nreg=3, per_img=40, TX=(8, 1, 12), TY=(4, 25, 2), bx=(3, 1, 2), by=(12, 2, 1)),
+        (200, 200): dict(nreg=2, per_img=157, TX=(8, 2, 0), TY=(4, 15, 0), bx=(6, 1, 0), by=(25, 7, 0)),
+        (64, 80): dict(nreg=1, per_img=20, TX=(4, 0, 0), TY=(8, 0, 0), bx=(5, 0, 0), by=(4, 0, 0)),
+        (50, 50): dict(nreg=2, per_img=11, TX=(6, 1, 0), TY=(5, 25, 0), bx=(2, 1, 0), by=(5, 1, 0)),
+        (14, 14): dict(nreg=1, per_img=1, TX=(4, 0, 0), TY=(7, 0, 0), bx=(1, 0, 0), by=(1, 0, 0)),
+    }
+    for (h, w), exp in want.items():
+        lay = T.query(L, 1, h, w, 256, 256, 1)
+        assert {k: lay[k] for k in exp} == exp, (h, w, lay)
+        assert (lay["stack"], lay["G"], lay["PH"], lay["nt"], lay["tiles_n"], lay["nsplit"]) == (0, 1, 0, 2, 4, 1), (h, w, lay)
+        assert lay["patch_blocks"] == exp["per_img"] and lay["grid_blocks"] == 4 * exp["per_img"] == L.seam_conv3x3_wino24sx_blocks(1, h, w, 256, 256, 1)
+        # eighty images: the same regions, eighty times the blocks; the fp32 launcher's plan differs in the n-tiles per block alone
+        many, f32 = T.query(L, 80, h, w, 256, 256, 1), T.query(L, 1, h, w, 256, 256, 1, sx=0)
+        if (h, w) == (14, 14):            # ... but the ROI-sized map, which stacks: 8 of the batch's 560 tile rows per block
+            assert (many["stack"], many["TX"][0], many["TY"][0], many["G"], many["patch_blocks"]) == (1, 4, 8, 2, 70), many
+        else:
+            assert {k: many[k] for k in exp} == exp and many["patch_blocks"] == 80 * exp["per_img"]
+        assert {k: f32[k] for k in exp} == exp and f32["nt"] == L.seam_wino24_variant(1, h, w, 256, 256, 1) and f32["tiles_n"] * f32["nt"] == 8
+    # a forced split shows in the query (it reads the launcher's own arguments) and pads the grid, not the tiles
+    before = L.seam_conv3x3_wino24sx_get_nsplit()
+    try:
+        assert L.seam_conv3x3_wino24sx_set_nsplit(2) == 0
+        lay = T.query(L, 1, 100, 100, 256, 256, 1)
+        assert lay["nsplit"] == 2 and lay["patch_blocks"] == 40 and lay["grid_blocks"] == 8 * 10 * 2
+        assert T.query(L, 1, 100, 100, 256, 256, 1, sx=0)["nsplit"] == 1
+    finally:
+        L.seam_conv3x3_wino24sx_set_nsplit(before)
+
+
 def test_knobs_restore_the_old_route(ops):
     pc = twin(ops, u24x=T)
     for knob, off in (("W24SX", False), ("WINOGRAD", False), ("WINOGRAD24", 0), ("W24SX_MIN_C", 512), ("W24SX_MIN_BLOCKS", 128)):
