@@ -117,9 +117,11 @@ struct SxpcArgs {
 
 // The second source of the dual form (conv1x1_sxpc_dual): chunks [0, n1) of a tile are its 128 consecutive rows of x = x1 [M, C1],
 // chunks [n1, nchunks) the pixels (n, stride2 ho, stride2 wo) of x2 [N, H2, W2, C2]; SxpcArgs::C = C1 + C2 (the consumers' reduction).
+// A second source is addressed per output pixel (n, ho, wo) of the [N, Ho, Wo] grid; its fields but the pointer, C1 and n1 are filled
+// by sxpc_src_plan and read by sxpc_pixel, for SxpcUp under the same names.
 struct SxpcDual {
     const float* x2;
-    unsigned long long img2_bytes;      // H2 * W2 * C2 * 4
+    unsigned long long img_bytes;       // H2 * W2 * C2 * 4
     int N, C1, n1;
     unsigned HoWo, Wo;
     // row rl of the first image's output grid (rl < BM + HoWo) -> image rl / HoWo = umulhi(rl, m_howo) + rl * one_howo + (rl >= thr):
@@ -139,6 +141,15 @@ struct SxpcUp {
     unsigned m_wo, one_wo;              // the remainder by Wo
     unsigned img_step, row_step, px_step;      // byte steps of top per image / per coarse row (rW K 4) / per coarse pixel (K 4)
 };
+
+// row rl (< BM + HoWo) of the output grid of the first image a tile touches -> (image, ho, wo), by the multiply-high rules above
+template <class Src>
+__device__ __forceinline__ void sxpc_pixel(const Src& s, const unsigned rl, unsigned& nl, unsigned& ho, unsigned& wo) {
+    nl = __umulhi(rl, s.m_howo) + rl * s.one_howo + (rl >= s.thr ? 1u : 0u);
+    const unsigned rem = rl - nl * s.HoWo;
+    ho = __umulhi(rem, s.m_wo) + rem * s.one_wo;
+    wo = rem - ho * s.Wo;
+}
 
 // NG: 32-pixel groups (accumulator tiles) per consumer wave.  4: the forms above, 128 output channels per tile, wave w = channels
 // 32 w of all 128 pixels.  2: the 64-output-channel forms (see "K = 64" below), wave w = channels 32 (w & 1) of pixels 64 (w >> 1).
@@ -195,16 +206,14 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
             const bool live = tiles_left > 0;
             const unsigned row0 = live ? (unsigned)fdivu(tl, p.tiles_n, p.m_tiles_n) * BM : 0u;
             const unsigned n_first = __builtin_amdgcn_readfirstlane(row0 / d.HoWo);       // (a true division: once per tile, any M)
-            const unsigned long long left = (unsigned long long)((unsigned)d.N - n_first) * d.img2_bytes;
-            rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)d.x2 + (size_t)n_first * d.img2_bytes), 0,
+            const unsigned long long left = (unsigned long long)((unsigned)d.N - n_first) * d.img_bytes;
+            rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)d.x2 + (size_t)n_first * d.img_bytes), 0,
                                                     live ? (int)(left > kOob ? kOob : (unsigned)left) : 0, 0x00020000);
             const unsigned rl0 = row0 - n_first * d.HoWo + (unsigned)(ptid >> 4);      // row inside that image's output grid
 #pragma unroll
             for (int r = 0; r < NP; ++r) {
-                const unsigned rl = rl0 + 16 * r;       // < BM + HoWo
-                const unsigned nl = __umulhi(rl, d.m_howo) + rl * d.one_howo + (rl >= d.thr ? 1u : 0u);
-                const unsigned rem = rl - nl * d.HoWo;
-                const unsigned ho = __umulhi(rem, d.m_wo) + rem * d.one_wo, wo = rem - ho * d.Wo;
+                unsigned nl, ho, wo;
+                sxpc_pixel(d, rl0 + 16 * r, nl, ho, wo);
                 const unsigned off = nl * d.img_step + ho * d.row_step + wo * d.px_step + (STEM ? 0u : (unsigned)((ptid & 15) * 16));
                 goff2[r] = row0 + (unsigned)(ptid >> 4) + 16 * r < (unsigned)p.M ? off : kOob;
             }
@@ -250,10 +259,8 @@ __device__ __forceinline__ void sxpc_body(const SxpcArgs& p, const SxpcDual& d, 
             const unsigned row0 = (unsigned)fdivu(tl, p.tiles_n, p.m_tiles_n) * BM;
             const unsigned n_first = __builtin_amdgcn_readfirstlane(row0 / u.HoWo);       // (a true division: once per tile, any M)
             const unsigned r = (unsigned)ptid >> 1;
-            const unsigned rl = row0 - n_first * u.HoWo + r;       // row inside that image's output grid: < BM + HoWo
-            const unsigned nl = __umulhi(rl, u.m_howo) + rl * u.one_howo + (rl >= u.thr ? 1u : 0u);
-            const unsigned rem = rl - nl * u.HoWo;
-            const unsigned ho = __umulhi(rem, u.m_wo) + rem * u.one_wo, wo = rem - ho * u.Wo;
+            unsigned nl, ho, wo;
+            sxpc_pixel(u, row0 - n_first * u.HoWo + r, nl, ho, wo);       // row inside that image's output grid: < BM + HoWo
             const unsigned hs = (unsigned)seam_fpn::nearest_src((int)ho, fh, u.rH), ws = (unsigned)seam_fpn::nearest_src((int)wo, fw, u.rW);
             const unsigned off = nl * u.img_step + hs * u.row_step + ws * u.px_step;
             LDSQ char* const tb = (LDSQ char*)smem + TBL0 + par * TBLB;
@@ -537,7 +544,36 @@ int sxpc_plan(SxpcArgs& a, long long M, int C, int K, int min_c = 256) {
     return 0;
 }
 
-// the dual form: the plain plan of (M, C1 + C2, K) and the second source's geometry
+// The geometry of a second source (Src: SxpcDual or SxpcUp) under the [N, Ho, Wo] output grid: one image of it is `pixels` x px_bytes
+// bytes; output pixel (n, ho, wo) lies img_bytes n + row_step ho + px_step wo bytes in (the upsampled-residual form: ho, wo through
+// nearest_src first).
+template <class Src>
+int sxpc_src_plan(Src& s, long long N, long long Ho, long long Wo, unsigned long long pixels, unsigned long long px_bytes,
+                  unsigned long long row_step, unsigned long long px_step) {
+    const long long HoWo = Ho * Wo;
+    if (pixels >= (1ull << 31) / px_bytes) return 1;        // one image of the source inside a descriptor
+    const unsigned long long img = pixels * px_bytes;
+    // a tile's 128 rows touch at most this many images; their pixels are addressed from the first one's start with 32-bit offsets
+    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
+    if (imgs * img > kOob) return 1;
+    // divisions of the producers: a row of the tile's image span by HoWo (by multiply-high for 2 <= HoWo < BM only: numerators
+    // below BM + HoWo), its remainder by Wo
+    const bool mid = HoWo >= 2 && HoWo < BM;
+    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
+    if (!seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)HoWo)) return 1;
+    s.img_bytes = img;
+    s.N = (int)N; s.HoWo = (unsigned)HoWo; s.Wo = (decltype(s.Wo))Wo;
+    s.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
+    s.one_howo = HoWo == 1 ? 1u : 0u;
+    s.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
+    s.m_wo = seam_fastdiv::magic((unsigned long long)Wo);       // (0 for Wo = 1)
+    s.one_wo = Wo == 1 ? 1u : 0u;
+    // (a step that exceeds 32 bits multiplies an index that is always 0: Ho = 1 / Wo = 1 with a large stride)
+    s.img_step = (unsigned)img; s.row_step = (unsigned)row_step; s.px_step = (unsigned)px_step;
+    return 0;
+}
+
+// the dual form: the plain plan of (M, C1 + C2, K) and x2's pixels (n, stride2 ho, stride2 wo) as the second source
 int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long long Wo, int C1, long long H2, long long W2, int C2, int stride2, int K,
                    int min_c = 256) {
     if (N <= 0 || Ho <= 0 || Wo <= 0 || H2 <= 0 || W2 <= 0 || C1 < CK || C2 < CK || (C1 % CK) || (C2 % CK) || stride2 < 1) return 1;
@@ -545,57 +581,19 @@ int sxpc_dual_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Ho, long lon
     if ((Ho - 1) * stride2 >= H2 || (Wo - 1) * stride2 >= W2) return 1;
     if (Ho * Wo >= (1LL << 31) || N * (Ho * Wo) >= (1LL << 31)) return 1;
     if (sxpc_plan(a, N * Ho * Wo, C1 + C2, K, min_c)) return 1;
-    const long long HoWo = Ho * Wo;
-    if ((unsigned long long)H2 * W2 >= (1ull << 31) / ((unsigned long long)C2 * 4)) return 1;      // one image of x2 inside a descriptor
-    const unsigned long long img2 = (unsigned long long)H2 * W2 * C2 * 4;
-    // a tile's 128 rows touch at most this many images; their pixels are addressed from the first one's start with 32-bit offsets
-    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
-    if (imgs * img2 > kOob) return 1;
-    // divisions of the producers: a row of the tile's image span by HoWo (by multiply-high for 2 <= HoWo < BM only: numerators
-    // below BM + HoWo), its remainder by Wo
-    const bool mid = HoWo >= 2 && HoWo < BM;
-    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
-    if (!seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)HoWo)) return 1;
-    d.img2_bytes = img2;
-    d.N = (int)N; d.C1 = C1; d.n1 = C1 / CK; d.HoWo = (unsigned)HoWo; d.Wo = (unsigned)Wo;
-    d.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
-    d.one_howo = HoWo == 1 ? 1u : 0u;
-    d.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
-    d.m_wo = seam_fastdiv::magic((unsigned long long)Wo);       // (0 for Wo = 1)
-    d.one_wo = Wo == 1 ? 1u : 0u;
-    // (a step that exceeds 32 bits multiplies an index that is always 0: Ho = 1 / Wo = 1 with a large stride)
-    d.img_step = (unsigned)img2;
-    d.row_step = (unsigned)((unsigned long long)stride2 * W2 * C2 * 4);
-    d.px_step = (unsigned)((unsigned long long)stride2 * C2 * 4);
-    return 0;
+    d.C1 = C1; d.n1 = C1 / CK;
+    return sxpc_src_plan(d, N, Ho, Wo, (unsigned long long)H2 * W2, (unsigned long long)C2 * 4,
+                         (unsigned long long)stride2 * W2 * C2 * 4, (unsigned long long)stride2 * C2 * 4);
 }
 
-// the upsampled-residual form: the plain plan of (N Ho Wo, C, K) and the coarse map's geometry
+// the upsampled-residual form: the plain plan of (N Ho Wo, C, K) and the coarse map as the second source
 int sxpc_up_plan(SxpcArgs& a, SxpcUp& u, long long N, long long Ho, long long Wo, int C, int K, long long rH, long long rW) {
     if (N <= 0 || Ho <= 0 || Wo <= 0 || rH <= 0 || rW <= 0) return 1;
     if (N >= (1LL << 31) || Ho >= (1LL << 24) || Wo >= (1LL << 24) || rH >= (1LL << 24) || rW >= (1LL << 24)) return 1;     // (nearest_src: indices exact in fp32)
     if (Ho * Wo >= (1LL << 31) || N * (Ho * Wo) >= (1LL << 31)) return 1;
     if (sxpc_plan(a, N * Ho * Wo, C, K)) return 1;
-    const long long HoWo = Ho * Wo;
-    if ((unsigned long long)rH * rW >= (1ull << 31) / ((unsigned long long)K * 4)) return 1;       // one image of top inside a descriptor
-    const unsigned long long img = (unsigned long long)rH * rW * K * 4;
-    // a tile's 128 rows touch at most this many images; their pixels are addressed from the first one's start with 32-bit offsets
-    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
-    if (imgs * img > kOob) return 1;
-    const bool mid = HoWo >= 2 && HoWo < BM;
-    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
-    if (!seam_fastdiv::exact((unsigned long long)Wo, (unsigned long long)HoWo)) return 1;
-    u.img_bytes = img;
-    u.N = (int)N; u.Ho = (int)Ho; u.Wo = (int)Wo; u.rH = (int)rH; u.rW = (int)rW; u.HoWo = (unsigned)HoWo;
-    u.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
-    u.one_howo = HoWo == 1 ? 1u : 0u;
-    u.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
-    u.m_wo = seam_fastdiv::magic((unsigned long long)Wo);       // (0 for Wo = 1)
-    u.one_wo = Wo == 1 ? 1u : 0u;
-    u.img_step = (unsigned)img;
-    u.row_step = (unsigned)((unsigned long long)rW * K * 4);
-    u.px_step = (unsigned)((unsigned long long)K * 4);
-    return 0;
+    u.Ho = (int)Ho; u.rH = (int)rH; u.rW = (int)rW;
+    return sxpc_src_plan(u, N, Ho, Wo, (unsigned long long)rH * rW, (unsigned long long)K * 4, (unsigned long long)rW * K * 4, (unsigned long long)K * 4);
 }
 
 // the 64-output-channel form: one n-tile of 64 channels, two chunks per tile at the least (one chunk is refused: untested, unused)
@@ -615,26 +613,31 @@ int stem_sxpc_plan(SxpcArgs& a, SxpcDual& d, long long N, long long Hs, long lon
     if (N <= 0 || Hs <= 0 || Ws <= 0 || N >= (1LL << 31) || Hs >= (1LL << 31) - 3 || Ws >= (1LL << 31) - 3) return 1;
     if (Hs * Ws >= (1LL << 31) || N * (Hs * Ws) >= (1LL << 31)) return 1;
     if (sxpc64_plan(a, N * Hs * Ws, 192, 64)) return 1;
-    const long long HoWo = Hs * Ws;
-    if ((unsigned long long)(Hs + 3) * (Ws + 3) >= (1ull << 31) / 48) return 1;      // one frame inside a descriptor
-    const unsigned long long img = (unsigned long long)(Hs + 3) * (Ws + 3) * 48;
-    // a tile's 128 rows touch at most this many frames; their windows are addressed from the first one's start with 32-bit offsets
-    const unsigned long long imgs = std::min<unsigned long long>((unsigned long long)N, (unsigned long long)((BM - 2) / HoWo + 2));
-    if (imgs * img > kOob) return 1;
-    const bool mid = HoWo >= 2 && HoWo < BM;
-    if (mid && !seam_fastdiv::exact((unsigned long long)HoWo, (unsigned long long)(BM + HoWo))) return 1;
-    if (!seam_fastdiv::exact((unsigned long long)Ws, (unsigned long long)HoWo)) return 1;
-    d.img2_bytes = img;
-    d.N = (int)N; d.C1 = 0; d.n1 = 0; d.HoWo = (unsigned)HoWo; d.Wo = (unsigned)Ws;
-    d.m_howo = mid ? seam_fastdiv::magic((unsigned long long)HoWo) : 0u;
-    d.one_howo = HoWo == 1 ? 1u : 0u;
-    d.thr = HoWo >= BM ? (unsigned)HoWo : 0xffffffffu;
-    d.m_wo = seam_fastdiv::magic((unsigned long long)Ws);
-    d.one_wo = Ws == 1 ? 1u : 0u;
-    d.img_step = (unsigned)img;
-    d.row_step = (unsigned)((Ws + 3) * 48);
-    d.px_step = 48u;
-    return 0;
+    d.C1 = 0; d.n1 = 0;
+    return sxpc_src_plan(d, N, Hs, Ws, (unsigned long long)(Hs + 3) * (Ws + 3), 48, (unsigned long long)((Ws + 3) * 48), 48);
+}
+
+// the launch entries' common tail: the I/O fields of a planned SxpcArgs ...
+void sxpc_io(SxpcArgs& a, const float* x, const void* w_packed, const float* scale, const float* shift, const float* res, float* y, int relu) {
+    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = res; a.y = y; a.relu = relu;
+}
+
+// ... and the launch: one persistent block per CU, at most one per tile
+template <auto Kernel, class... Extra>
+int sxpc_launch(int lds_bytes, void* stream, const SxpcArgs& a, const Extra&... extra) {
+    int ncu;
+    const hipError_t e = seam_launch::prepare<Kernel>(lds_bytes, &ncu);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(512), lds_bytes, (hipStream_t)stream, a, extra...);
+    return (int)hipGetLastError();
+}
+
+// the pack entries' launch, behind each entry's own rule for (C, K)
+int sxpc_pack(const float* w, void* w_packed, int K, int C, void* stream) {
+    const size_t total = (size_t)K * C / 8;
+    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(seam_launch::grid256(total)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -653,10 +656,7 @@ long long seam_conv1x1_sxpc_weight_bytes(int K, int C) { return (long long)K * C
 int seam_pack_conv1x1_weight_sxpc(const float* w, void* w_packed, int K, int C, void* stream) {
     SxpcArgs a;
     if (sxpc_plan(a, 1, C, K)) return (int)hipErrorInvalidValue;      // the kernel's own rule for (C, K)
-    const size_t total = (size_t)K * C / 8;
-    const unsigned grid = seam_launch::grid256(total);
-    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
-    return (int)hipGetLastError();
+    return sxpc_pack(w, w_packed, K, C, stream);
 }
 
 /* y[M, K] = act(scale * (x[M, C] . w^T) + shift + residual), fp32 in / out, six-term split-bf16 products: the bits of seam_conv2d_sx
@@ -665,13 +665,8 @@ int seam_conv1x1_sxpc(const float* x, const void* w_packed, const float* scale, 
                       long long M, int C, int K, int relu, void* stream) {
     SxpcArgs a;
     if ((relu != 0 && relu != 1) || sxpc_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    sxpc_io(a, x, w_packed, scale, shift, residual, y, relu);
+    return sxpc_launch<conv1x1_sxpc>(LDS_BYTES, stream, a);
 }
 
 /* 1 when the channel counts and M of a two-source layer suit seam_conv1x1_sxpc_dual (C1, C2 multiples of 64; the plain rule for
@@ -689,14 +684,9 @@ int seam_conv1x1_sxpc_dual(const float* x1, const float* x2, const void* w_packe
     SxpcArgs a;
     SxpcDual d;
     if ((relu != 0 && relu != 1) || !x2 || sxpc_dual_plan(a, d, N, Ho, Wo, C1, H2, W2, C2, stride2, K)) return (int)hipErrorInvalidValue;
-    a.x = x1; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    sxpc_io(a, x1, w_packed, scale, shift, nullptr, y, relu);
     d.x2 = x2;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_dual>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc_dual, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
-    return (int)hipGetLastError();
+    return sxpc_launch<conv1x1_sxpc_dual>(LDS_BYTES, stream, a, d);
 }
 
 /* 1 when seam_conv1x1_sxpc_up takes this lateral: the plain rule for (M, C, K), M == N Ho Wo, rH, rW >= 1 and the geometry rules of
@@ -715,14 +705,9 @@ int seam_conv1x1_sxpc_up(const float* x, const void* w_packed, const float* scal
     SxpcArgs a;
     SxpcUp u;
     if ((relu != 0 && relu != 1) || !top || sxpc_up_plan(a, u, N, Ho, Wo, C, K, rH, rW)) return (int)hipErrorInvalidValue;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    sxpc_io(a, x, w_packed, scale, shift, nullptr, y, relu);
     u.top = top;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_up>(LDS_UP_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc_up, dim3(grid), dim3(512), LDS_UP_BYTES, (hipStream_t)stream, a, u);
-    return (int)hipGetLastError();
+    return sxpc_launch<conv1x1_sxpc_up>(LDS_UP_BYTES, stream, a, u);
 }
 
 /* The `short` entries: conv1x1_sxpc / conv1x1_sxpc_dual on two-chunk reductions, C == 128 / C1 == C2 == 64 with stride2 == 1 */
@@ -733,22 +718,15 @@ int seam_conv1x1_sxpc_short_supported(long long M, int C, int K) {
 
 int seam_pack_conv1x1_weight_sxpc_short(const float* w, void* w_packed, int K, int C, void* stream) {
     if (!seam_conv1x1_sxpc_short_supported(1, C, K)) return (int)hipErrorInvalidValue;
-    const size_t total = (size_t)K * C / 8;
-    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(seam_launch::grid256(total)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
-    return (int)hipGetLastError();
+    return sxpc_pack(w, w_packed, K, C, stream);
 }
 
 int seam_conv1x1_sxpc_short(const float* x, const void* w_packed, const float* scale, const float* shift, const float* residual, float* y,
                             long long M, int C, int K, int relu, void* stream) {
     SxpcArgs a;
     if ((relu != 0 && relu != 1) || C != 2 * CK || sxpc_plan(a, M, C, K, 2 * CK)) return (int)hipErrorInvalidValue;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    sxpc_io(a, x, w_packed, scale, shift, residual, y, relu);
+    return sxpc_launch<conv1x1_sxpc>(LDS_BYTES, stream, a);
 }
 
 int seam_conv1x1_sxpc_dual_short_supported(long long M, int C1, int C2, int K) {
@@ -762,14 +740,9 @@ int seam_conv1x1_sxpc_dual_short(const float* x1, const float* x2, const void* w
     SxpcDual d;
     if ((relu != 0 && relu != 1) || !x2 || C1 != CK || C2 != CK || sxpc_dual_plan(a, d, N, Ho, Wo, C1, H2, W2, C2, 1, K, 2 * CK))
         return (int)hipErrorInvalidValue;
-    a.x = x1; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    sxpc_io(a, x1, w_packed, scale, shift, nullptr, y, relu);
     d.x2 = x2;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc_dual>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc_dual, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
-    return (int)hipGetLastError();
+    return sxpc_launch<conv1x1_sxpc_dual>(LDS_BYTES, stream, a, d);
 }
 
 /* 1 when seam_conv1x1_sxpc64 takes this layer (1x1 / stride 1 / pad 0; K == 64; C >= 128 and a multiple of 64; M >= 1), else 0 */
@@ -782,9 +755,7 @@ int seam_conv1x1_sxpc64_supported(long long M, int C, int K) {
 int seam_pack_conv1x1_weight_sxpc64(const float* w, void* w_packed, int K, int C, void* stream) {
     SxpcArgs a;
     if (sxpc64_plan(a, 1, C, K)) return (int)hipErrorInvalidValue;
-    const size_t total = (size_t)K * C / 8;
-    hipLaunchKernelGGL(sxpc_pack_kernel, dim3(seam_launch::grid256(total)), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)w_packed, K, C);
-    return (int)hipGetLastError();
+    return sxpc_pack(w, w_packed, K, C, stream);
 }
 
 /* y[M, 64] = act(scale * (x[M, C] . w^T) + shift + residual): seam_conv1x1_sxpc's arithmetic (the bits of seam_conv2d_sx with
@@ -793,13 +764,8 @@ int seam_conv1x1_sxpc64(const float* x, const void* w_packed, const float* scale
                         long long M, int C, int K, int relu, void* stream) {
     SxpcArgs a;
     if ((relu != 0 && relu != 1) || sxpc64_plan(a, M, C, K)) return (int)hipErrorInvalidValue;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y; a.relu = relu;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<conv1x1_sxpc64>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(conv1x1_sxpc64, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    sxpc_io(a, x, w_packed, scale, shift, residual, y, relu);
+    return sxpc_launch<conv1x1_sxpc64>(LDS_BYTES, stream, a);
 }
 
 /* 1 when seam_stem_sxpc takes the frame geometry (N frames of Hs x Ws space-to-depth cells), else 0 */
@@ -818,14 +784,9 @@ int seam_stem_sxpc(const float* xp, const void* w_packed, const float* scale, co
     SxpcArgs a;
     SxpcDual d;
     if ((relu != 0 && relu != 1) || !xp || stem_sxpc_plan(a, d, N, Hs, Ws)) return (int)hipErrorInvalidValue;
-    a.x = xp; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y; a.relu = relu;
+    sxpc_io(a, xp, w_packed, scale, shift, nullptr, y, relu);
     d.x2 = xp;
-    int ncu;
-    const hipError_t e = seam_launch::prepare<stem_sxpc>(LDS_BYTES, &ncu);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)(a.total_tiles > ncu ? ncu : a.total_tiles);
-    hipLaunchKernelGGL(stem_sxpc, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a, d);
-    return (int)hipGetLastError();
+    return sxpc_launch<stem_sxpc>(LDS_BYTES, stream, a, d);
 }
 
 }  // extern "C"
