@@ -20,51 +20,16 @@ What is exact and what is bounded (the counts are derived in ``detect_refs``' do
   outside the integer box; box_iou: bit-exact on lattice boxes (NaN at the same places), IOU_ROUNDINGS + 1 = 16 relative
   roundings on float boxes.
 Each test prints its worst error / bound ratio; it must stay below 1."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import detect_refs as DR
+from stress_kit import POISON_WORD as POISON, Buf, P, st
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-GUARD = 1 << 14                 # 4-byte words on each side (64 KiB, keeps 16-byte alignment of the body)
-GUARD_WORD = 0x5A5A5A5A
-POISON = 0x7FC00001             # a NaN in fp32, a large value in the integer outputs
-
-
-class Buf:
-    def __init__(self, shape, dtype):
-        n = int(np.prod(shape))
-        es = torch.empty((), dtype=dtype).element_size()
-        words = (n * es + 3) // 4
-        self.raw = torch.full((2 * GUARD + words,), GUARD_WORD, dtype=torch.int32, device=DEV)
-        self.body = self.raw[GUARD:GUARD + words]
-        self.body.fill_(POISON)
-        self.t = self.body.view(torch.uint8)[:n * es].view(dtype).view(shape)
-
-    def guard_ok(self):
-        return bool((self.raw[:GUARD] == GUARD_WORD).all()) and bool((self.raw[GUARD + self.body.numel():] == GUARD_WORD).all())
-
-    def untouched(self):
-        return bool((self.body == POISON).all())
-
-    def filled(self):
-        return not bool((self.body == POISON).any())
-
-    def bits(self):
-        return self.body.cpu()
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _lib():

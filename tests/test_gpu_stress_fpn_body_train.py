@@ -33,51 +33,15 @@ import torch.nn.functional as F
 
 import fpn_body_stress_cases as SC
 import fpn_train_refs as FR
+from stress_kit import Buf, P, st
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-GUARD = 1 << 18                 # 4-byte words (1 MiB)
-POISON = 0x7FC00001             # a NaN in fp32
-FENCE = 0x5A5A5A5A
 U = FR.U
 # The whole module took 4.0 s on the MI355X (the float64 references on the host included); the limit is three times that,
 # rounded up to 10 s, for a shared and loaded machine.
 SWEEP_LIMIT_S = 20.0
-
-
-class Buf:
-    """An fp32 output of ``shape``: poisoned (or holding ``init`` for a kernel that updates in place), a guard behind it."""
-
-    def __init__(self, shape, init=None):
-        n = int(np.prod(shape))
-        self.raw = torch.empty(n + GUARD, dtype=torch.int32, device=DEV)
-        self.raw.fill_(FENCE)
-        self.words = n
-        self.raw[:n].fill_(POISON)
-        self.t = self.raw[:n].view(torch.float32).view(shape)
-        if init is not None:
-            self.t.copy_(init)
-
-    def guard_ok(self):
-        return bool((self.raw[self.words:] == FENCE).all())
-
-    def untouched(self):
-        return bool((self.raw[:self.words] == POISON).all())
-
-    def written(self):
-        return not bool((self.raw[:self.words] == POISON).any())
-
-    def bits(self):
-        return self.raw[:self.words]
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _lib():
@@ -104,7 +68,7 @@ def _twice(launch, desc, fully_written=True):
     assert a_rc == 0 and b_rc == 0, (desc, a_rc, b_rc)
     assert all(o.guard_ok() for o in a + b), desc
     if fully_written:
-        assert all(o.written() for o in a + b), desc
+        assert all(o.filled() for o in a + b), desc
     assert all(torch.equal(x.bits(), y.bits()) for x, y in zip(a, b)), desc
     return a
 
@@ -285,7 +249,8 @@ def test_stress_subsample_add_bwd():
         dp = cs["dpool"].to(DEV)
 
         def launch():
-            d = Buf((n, h, w, c), init=cs["d"])                    # updated in place: the whole result is compared
+            d = Buf((n, h, w, c))
+            d.t.copy_(cs["d"])                          # updated in place: the whole result is compared
             rc = lib.seam_subsample_add_bwd_f32(P(d.t), P(dp), n, h, w, hp, wp, c, st())
             torch.cuda.synchronize()
             return rc, [d]
@@ -322,7 +287,7 @@ def test_stress_conv3x3s2_dgrad():
                 wp = Buf((9, c, k))
                 assert lib.seam_pack_conv3x3s2_dgrad_f32(P(wt), P(scale), P(wp.t), k, c, st()) == 0
                 torch.cuda.synchronize()
-                assert wp.written() and wp.guard_ok()
+                assert wp.filled() and wp.guard_ok()
                 pk = ops.pack_conv3x3s2_dgrad(wt, scale)
                 assert torch.equal(pk.wp, wp.t)
                 for with_mask in (False, True):
@@ -417,9 +382,9 @@ def test_stress_relu_mask_add():
             return rc, [out]
         (out,) = _twice(launch, cs["name"])
         want = torch.where(cs["y"] > 0, cs["a"] + cs["b"] if cs["b"] is not None else cs["a"], torch.zeros(()))
-        mism = int((out.bits().cpu() != want.view(torch.int32).view(-1)).sum())
+        mism = int((out.bits().cpu().view(-1) != want.view(torch.int32).view(-1)).sum())
         print(f"{cs['name']}: mismatching bit patterns {mism}")
-        assert torch.equal(out.bits().cpu(), want.view(torch.int32).view(-1)), cs["name"]
+        assert torch.equal(out.bits().cpu().view(-1), want.view(torch.int32).view(-1)), cs["name"]
     print("relu_mask_add: bit for bit on every case")
     z = torch.zeros((8, 4), device=DEV)
     for mm, cc, null in ((0, 4, None), (-1, 4, None), (8, 6, None), (8, 0, None), (8, 4, "y"), (8, 4, "a"), (8, 4, "out")):

@@ -24,11 +24,12 @@ e_sx <= 2 e_f32 + 1e-7 with e_f32 measured on the same case.
 import math
 import os
 import random
-import subprocess
 import sys
 import time
 
 import pytest
+
+import stress_kit
 
 pytestmark = pytest.mark.gpu
 
@@ -499,30 +500,16 @@ def child_main(argv):
     only = argv[1:]
     dev = torch.device("cuda:0")
     lib = _native.lib()
-    st = lambda: torch.cuda.current_stream().cuda_stream
-    P = lambda t: None if t is None else t.data_ptr()
-    fails = []
-    GUARD = 1 << 20          # bytes behind every output that must stay untouched
-    guards = []
-
-    def say(*a):
-        print(*a, flush=True)
+    Buf, P, fails, say, st = stress_kit.Buf, stress_kit.P, stress_kit.fails, stress_kit.say, stress_kit.st
+    bufs = []
 
     def poisoned(shape, dtype, which):
-        n = 1
-        for d in shape:
-            n *= d
-        es = torch.empty((), dtype=dtype).element_size()
-        raw = torch.empty(n * es + GUARD, dtype=torch.uint8, device=dev)
-        raw[n * es:].fill_(0x5A)
-        y = raw[:n * es].view(dtype).view(shape)
-        y.fill_(float("nan") if which == 0 else 3.0e4)
-        guards.append(raw[n * es:])
-        return y
+        bufs.append(Buf(shape, dtype, which))
+        return bufs[-1].t
 
     def guards_intact():
-        ok = all(bool((g == 0x5A).all()) for g in guards)
-        guards.clear()
+        ok = all(b.guard_ok() for b in bufs)
+        bufs.clear()
         return ok
 
     def errors(got, ref):
@@ -809,41 +796,17 @@ def child_main(argv):
 @pytest.fixture(scope="module")
 def sweep():
     """One child process runs every family (one ``import torch``); its stdout is what the tests below read."""
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), str(SEED)], cwd=ROOT, env=dict(os.environ), capture_output=True,
-                           text=True, timeout=WALL_S)
-        return {"rc": r.returncode, "out": r.stdout, "err": r.stderr, "hung": False}
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout.decode() if isinstance(e.stdout, bytes) else (e.stdout or "")
-        err = e.stderr.decode() if isinstance(e.stderr, bytes) else (e.stderr or "")
-        return {"rc": -1, "out": out, "err": err, "hung": True}
-
-
-def summary_fields(line):
-    t = line.split()
-    return {t[i]: t[i + 1] for i in range(2, len(t) - 1, 2)}
+    return stress_kit.run_child([sys.executable, os.path.abspath(__file__), str(SEED)], WALL_S, ROOT)
 
 
 def _family_ok(sweep, name):
-    out = sweep["out"]
-    lines = out.splitlines()
-    starts = [ln for ln in lines if ln.startswith("START")]
-    if sweep["hung"]:
-        pytest.fail(f"the sweep did not finish in {WALL_S} s -- last shape started: {starts[-1] if starts else '(none)'}")
-    line = [ln for ln in lines if ln.startswith(f"KERNEL {name} ")]
-    assert line, f"sweep of {name} did not run to its end (rc {sweep['rc']}); last shape started: {starts[-1] if starts else '(none)'}\n" \
-                 + out[-1500:] + sweep["err"][-3000:]
-    failed = [ln for ln in lines if ln.startswith(f"FAIL {name} ")]
-    assert line[0].split()[-1] == "0", "\n".join(failed[:20])
-    summary = [ln for ln in lines if ln.startswith(f"SUMMARY {name} ")]
-    assert summary, name
-    f = summary_fields(summary[0])
+    f = stress_kit.family_ok(sweep, name, WALL_S)
     if name in FAMILIES:
-        assert int(f["cases"]) >= FAMILIES[name][1], summary
+        assert int(f["cases"]) >= FAMILIES[name][1], f
         for key, need in REQUIRED[name].items():
-            assert int(f.get(key, 0)) >= need, (key, need, summary[0])
+            assert int(f.get(key, 0)) >= need, (key, need, f)
         if "div_fast0" in REQUIRED[name]:
-            assert int(f["div_fast0"]) == REQUIRED[name]["div_fast0"], summary[0]
+            assert int(f["div_fast0"]) == REQUIRED[name]["div_fast0"], f
     return f
 
 

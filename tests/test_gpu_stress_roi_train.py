@@ -3,44 +3,17 @@
 results must be bit-identical (fixed-order reductions, no float atomics); each result is compared with the restatement
 of ``roi_train_refs.py`` (exact for the sampler's indices, labels and matches; the bounds of ``test_gpu_roi_train.py``
 for the rest).  Each launcher's refusals must leave every output untouched."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import roi_train_refs as RR
+from stress_kit import Buf, P, st
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-GUARD = 1 << 18                 # 4-byte words (1 MiB)
 NCASE = 40
-
-
-class Buf:
-    def __init__(self, shape, dtype):
-        n = int(np.prod(shape))
-        words = (n * torch.empty((), dtype=dtype).element_size() + 3) // 4
-        self.raw = torch.empty(words + GUARD, dtype=torch.int32, device=DEV)
-        self.raw.fill_(0x5A5A5A5A)
-        self.words = words
-        self.t = self.raw[:words].view(torch.uint8)[:n * torch.empty((), dtype=dtype).element_size()].view(dtype).view(shape)
-        self.raw[:words].fill_(0x7FC00001)          # NaN pattern in fp32, a large value in the integer outputs
-
-    def guard_ok(self):
-        return bool((self.raw[self.words:] == 0x5A5A5A5A).all())
-
-    def untouched(self):
-        return bool((self.raw[:self.words] == 0x7FC00001).all())
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _lib():

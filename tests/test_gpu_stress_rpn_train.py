@@ -11,41 +11,12 @@ import pytest
 import torch
 
 import rpn_train_refs as PR
+from stress_kit import Buf, P, st
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-GUARD = 1 << 18                 # 4-byte words (1 MiB)
 MAX_A, MAX_G = 1 << 20, 128
-
-
-class Buf:
-    def __init__(self, shape, dtype):
-        n = int(np.prod(shape))
-        es = torch.empty((), dtype=dtype).element_size()
-        words = (n * es + 3) // 4
-        self.raw = torch.empty(words + GUARD, dtype=torch.int32, device=DEV)
-        self.raw.fill_(0x5A5A5A5A)
-        self.words = words
-        self.t = self.raw[:words].view(torch.uint8)[:n * es].view(dtype).view(shape)
-        self.raw[:words].fill_(0x7FC00001)          # NaN pattern in fp32, a large value in the integer outputs
-
-    def guard_ok(self):
-        return bool((self.raw[self.words:] == 0x5A5A5A5A).all())
-
-    def untouched(self):
-        return bool((self.raw[:self.words] == 0x7FC00001).all())
-
-    def bits(self):
-        return self.raw[:self.words].cpu()
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _lib():

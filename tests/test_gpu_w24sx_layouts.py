@@ -23,12 +23,12 @@ the limit WALL_S = 16 is four times that.  Measured there too: e_new / e_w24 = 0
 (profiles/w24sx_layout_sweep.txt)."""
 import math
 import os
-import subprocess
 import sys
 import time
 
 import pytest
 
+import stress_kit
 import w24_layout_cases as T
 
 pytestmark = pytest.mark.gpu
@@ -189,14 +189,7 @@ def child_main(argv):
 @pytest.fixture(scope="module")
 def sweep():
     t0 = time.time()
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True,
-                           timeout=WALL_S)
-        res = {"rc": r.returncode, "out": r.stdout, "err": r.stderr, "hung": False}
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout.decode() if isinstance(e.stdout, bytes) else (e.stdout or "")
-        err = e.stderr.decode() if isinstance(e.stderr, bytes) else (e.stderr or "")
-        res = {"rc": -1, "out": out, "err": err, "hung": True}
+    res = stress_kit.run_child([sys.executable, os.path.abspath(__file__)], WALL_S, ROOT)
     res["wall"] = time.time() - t0
     print(f"\nw24sx layout sweep: {res['wall']:.1f} s of wall time (limit {WALL_S} s)")
     return res
