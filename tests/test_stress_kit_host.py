@@ -1,5 +1,5 @@
 """``stress_kit.py`` on the CPU: the kit catches what it exists to catch, each shown by one deliberate edit of a CPU buffer; the
-parent's side reads canned child output; the four ``stress_child_*.py`` import without a GPU and declare the families their test
+parent's side reads canned child output; the five ``stress_child_*.py`` import without a GPU and declare the families their test
 files ask for."""
 import ast
 import importlib
@@ -224,7 +224,8 @@ def asked_families(test_file):
 
 @pytest.mark.parametrize("child, test_file", [("stress_child_conv", "test_gpu_stress.py"), ("stress_child_aux", "test_gpu_stress_aux.py"),
                                               ("stress_child_heads", "test_gpu_stress_heads.py"),
-                                              ("stress_child_train", "test_gpu_stress_train.py")])
+                                              ("stress_child_train", "test_gpu_stress_train.py"),
+                                              ("stress_child_sxpc", "test_gpu_stress_sxpc.py")])
 def test_child_imports_without_a_gpu_and_declares_the_families_asked_for(child, test_file):
     mod = importlib.import_module(child)
     names = [n for n, _ in mod.FAMILIES]
