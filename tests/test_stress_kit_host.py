@@ -225,7 +225,8 @@ def asked_families(test_file):
 @pytest.mark.parametrize("child, test_file", [("stress_child_conv", "test_gpu_stress.py"), ("stress_child_aux", "test_gpu_stress_aux.py"),
                                               ("stress_child_heads", "test_gpu_stress_heads.py"),
                                               ("stress_child_train", "test_gpu_stress_train.py"),
-                                              ("stress_child_sxpc", "test_gpu_stress_sxpc.py")])
+                                              ("stress_child_sxpc", "test_gpu_stress_sxpc.py"),
+                                              ("stress_child_w24sx", "test_gpu_stress_w24sx.py")])
 def test_child_imports_without_a_gpu_and_declares_the_families_asked_for(child, test_file):
     mod = importlib.import_module(child)
     names = [n for n, _ in mod.FAMILIES]
