@@ -21,6 +21,8 @@
 //     out-of-range zero fills (no branches around loads).
 //   Epilogue: the nu half of the output transform in registers, the xi half through a 32 KiB LDS exchange, then
 //     scale/shift (+ residual, ReLU) and 16-byte NHWC stores.
+//   Which blocks exist -- the patch shape per region, or the stacked form of small maps -- is chosen on the host by
+//     seam_wino_layout.h (forms F22_MT1 / F22_MT2, shared with the F(2x4) kernels); wino_plan picks MT and the n-tile split.
 #include <hip/hip_runtime.h>
 #include "seam_device.h"
 #include "seam_launch.h"
@@ -28,8 +30,11 @@
 #include <stdlib.h>
 #include "seam_opts.h"
 #include "seam_pack_items.h"
+#include "seam_wino_layout.h"
 
 namespace {
+
+using namespace seam_wino_layout;      // Layout, choose_layout, wino_ok and the planners' shared tail
 
 __device__ __forceinline__ f32x4 add4(f32x4 a, f32x4 b) {
     const f32x2 lo = pk_add(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1));
@@ -80,7 +85,8 @@ struct WinoArgs {
 };
 
 template <int MT> struct WinoCfg {
-    static constexpr int NPIXMAX = MT == 2 ? 384 : 208;           // raw patch pixels per buffer
+    static constexpr int NPIXMAX = MT == 2 ? F22_MT2.npixmax : F22_MT1.npixmax;    // raw patch pixels per buffer: what the chooser fits
+    static_assert((MT == 2 ? F22_MT2.slots : F22_MT1.slots) == 32 * MT, "the chooser's tile slots are the block's");
     static constexpr int NI = (2 * NPIXMAX + 255) / 256;          // 16-byte raw loads per thread per chunk
 };
 
@@ -447,101 +453,6 @@ __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict_
         seam_pack::wino_item(w, out, i, K, Cin, nch, mode);
 }
 
-// Block layout for one tile variant (32*MT tile slots per block).  Small maps: the whole tile grid of G images per block.
-// Otherwise up to three regions per image: a main region tiled exactly by TX x TY patches, and the right / bottom strips
-// that remain, each tiled by the best patch for ITS shape -- a 100 x 100 tile map takes 157 blocks of 64 instead of 169.
-struct Layout {
-    int nreg, G, stack, PH;
-    int rx0[3], ry0[3], rxe[3], rye[3], TX[3], TY[3], bx[3], by[3];
-    long per_img, blocks;      // blocks: per n-tile, for N images
-};
-
-inline bool patch_ok(int tx, int ty, int cap, int npixmax) { return tx >= 1 && ty >= 1 && tx * ty <= cap && (2 * tx + 2) * (2 * ty + 2) <= npixmax; }
-
-// best uniform tiling of a w x h tile rectangle: fewest blocks, then the smallest raw patch
-inline long best_uniform(int w, int h, int cap, int npixmax, int& TX, int& TY) {
-    long best = -1, best_cost = -1;
-    for (int ty = 1; ty <= cap && ty <= h; ++ty)
-        for (int tx = 1; tx * ty <= cap && tx <= w; ++tx) {
-            if (!patch_ok(tx, ty, cap, npixmax)) continue;
-            const long nb = (long)((w + tx - 1) / tx) * ((h + ty - 1) / ty);
-            const long cost = nb * 4096 + (2 * tx + 2) * (2 * ty + 2);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = nb; TX = tx; TY = ty; }
-        }
-    return best;
-}
-
-inline Layout choose_layout(int N, int tiles_x, int tiles_y, int mt, size_t in_img_bytes, size_t out_img_bytes) {
-    const int cap = 32 * mt, npixmax = mt == 2 ? 384 : 208;
-    Layout L;
-    L.nreg = 1; L.G = 1; L.stack = 0; L.PH = 0;
-    // Stacked candidate (maps narrower than a block): TY consecutive tile rows of the batch at full width per block.
-    Layout S;
-    S.blocks = -1;
-    if (tiles_x <= cap) {
-        const int t = tiles_y, pitch = 2 * t + 2, pw = 2 * tiles_x + 2;
-        for (int ty = cap / tiles_x; ty >= 1; --ty) {
-            int phmax = 0, gmax = 0;
-            for (int b = 0; b < t; ++b) {                                // block starts repeat with period <= tiles_y
-                const int tyf = (int)(((long)b * ty) % t);
-                const int last = tyf + ty - 1;
-                const int gl = last / t, tyl = last - gl * t;
-                const int span = pitch * gl + 2 * tyl + 4 - 2 * tyf;
-                if (span > phmax) phmax = span;
-                if (gl + 1 > gmax) gmax = gl + 1;
-            }
-            if (phmax * pw > npixmax) continue;
-            if ((size_t)gmax * in_img_bytes >= kOob || (size_t)gmax * out_img_bytes >= kOob) continue;
-            S.nreg = 1; S.stack = 1; S.PH = phmax; S.G = gmax;
-            S.rx0[0] = S.ry0[0] = 0; S.rxe[0] = tiles_x; S.rye[0] = tiles_y; S.TX[0] = tiles_x; S.TY[0] = ty; S.bx[0] = S.by[0] = 1;
-            S.per_img = 1;
-            S.blocks = ((long)N * t + ty - 1) / ty;
-            break;
-        }
-    }
-    // one region (uniform tiling) is the baseline
-    long best_blocks = best_uniform(tiles_x, tiles_y, cap, npixmax, L.TX[0], L.TY[0]);
-    L.rx0[0] = L.ry0[0] = 0; L.rxe[0] = tiles_x; L.rye[0] = tiles_y;
-    L.bx[0] = (tiles_x + L.TX[0] - 1) / L.TX[0]; L.by[0] = (tiles_y + L.TY[0] - 1) / L.TY[0];
-    // main region + strips
-    for (int ty = 1; ty <= cap && ty <= tiles_y; ++ty)
-        for (int tx = 1; tx * ty <= cap && tx <= tiles_x; ++tx) {
-            if (!patch_ok(tx, ty, cap, npixmax)) continue;
-            const int mx = tiles_x / tx, my = tiles_y / ty;              // exact blocks of the main region
-            const int wm = mx * tx, hm = my * ty;
-            if (wm == 0 || hm == 0) continue;
-            Layout C;
-            C.G = 1; C.nreg = 1; C.stack = 0; C.PH = 0;
-            C.rx0[0] = 0; C.ry0[0] = 0; C.rxe[0] = wm; C.rye[0] = hm; C.TX[0] = tx; C.TY[0] = ty; C.bx[0] = mx; C.by[0] = my;
-            long nb = (long)mx * my;
-            if (wm < tiles_x) {                                          // right strip: full height
-                const int r = C.nreg++;
-                const long b = best_uniform(tiles_x - wm, tiles_y, cap, npixmax, C.TX[r], C.TY[r]);
-                C.rx0[r] = wm; C.ry0[r] = 0; C.rxe[r] = tiles_x; C.rye[r] = tiles_y;
-                C.bx[r] = (tiles_x - wm + C.TX[r] - 1) / C.TX[r]; C.by[r] = (tiles_y + C.TY[r] - 1) / C.TY[r];
-                nb += b;
-            }
-            if (hm < tiles_y) {                                          // bottom strip: under the main region only
-                const int r = C.nreg++;
-                const long b = best_uniform(wm, tiles_y - hm, cap, npixmax, C.TX[r], C.TY[r]);
-                C.rx0[r] = 0; C.ry0[r] = hm; C.rxe[r] = wm; C.rye[r] = tiles_y;
-                C.bx[r] = (wm + C.TX[r] - 1) / C.TX[r]; C.by[r] = (tiles_y - hm + C.TY[r] - 1) / C.TY[r];
-                nb += b;
-            }
-            if (nb < best_blocks) {
-                best_blocks = nb;
-                L = C;
-            }
-        }
-    L.per_img = 0;
-    for (int r = 0; r < L.nreg; ++r) L.per_img += (long)L.bx[r] * L.by[r];
-    L.blocks = L.per_img * N;
-    if (S.blocks > 0 && S.blocks < L.blocks) return S;
-    return L;
-}
-
-inline bool wino_ok(int C, int K, int R, int S, int stride) { return R == 3 && S == 3 && stride == 1 && C % 8 == 0 && K % 32 == 0 && C >= 8; }
-
 }  // namespace
 
 extern "C" {
@@ -568,7 +479,7 @@ static int wino_plan(WinoArgs& a, int N, int H, int W, int C, int K, int pad, in
     const int tiles_x = (a.Wo + 1) / 2, tiles_y = (a.Ho + 1) / 2;
     const int force_mt = seam_opt::get(seam_opt::WINO_MT);    // kernel experiments
     const size_t in_b = (size_t)H * W * C * 4, out_b = (size_t)a.Ho * a.Wo * K * 4;
-    const Layout p2 = choose_layout(N, tiles_x, tiles_y, 2, in_b, out_b), p1 = choose_layout(N, tiles_x, tiles_y, 1, in_b, out_b);
+    const Layout p2 = choose_layout(F22_MT2, N, tiles_x, tiles_y, in_b, out_b, kOob), p1 = choose_layout(F22_MT1, N, tiles_x, tiles_y, in_b, out_b, kOob);
     a.tiles_n = K / 32;
     a.nchunks = C / 8;
     // Tile variant: a 64-tile block costs ~1.9x a 32-tile block (same weight stream, twice the MFMAs); take the 32-tile
@@ -576,29 +487,20 @@ static int wino_plan(WinoArgs& a, int N, int H, int W, int C, int K, int pad, in
     mt = (p1.blocks * 100 < p2.blocks * 190 || p2.blocks * a.tiles_n < 1024) ? 1 : 2;
     if (force_mt == 1 || force_mt == 2) mt = force_mt;
     const Layout& pp = mt == 2 ? p2 : p1;
-    a.nreg = pp.nreg; a.G = pp.G; a.per_img = (int)pp.per_img;
-    a.stack = pp.stack; a.PH = pp.PH; a.tiles_y = tiles_y;
-    for (int r = 0; r < 3; ++r) {
-        const int q = r < pp.nreg ? r : 0;
-        a.rx0[r] = pp.rx0[q]; a.ry0[r] = pp.ry0[q]; a.rxe[r] = pp.rxe[q]; a.rye[r] = pp.rye[q];
-        a.TX[r] = pp.TX[q]; a.TY[r] = pp.TY[q]; a.bx[r] = pp.bx[q]; a.by[r] = pp.by[q];
-    }
-    blocks = pp.blocks * a.tiles_n;
-    {
-        // n-tile split (see the kernel's tile decode): as many XCD groups as it takes for a group's share of the weights to sit in
-        // its L2 beside the patches (<= 2.5 MB), when the launch is large enough for every group to keep its CUs busy
-        const int want = seam_opt::get(seam_opt::WINO_NSPLIT);      // 0: this rule; > 0: forced (experiments)
-        int ns = 1;
-        const size_t wbytes = (size_t)16 * K * C * 4;
-        if (want > 0) ns = want;
-        else while (ns < 8 && wbytes / ns > (size_t)2560 * 1024) ns <<= 1;
-        while (ns > 1 && (a.tiles_n % ns || 8 % ns || pp.blocks * (a.tiles_n / ns) < 8L * 64)) ns >>= 1;
-        a.nsplit = ns < 1 ? 1 : ns;
-        a.tns = a.tiles_n / a.nsplit;
-        const int parts = 8 / a.nsplit;
-        a.part_q = (int)(pp.blocks / parts); a.part_r = (int)(pp.blocks % parts);
-        if (a.nsplit > 1) blocks = 8L * (a.part_q + (a.part_r ? 1 : 0)) * a.tns;
-    }
+    set_layout(a, pp, tiles_y);
+    // n-tile split (see the kernel's tile decode): as many XCD groups as it takes for a group's share of the weights to sit in
+    // its L2 beside the patches (<= 2.5 MB), when the launch is large enough for every group to keep its CUs busy
+    const int want = seam_opt::get(seam_opt::WINO_NSPLIT);      // 0: this rule; > 0: forced (experiments)
+    int ns = 1;
+    const size_t wbytes = (size_t)16 * K * C * 4;
+    if (want > 0) ns = want;
+    else while (ns < 8 && wbytes / ns > (size_t)2560 * 1024) ns <<= 1;
+    // This floor first, split_ntiles' divisor loop second, ends where one loop over both conditions does, because each, once met,
+    // stays met as ns halves: tiles_n / ns only grows; and split_ntiles wants tiles_n % ns == 0 AND 8 % ns == 0 -- the second
+    // makes ns a power of two, so every further ns >> 1 is an exact half and divides both again (tiles_n % ns alone would not
+    // do: 5 divides 5, 5 >> 1 = 2 does not).  Keep `8 % ns` in split_ntiles' loop, or fold this floor back into it.
+    while (ns > 1 && pp.blocks * (a.tiles_n / ns) < 8L * 64) ns >>= 1;
+    blocks = split_ntiles(a, pp.blocks, ns);
     if (blocks > 0x7fffffffL) return (int)hipErrorInvalidValue;
     return 0;
 }
@@ -611,7 +513,7 @@ int seam_wino_slot_fill_pct(int N, int H, int W, int C, int K, int pad) {
     long blocks;
     if (wino_plan(a, N, H, W, C, K, pad, mt, blocks)) return 0;
     const double tiles = (double)N * ((a.Wo + 1) / 2) * ((a.Ho + 1) / 2) * a.tiles_n;
-    const long work = a.nsplit > 1 ? ((long)(8 / a.nsplit) * a.part_q + a.part_r) * a.tiles_n : blocks;     // without the padding blocks
+    const long work = patch_blocks(a) * a.tiles_n;     // without the padding blocks of an n-tile split
     return (int)(100.0 * tiles / ((double)work * 32 * mt));
 }
 
@@ -622,7 +524,7 @@ long long seam_wino_issue_slots(int N, int H, int W, int C, int K, int pad) {
     int mt;
     long blocks;
     if (wino_plan(a, N, H, W, C, K, pad, mt, blocks)) return 0;
-    const long work = a.nsplit > 1 ? ((long)(8 / a.nsplit) * a.part_q + a.part_r) * a.tiles_n : blocks;
+    const long work = patch_blocks(a) * a.tiles_n;
     return (long long)work * 32 * mt * 16;
 }
 

@@ -743,7 +743,7 @@ long long seam_wino24_issue_slots(int N, int H, int W, int C, int K, int pad) {
     Wino24Args a;
     long blocks;
     if (wino24_plan(a, N, H, W, C, K, pad, blocks)) return 0;
-    const long work = a.nsplit > 1 ? ((long)(8 / a.nsplit) * a.part_q + a.part_r) * a.tiles_n : blocks;     // without the padding blocks
+    const long work = patch_blocks(a) * a.tiles_n;     // without the padding blocks of an n-tile split
     return (long long)work * a.nt * 32 * 24;
 }
 

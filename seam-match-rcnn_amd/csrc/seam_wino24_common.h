@@ -1,7 +1,7 @@
-// seam_wino24_common.h -- what the F(2x4,3x3) Winograd kernel files share: the launch arguments and their planner (block layout
-// chooser, n-tile rule), the raw-patch loader with its LDS rules, the symmetric block w24_block (K loop of conv3x3_wino24<NT> or,
-// SX, of conv3x3_wino24sx; one epilogue) and the block's tile decode.  seam_wino24.hip (fp32 MFMAs) and seam_wino24sx.hip (six-term
-// split-bf16 MFMAs) include it; each describes its own kernel.
+// seam_wino24_common.h -- what the F(2x4,3x3) Winograd kernel files share: the launch arguments and their planner (the n-tile rules
+// and the fastdiv magics; the block layout comes from seam_wino_layout.h, form F24), the raw-patch loader with its LDS rules, the
+// symmetric block w24_block (K loop of conv3x3_wino24<NT> or, SX, of conv3x3_wino24sx; one epilogue) and the block's tile decode.
+// seam_wino24.hip (fp32 MFMAs) and seam_wino24sx.hip (six-term split-bf16 MFMAs) include it; each describes its own kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "seam_device.h"
@@ -11,8 +11,11 @@
 #include "seam_launch.h"
 #include "seam_opts.h"
 #include "seam_split.h"
+#include "seam_wino_layout.h"
 
 namespace {
+
+using namespace seam_wino_layout;      // Layout, choose_layout, wino_ok and the planners' shared tail
 
 #ifndef SEAM_W24_PK
 #define SEAM_W24_PK 1       // 1 (default): the in-loop input transform on packed fp32 VALU ops; 0: scalar-lane v_fma_f32 / v_add_f32
@@ -94,7 +97,7 @@ struct Wino24Args {
     int Ho, Wo, pad, relu;
     // Up to three regions tile an image (main region + right strip + bottom strip), each with its own block patch shape,
     // or -- stacked mode, maps narrower than a block -- TY[0] consecutive tile rows of the whole batch per block
-    // (see seam_wino.hip; identical conventions, only the tile is 4 output columns wide).
+    // (the conventions of seam_wino.hip's WinoArgs, chosen by the same seam_wino_layout.h; only the tile is 4 output columns wide).
     int nreg;
     int rx0[3], ry0[3];
     int rxe[3], rye[3];
@@ -123,10 +126,11 @@ struct Wino24Args {
 };
 
 
-constexpr int NPIXMAX = 384;                       // raw patch pixels per buffer (3 x 16-byte loads per thread per chunk)
+constexpr int NPIXMAX = F24.npixmax;                // raw patch pixels per buffer (384: 3 x 16-byte loads per thread per chunk)
 constexpr int NI = (2 * NPIXMAX + 255) / 256;
-constexpr int ENTMAX = 672;                        // 16-byte LDS entries per channel half (row pairs x PR, see the kernel)
+constexpr int ENTMAX = F24.entmax;                  // 16-byte LDS entries per channel half (672; row pairs x PR, see the kernel)
 constexpr int RAWB = (2 * ENTMAX + 1) * 16;        // bytes per raw buffer (+1 dump slot for idle loader lanes)
+static_assert(F24.tile_w == 4 && F24.slots == 32, "the chooser's tile and tile slots are the block's");
 
 // NT = 32-channel n-tiles per block.  NT = 1: 96 accumulator VGPRs, two blocks per CU.  NT = 2: 192 accumulators (AccVGPRs), one block
 // per CU, one wave per SIMD: every A fragment (the transform's output) and the raw patch feed twice the MFMAs.  Measured on this
@@ -724,104 +728,6 @@ __device__ __forceinline__ void w24_tile(const Wino24Args& p, char* smem) {
     else w24_block<NT, 0, SX>(p, smem, reg, rb, tm, tn, tm_img);
 }
 
-// ---- block layout (32 tile slots of 2 x 4 outputs per block) --------------------------------------------------------
-struct Layout {
-    int nreg, G, stack, PH;
-    int rx0[3], ry0[3], rxe[3], rye[3], TX[3], TY[3], bx[3], by[3];
-    long per_img, blocks;      // blocks: per n-tile, for N images
-};
-
-constexpr int CAP = 32;
-
-// LDS entries per channel half for a patch of tx tiles x ph rows (the kernel's HS / PR / NENT)
-inline int lds_entries(int tx, int ph) {
-    const int hs = (tx + 1) | 1, pr = 8 * hs + (tx & 7), n0 = pr * ((ph + 1) / 2);
-    return n0 + ((4 - n0) & 7);
-}
-
-inline bool patch_ok(int tx, int ty) {
-    return tx >= 1 && ty >= 1 && tx * ty <= CAP && (4 * tx + 2) * (2 * ty + 2) <= NPIXMAX && lds_entries(tx, 2 * ty + 2) <= ENTMAX;
-}
-
-inline long best_uniform(int w, int h, int& TX, int& TY) {
-    long best = -1, best_cost = -1;
-    for (int ty = 1; ty <= CAP && ty <= h; ++ty)
-        for (int tx = 1; tx * ty <= CAP && tx <= w; ++tx) {
-            if (!patch_ok(tx, ty)) continue;
-            const long nb = (long)((w + tx - 1) / tx) * ((h + ty - 1) / ty);
-            const long cost = nb * 4096 + (4 * tx + 2) * (2 * ty + 2);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = nb; TX = tx; TY = ty; }
-        }
-    return best;
-}
-
-inline Layout choose_layout(int N, int tiles_x, int tiles_y, size_t in_img_bytes, size_t out_img_bytes) {
-    Layout L;
-    L.nreg = 1; L.G = 1; L.stack = 0; L.PH = 0;
-    Layout S;
-    S.blocks = -1;
-    if (tiles_x <= CAP) {      // stacked candidate: TY consecutive tile rows of the batch at full width per block
-        const int t = tiles_y, pitch = 2 * t + 2, pw = 4 * tiles_x + 2;
-        for (int ty = CAP / tiles_x; ty >= 1; --ty) {
-            int phmax = 0, gmax = 0;
-            for (int b = 0; b < t; ++b) {
-                const int tyf = (int)(((long)b * ty) % t);
-                const int last = tyf + ty - 1;
-                const int gl = last / t, tyl = last - gl * t;
-                const int span = pitch * gl + 2 * tyl + 4 - 2 * tyf;
-                if (span > phmax) phmax = span;
-                if (gl + 1 > gmax) gmax = gl + 1;
-            }
-            if (phmax * pw > NPIXMAX || lds_entries(tiles_x, phmax) > ENTMAX) continue;
-            if ((size_t)gmax * in_img_bytes >= kOob || (size_t)gmax * out_img_bytes >= kOob) continue;
-            S.nreg = 1; S.stack = 1; S.PH = phmax; S.G = gmax;
-            S.rx0[0] = S.ry0[0] = 0; S.rxe[0] = tiles_x; S.rye[0] = tiles_y; S.TX[0] = tiles_x; S.TY[0] = ty; S.bx[0] = S.by[0] = 1;
-            S.per_img = 1;
-            S.blocks = ((long)N * t + ty - 1) / ty;
-            break;
-        }
-    }
-    long best_blocks = best_uniform(tiles_x, tiles_y, L.TX[0], L.TY[0]);
-    L.rx0[0] = L.ry0[0] = 0; L.rxe[0] = tiles_x; L.rye[0] = tiles_y;
-    L.bx[0] = (tiles_x + L.TX[0] - 1) / L.TX[0]; L.by[0] = (tiles_y + L.TY[0] - 1) / L.TY[0];
-    for (int ty = 1; ty <= CAP && ty <= tiles_y; ++ty)
-        for (int tx = 1; tx * ty <= CAP && tx <= tiles_x; ++tx) {
-            if (!patch_ok(tx, ty)) continue;
-            const int mx = tiles_x / tx, my = tiles_y / ty;
-            const int wm = mx * tx, hm = my * ty;
-            if (wm == 0 || hm == 0) continue;
-            Layout C;
-            C.G = 1; C.nreg = 1; C.stack = 0; C.PH = 0;
-            C.rx0[0] = 0; C.ry0[0] = 0; C.rxe[0] = wm; C.rye[0] = hm; C.TX[0] = tx; C.TY[0] = ty; C.bx[0] = mx; C.by[0] = my;
-            long nb = (long)mx * my;
-            if (wm < tiles_x) {
-                const int r = C.nreg++;
-                const long b = best_uniform(tiles_x - wm, tiles_y, C.TX[r], C.TY[r]);
-                C.rx0[r] = wm; C.ry0[r] = 0; C.rxe[r] = tiles_x; C.rye[r] = tiles_y;
-                C.bx[r] = (tiles_x - wm + C.TX[r] - 1) / C.TX[r]; C.by[r] = (tiles_y + C.TY[r] - 1) / C.TY[r];
-                nb += b;
-            }
-            if (hm < tiles_y) {
-                const int r = C.nreg++;
-                const long b = best_uniform(wm, tiles_y - hm, C.TX[r], C.TY[r]);
-                C.rx0[r] = 0; C.ry0[r] = hm; C.rxe[r] = wm; C.rye[r] = tiles_y;
-                C.bx[r] = (wm + C.TX[r] - 1) / C.TX[r]; C.by[r] = (tiles_y - hm + C.TY[r] - 1) / C.TY[r];
-                nb += b;
-            }
-            if (nb < best_blocks) {
-                best_blocks = nb;
-                L = C;
-            }
-        }
-    L.per_img = 0;
-    for (int r = 0; r < L.nreg; ++r) L.per_img += (long)L.bx[r] * L.by[r];
-    L.blocks = L.per_img * N;
-    if (S.blocks > 0 && S.blocks < L.blocks) return S;
-    return L;
-}
-
-inline bool wino_ok(int C, int K, int R, int S, int stride) { return R == 3 && S == 3 && stride == 1 && C % 8 == 0 && K % 32 == 0 && C >= 8; }
-
 // n-tiles per block.  NT = 2 (one block per CU, 192 accumulators in AccVGPRs, every A fragment and the raw patch feeding twice
 // the MFMAs) is built and parity-clean but NOT the default: as compiled by hipcc 7.2 it ties on the 200^2 layers and loses
 // 3-13 % elsewhere -- the register allocator parks the loop-invariant LDS / load addresses and 8 transform registers in spare
@@ -863,28 +769,13 @@ inline int wino24_plan(Wino24Args& a, int N, int H, int W, int C, int K, int pad
     if (a.Ho <= 0 || a.Wo <= 0) return (int)hipErrorInvalidValue;
     if ((size_t)H * W * C * 4 >= kOob || (size_t)a.Ho * a.Wo * K * 4 >= kOob) return (int)hipErrorInvalidValue;
     const int tiles_x = (a.Wo + 3) / 4, tiles_y = (a.Ho + 1) / 2;
-    const Layout pp = choose_layout(N, tiles_x, tiles_y, (size_t)H * W * C * 4, (size_t)a.Ho * a.Wo * K * 4);
+    const Layout pp = choose_layout(F24, N, tiles_x, tiles_y, (size_t)H * W * C * 4, (size_t)a.Ho * a.Wo * K * 4, kOob);
     a.nt = force_nt ? force_nt : wino24_nt(K, C, pp.blocks * (K / 32));
     a.tiles_n = K / (32 * a.nt);
     a.nchunks = C / 8;
-    a.nreg = pp.nreg; a.G = pp.G; a.per_img = (int)pp.per_img;
-    a.stack = pp.stack; a.PH = pp.PH; a.tiles_y = tiles_y;
-    for (int r = 0; r < 3; ++r) {
-        const int q = r < pp.nreg ? r : 0;
-        a.rx0[r] = pp.rx0[q]; a.ry0[r] = pp.ry0[q]; a.rxe[r] = pp.rxe[q]; a.rye[r] = pp.rye[q];
-        a.TX[r] = pp.TX[q]; a.TY[r] = pp.TY[q]; a.bx[r] = pp.bx[q]; a.by[r] = pp.by[q];
-    }
-    blocks = pp.blocks * a.tiles_n;
-    if (tiles) *tiles = blocks;
-    {
-        int ns = nsplit_rule(C, K, pp.blocks);
-        while (ns > 1 && (a.tiles_n % ns || 8 % ns)) ns >>= 1;
-        a.nsplit = ns < 1 ? 1 : ns;
-        a.tns = a.tiles_n / a.nsplit;
-        const int parts = 8 / a.nsplit;
-        a.part_q = (int)(pp.blocks / parts); a.part_r = (int)(pp.blocks % parts);
-        if (a.nsplit > 1) blocks = 8L * (a.part_q + (a.part_r ? 1 : 0)) * a.tns;
-    }
+    set_layout(a, pp, tiles_y);
+    if (tiles) *tiles = pp.blocks * a.tiles_n;
+    blocks = split_ntiles(a, pp.blocks, nsplit_rule(C, K, pp.blocks));
     if (blocks >= (1L << 24)) return (int)hipErrorInvalidValue;
     // fdivu numerator bounds: a tile index (< blocks + grid, grid < 2^16) by tiles_n, a block's j by tns; tm by per_img; rb < per_img
     // by bx; stacked: a tile row R < (tm + 1) * TY by tiles_y, a patch row (< 2^15 + pitch) by pitch; a slot id, patch pixel (< 2^16)

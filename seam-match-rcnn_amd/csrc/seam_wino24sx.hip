@@ -144,7 +144,7 @@ int seam_wino24_layout(int N, int H, int W, int C, int K, int pad, int sx, int* 
         out[14 + r] = used ? a.bx[r] : 0;
         out[17 + r] = used ? a.by[r] : 0;
     }
-    out[20] = (8 / a.nsplit) * a.part_q + a.part_r;
+    out[20] = (int)patch_blocks(a);
     out[21] = (int)blocks;
     out[22] = out[23] = 0;
     return 0;

@@ -2,7 +2,7 @@
 launch's block layout from the library (``seam_wino24_layout``, csrc/seam_wino24sx.hip).  Pure Python: no torch, no device.
 
 How a launch of ``conv3x3_wino24sx`` / ``conv3x3_wino24<NT>`` is laid out is decided by ``choose_layout``
-(csrc/seam_wino24_common.h) from the output grid alone: tiles_x = ceil(Wo / 4), tiles_y = ceil(Ho / 2) and, for the stacked form,
+(csrc/seam_wino_layout.h, form F24) from the output grid alone: tiles_x = ceil(Wo / 4), tiles_y = ceil(Ho / 2) and, for the stacked form,
 the batch.  ``w24_tile`` then picks one of four instantiations of ``w24_block`` per region from HS = (TX + 1) | 1: 9, 5, 3 or the
 run-time form (``RT`` below).  Every case names the layout it exists for in ``expect``; tests/test_w24_layout_cases_host.py asks
 the library for each case's layout and fails where a case does not reach its branch, before anything is launched.
