@@ -584,18 +584,34 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm(const Con
 }
 
 // =====================================================================================================================
-// Split-bf16 variant ("bx3"): fp32 activations in HBM, 3 bf16 MFMAs per product, fp32 accumulate.
-//   a = a_hi + a_lo (both bf16, a_hi = rn(a), a_lo = rn(a - a_hi)):  a*b ~= a_hi*b_hi + a_hi*b_lo + a_lo*b_hi, relative
-//   error <= ~3 * 2^-18 per product (the dropped lo*lo term and the two roundings of the lo parts) -- 1e-5, two orders
-//   inside the 1e-3 contract, with the fp32 exponent range (no overflow / underflow hazards of an fp16 split).
-//   v_mfma_f32_32x32x16_bf16 issues 16x the FLOPs of the fp32 MFMA per cycle, so three of them per k-step are still
-//   5.3x faster than the exact-fp32 path on the matrix pipe.
-// Operands: the A gather is the fp32 kernel's (same buffer loads, same chunk walk: 32 k-values = 128 B per row);
-//   the split of A happens ONCE per block at the LDS store (10 VALU per 16 B).  Weights are split at pack time
-//   (seam_pack_conv_weight_bx3): a packed row of a chunk is [32 hi | 32 lo] bf16 = the same 128 B as an fp32 row.
-// LDS: hi and lo planes, rows of exactly 64 B (32 bf16), XOR-swizzled 16-B slots (slot ^ ((row >> 2) & 3)): the
-//   ds_read_b128 lane groups {0-3,12-15,20-27}/{4-11,16-19,28-31} land on 4 distinct slots => conflict-free without
-//   padding; 64 KiB per block at 128x128 (two blocks per CU).
+// Split-bf16 kernels: fp32 activations in HBM, the product as bf16 piece products on the matrix pipe, fp32 accumulate.
+// ONE tile body (seam_igemm_split_tile.h) with two forms, which differ in the number of planes per operand, the cut of an A
+// vector, the packed weight layout, the term table and the tile's tail; conv_igemm_bx3 / conv_igemm_sx wrap it.
+// Two planes ("bx3", FormBx3): a = a_hi + a_lo (both bf16, a_hi = rn(a), a_lo = rn(a - a_hi)):
+//   a*b ~= a_hi*b_hi + a_hi*b_lo + a_lo*b_hi, relative error <= ~3 * 2^-18 per product (the dropped lo*lo term and the two
+//   roundings of the lo parts) -- 1e-5, two orders inside the 1e-3 contract, with the fp32 exponent range (no overflow /
+//   underflow hazards of an fp16 split).  v_mfma_f32_32x32x16_bf16 issues 16x the FLOPs of the fp32 MFMA per cycle, so three
+//   of them per k-step are still 5.3x faster than the exact-fp32 path on the matrix pipe.
+//   Weights (seam_pack_conv_weight_bx3): a packed row of a chunk is [32 hi | 32 lo] bf16 = the same 128 B as an fp32 row.
+//   LDS: 64 KiB per block at 128x128 (two blocks per CU).  Tail: the element-wise epilogue.
+// Three planes ("sx", FormSx<TERMS>): the fp32 product itself.  a = a0 + a1 + a2, three bf16 pieces cut by TRUNCATION:
+//   a0 = the top 16 bits of a, a1 = the top 16 bits of a - a0, a2 = a - a0 - a1.  Both subtractions are exact in fp32 (the
+//   remainders have <= 16 and <= 8 significand bits), so the pieces sum back to a exactly; truncation never rounds up, so a
+//   finite a near FLT_MAX has finite pieces.  Every piece product ai*bj has a 16-bit significand: exact in the fp32 accumulator.
+//   TERMS = 6 keeps i + j <= 2: what is dropped (a1b2 + a2b1 + a2b2) is < 2^-22 |ab|, one fp32 rounding of the product.
+//   TERMS = 9 keeps all: the exact fp32 product; only the order of the fp32 additions differs from the fma chain.
+//   Within a k-step the terms are issued smallest first (i + j descending), so the low-order terms meet before a0b0.
+//   Denormals / tiny inputs: the pieces of |a| < 2^-110 reach below the bf16 denormal step 2^-133 and lose those bits
+//   (absolute error < 2^-133 |b|, and the matrix unit may flush denormal pieces): invisible at fp32 scale.  Inf / NaN
+//   inputs: a - a0 = NaN, the outputs that read them are NaN (the fp32 kernel gives Inf for Inf inputs).
+//   Weights (seam_pack_conv_weight_sx): [n_slab][chunk][plane 0..2][slab_bn rows][32 bf16] -- 192 B per row-chunk.
+//   LDS: 96 KiB at 128 x 128, one block per CU.  Tail: the fp32 kernel's 16-byte epilogue when K % 4 == 0.
+//   The split itself (top16, split3_bf16) lives in seam_split.h, shared with conv1x1_sxpc (seam_pwsx.hip).
+// Shared pipeline: the A gather is the fp32 kernel's (same buffer loads, same chunk walk: 32 k-values = 128 B per row); the
+//   split of A happens ONCE per block at the LDS store (10 VALU per 16 B in the two-plane form); weights are split at pack
+//   time; a ring of two register sets.  LDS: one plane per piece, rows of exactly 64 B (32 bf16), XOR-swizzled 16-B slots
+//   (slot ^ ((row >> 2) & 3)): the ds_read_b128 lane groups {0-3,12-15,20-27}/{4-11,16-19,28-31} land on 4 distinct slots
+//   => conflict-free without padding.
 
 __device__ __forceinline__ void split_bf16(const f32x4 v, u32x2& hi, u32x2& lo) {
 #pragma unroll
@@ -611,586 +627,69 @@ __device__ __forceinline__ void split_bf16(const f32x4 v, u32x2& hi, u32x2& lo) 
 #ifndef SEAM_BX3_ABL
 #define SEAM_BX3_ABL 0      // kernel experiments: 1 no global loads, 2 no LDS stores, 4 no split VALU, 8 no barrier, 16 no frag reads
 #endif
+
+// The forms of the tile body: what differs between the two-plane and the three-plane kernel, and nothing else.  Of a block of
+// 64 * NW threads, thread tid = 8 * lrow + lcol fetches weight vectors i = 0 .. BI-1 (16 bytes each) of a chunk: brow() is vector
+// i's byte offset inside the chunk of the packed slab (where it lands in LDS is written out in the body, see there); cut()
+// splits an A vector into the planes' pieces (the two-plane form leaves the third alone); term(t) = (piece of a) * 4 +
+// (piece of b) of the t-th MFMA group of a k-step; VEC_EPI: the tile ends with the 16-byte epilogue when K % 4 == 0.
+struct FormBx3 {
+    static constexpr int PLANES = 2, TERMS = 3;
+    static constexpr bool VEC_EPI = false;
+    template <int BN, int NW> static constexpr int BI = BN / (8 * NW);
+    static __device__ __forceinline__ int chunk_stride(const ConvArgs& p) { return p.slab_bn * CHUNK_BYTES; }
+    static __device__ __forceinline__ const char* w_base(const ConvArgs& p, int n0, int n_in_slab) {
+        return (const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * 4 + (size_t)n_in_slab * CHUNK_BYTES;
+    }
+    // a [BN][32 hi | 32 lo] slab: 8 lanes per row, 8 * NW rows per pass
+    template <int BN, int NW> static __device__ __forceinline__ int brow(const ConvArgs&, int i, int, int lrow, int lcol, int) {
+        return (lrow + 8 * NW * i) * CHUNK_BYTES + lcol * 16;
+    }
+    static __device__ __forceinline__ void cut(const f32x4 v, u32x2& q0, u32x2& q1, u32x2&) { split_bf16(v, q0, q1); }
+    static __device__ __forceinline__ int term(int t) {
+        constexpr int T3[3] = {0 * 4 + 1, 1 * 4 + 0, 0};          // hi*lo, lo*hi, hi*hi
+        return T3[t];
+    }
+};
+
+template <int TERMS_>
+struct FormSx {
+    static_assert(TERMS_ == 6 || TERMS_ == 9, "six or nine piece products");
+    static constexpr int PLANES = 3, TERMS = TERMS_;
+    static constexpr bool VEC_EPI = true;
+    template <int BN, int NW> static constexpr int BI = 3 * (BN * 4) / (64 * NW);      // BN * 4 vectors per weight plane of the tile
+    // one chunk of a slab: three planes of slab_bn 64-byte rows
+    static __device__ __forceinline__ int chunk_stride(const ConvArgs& p) { return p.slab_bn * 192; }
+    static __device__ __forceinline__ const char* w_base(const ConvArgs& p, int n0, int n_in_slab) {
+        return (const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * 6;
+    }
+    // weight vector v = tid + 64 * NW * i of the tile's [plane][BN rows][4 slots]: the plane is a compile-time function of i
+    template <int BN, int NW> static __device__ __forceinline__ int brow(const ConvArgs& p, int i, int tid, int, int, int n_in_slab) {
+        const int pl = (64 * NW * i) / (BN * 4), within = tid + (64 * NW * i) % (BN * 4);
+        return pl * p.slab_bn * 64 + (n_in_slab + (within >> 2)) * 64 + (within & 3) * 16;
+    }
+    static __device__ __forceinline__ void cut(const f32x4 v, u32x2& q0, u32x2& q1, u32x2& q2) { split3_bf16(v, q0, q1, q2); }
+    static __device__ __forceinline__ int term(int t) {
+        // by descending i + j; the six-term form starts at i + j = 2
+        constexpr int T9[9] = {2 * 4 + 2, 2 * 4 + 1, 1 * 4 + 2, 2 * 4 + 0, 1 * 4 + 1, 0 * 4 + 2, 1 * 4 + 0, 0 * 4 + 1, 0};
+        return T9[t + (9 - TERMS)];
+    }
+};
+
+// The tile body is the TEXT of seam_igemm_split_tile.h, placed in both kernels with Form, BM, BN, NW and p in scope.  Not a
+// function template: a forced-inline callee goes through the optimiser on its own before it is inlined (the kernel arguments are
+// then loads through a pointer), and every one of the 13 kernels came out with other code (profiles/igemm_split_fold.txt, 2a).
 template <int BM, int BN, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_igemm_bx3(const ConvArgs p) {
-    constexpr int ES = 4, EPV = 4, BKE = 32;
-    constexpr int WM = BM / (NW / 2), WN = BN / 2;
-    constexpr int MT = WM / 32, NT = WN / 32;
-    constexpr int RP = 8 * NW;
-    constexpr int AI = BM / RP, BI = BN / RP;
-    constexpr int Q = 3 * MT * NT;               // MFMAs per k-step (16 k-values)
-    constexpr int PA = BM * 64 + 64;             // bytes of one A plane (+64: the lo plane starts on the other bank half)
-    constexpr int PB = BN * 64 + 64;
-
-    __shared__ __attribute__((aligned(16))) char As[2][2 * PA];     // [buffer][hi plane | lo plane]
-    __shared__ __attribute__((aligned(16))) char Bs[2][2 * PB];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm0 = (wid >> 1) * WM;
-    const int wn0 = (wid & 1) * WN;
-
-    const int nblk = gridDim.x;
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int q8 = nblk >> 3, rem = nblk & 7;
-    const int tile = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + (b >> 3);
-    const int tm = tile / p.tiles_n;
-    const int tn = tile - tm * p.tiles_n;
-    const int m0 = tm * BM;
-    const int n0 = tn * BN;
-
-    const int nk = p.kred / BKE;
-    const int lcol = tid & 7;
-    const int lrow = tid >> 3;
-    const int HoWo = p.Ho * p.Wo;
-    const int n_first = m0 / HoWo;
-    const size_t img_elems = (size_t)p.H * p.W * p.C;
-    const size_t rem_bytes = ((size_t)(p.N - n_first) * img_elems) * ES;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.x + (size_t)n_first * img_elems * ES), 0,
-        (int)(rem_bytes > kOob ? kOob : (unsigned)rem_bytes), 0x00020000);
-    const int slab_stride = p.slab_bn * CHUNK_BYTES;
-    const int n_in_slab = n0 % p.slab_bn;
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * ES + (size_t)n_in_slab * CHUNK_BYTES), 0,
-        (int)((unsigned)nk * (unsigned)slab_stride), 0x00020000);
-
-    int arow[AI], ahi[AI], awi[AI];
-#pragma unroll
-    for (int i = 0; i < AI; ++i) {
-        const int m = m0 + lrow + RP * i;
-        if (m < p.M) {
-            const int n = m / HoWo;
-            const int rm = m - n * HoWo;
-            const int ho = rm / p.Wo;
-            const int wo = rm - ho * p.Wo;
-            ahi[i] = ho * p.stride - p.pad;
-            awi[i] = wo * p.stride - p.pad;
-            arow[i] = ((((n - n_first) * p.H + ahi[i]) * p.W + awi[i]) * p.C) * ES;
-        } else {
-            ahi[i] = -(1 << 28);
-            awi[i] = 0;
-            arow[i] = 0;
-        }
-    }
-    int brow[BI];
-#pragma unroll
-    for (int i = 0; i < BI; ++i) brow[i] = (lrow + RP * i) * CHUNK_BYTES + lcol * 16;
-
-    int kc, kr, ks, tapoff;
-    {
-        const int kk = lcol * EPV;
-        const int pos = kk / p.C;
-        kc = kk - pos * p.C;
-        kr = pos / p.S;
-        ks = pos - kr * p.S;
-        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
-    }
-    int uq = 0;
-
-    constexpr int D = 2;
-    f32x4 areg[D][AI], breg[D][BI];
-    auto load_a = [&](f32x4 (&ar)[AI], int i) {
-        const bool ok = (unsigned)(ahi[i] + kr) < (unsigned)p.H && (unsigned)(awi[i] + ks) < (unsigned)p.W && kr < p.R;
-        const unsigned off = ok ? (unsigned)(arow[i] + tapoff) : kOob;
-        if (!(SEAM_BX3_ABL & 1)) ar[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0));
-    };
-    auto load_b = [&](f32x4 (&br)[BI], int i) {
-        const int so = uq < nk ? uq * slab_stride : (int)kOob;
-        if (!(SEAM_BX3_ABL & 1)) br[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, brow[i], so, 0));
-    };
-    auto advance_k = [&]() {
-        ++uq;
-        if (p.C >= BKE) {
-            if (++ks == p.S) {
-                ks = 0;
-                kc += BKE;
-                if (kc >= p.C) { kc -= p.C; ++kr; }
-            }
-        } else {
-            kc += BKE;
-            while (kc >= p.C) {
-                kc -= p.C;
-                if (++ks == p.S) { ks = 0; ++kr; }
-            }
-        }
-        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
-    };
-    auto load_chunk = [&](f32x4 (&ar)[AI], f32x4 (&br)[BI]) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) load_a(ar, i);
-#pragma unroll
-        for (int i = 0; i < BI; ++i) load_b(br, i);
-        advance_k();
-    };
-    // LDS addresses of this thread's stores.  A: 4 floats -> 8 B of hi + 8 B of lo at bf16 index 4*lcol of the row;
-    // B: 16 B of the packed row: lcol < 4 -> hi plane slot lcol, else lo plane slot lcol-4.
-    auto store_row = [&](const f32x4 (&ar)[AI], const f32x4 (&br)[BI], int buf, int r) {
-        if (SEAM_BX3_ABL & 2) return;
-        if (r < AI) {
-            const int row = lrow + RP * r;
-            const int off = row * 64 + ((((lcol >> 1) ^ (row >> 2)) & 3) << 4) + (lcol & 1) * 8;
-            u32x2 hi, lo;
-            if (SEAM_BX3_ABL & 4) { hi[0] = __builtin_bit_cast(unsigned, ar[r][0]); hi[1] = __builtin_bit_cast(unsigned, ar[r][1]);
-                                    lo[0] = __builtin_bit_cast(unsigned, ar[r][2]); lo[1] = __builtin_bit_cast(unsigned, ar[r][3]); }
-            else split_bf16(ar[r], hi, lo);
-            *reinterpret_cast<u32x2*>(&As[buf][off]) = hi;
-            *reinterpret_cast<u32x2*>(&As[buf][PA + off]) = lo;
-        } else {
-            const int row = lrow + RP * (r - AI);
-            const int off = (lcol >> 2) * PB + row * 64 + (((lcol ^ (row >> 2)) & 3) << 4);
-            *reinterpret_cast<f32x4*>(&Bs[buf][off]) = br[r - AI];
-        }
-    };
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // fragment addresses: lane reads 16 B (8 bf16 of k) of row (l & 31) at slot 2*step + (l >> 5), swizzled
-    const int arow0 = wm0 + (lane & 31), brow0 = wn0 + (lane & 31);
-    struct Frag { f32x4 ah[MT], al[MT], bh[NT], bl[NT]; };
-    Frag f0, f1;
-    auto read_frags = [&](Frag& f, int buf, int step) {
-        if (SEAM_BX3_ABL & 16) return;
-        const int slot = 2 * step + (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int row = arow0 + i * 32;
-            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
-            f.ah[i] = *reinterpret_cast<const f32x4*>(&As[buf][off]);
-            f.al[i] = *reinterpret_cast<const f32x4*>(&As[buf][PA + off]);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int row = brow0 + j * 32;
-            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
-            f.bh[j] = *reinterpret_cast<const f32x4*>(&Bs[buf][off]);
-            f.bl[j] = *reinterpret_cast<const f32x4*>(&Bs[buf][PB + off]);
-        }
-    };
-    auto mf = [&](const Frag& f, int idx) {       // idx in [0, Q): term-major so the small terms of a tile go in first
-        const int term = idx / (MT * NT), i = (idx / NT) % MT, j = idx % NT;
-        const f32x4 a = term == 1 ? f.al[i] : f.ah[i];
-        const f32x4 bq = term == 0 ? f.bl[j] : f.bh[j];          // 0: hi*lo, 1: lo*hi, 2: hi*hi
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq),
-                                                            acc[i][j], 0, 0, 0);
-    };
-
-    auto chunk = [&](int buf, f32x4 (&lda)[AI], f32x4 (&ldb)[BI], const f32x4 (&sta)[AI], const f32x4 (&stb)[BI]) {
-        // k-step 0 (+ the gathers and weight rows of chunk t+D)
-        read_frags(f1, buf, 1);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            mf(f0, q);
-#pragma unroll
-            for (int i = 0; i < AI + BI; ++i)
-                if ((i * Q) / (AI + BI) == q) {
-                    if (i < AI) load_a(lda, i);
-                    else load_b(ldb, i - AI);
-                }
-            if (q == Q - 1) advance_k();
-        }
-        // k-step 1: chunk t+1 goes to the other LDS buffer behind the first two thirds of the MFMAs, then the barrier
-        // and the first fragments of the next chunk; the last third covers their latency
-        constexpr int QS = (2 * Q) / 3;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            mf(f1, q);
-#pragma unroll
-            for (int r = 0; r < AI + BI; ++r)
-                if ((r * QS) / (AI + BI) == q) store_row(sta, stb, buf ^ 1, r);
-            if (q == QS - 1) {
-                if (!(SEAM_BX3_ABL & 8)) __syncthreads();
-                read_frags(f0, buf ^ 1, 0);
-            }
-        }
-    };
-
-    load_chunk(areg[0], breg[0]);
-#pragma unroll
-    for (int r = 0; r < AI + BI; ++r) store_row(areg[0], breg[0], 0, r);
-    load_chunk(areg[1], breg[1]);
-    __syncthreads();
-    read_frags(f0, 0, 0);
-
-    for (int t = 0; t < nk; t += 2) {
-        chunk(0, areg[0], breg[0], areg[1], breg[1]);
-        if (t + 1 < nk) chunk(1, areg[1], breg[1], areg[0], breg[0]);
-    }
-
-    // ---- epilogue (the fp32 kernel's) ---------------------------------------------------------
-    const size_t tile_off = (size_t)m0 * p.K;
-    const unsigned rows_here = (unsigned)min(BM, p.M - m0);
-    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((char*)p.y + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)(p.res ? p.res : p.y) + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int n = n0 + wn0 + j * 32 + (lane & 31);
-        const bool nok = n < p.K;
-        const float sc = (p.scale && nok) ? p.scale[n] : 1.f;
-        const float sh = (p.shift && nok) ? p.shift[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            unsigned eo[16];
-            float rv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                eo[r] = (unsigned)(row * p.K + n);
-            }
-            if (p.res) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, nok ? eo[r] * 4u : kOob, 0, 0));
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = acc[i][j][r] * sc + sh;
-                if (p.res) v = p.relu == 2 ? (rv[r] > 0.f ? v : 0.f) : v + rv[r];
-                if (p.relu == 1) v = fmaxf(v, 0.f);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rsrc, nok ? eo[r] * 4u : kOob, 0, 0);
-            }
-        }
-    }
+    using Form = FormBx3;
+#include "seam_igemm_split_tile.h"
 }
 
-// =====================================================================================================================
-// Three-plane split ("sx"): the fp32 product itself on the bf16 matrix pipe.
-//   a = a0 + a1 + a2, three bf16 pieces cut by TRUNCATION: a0 = the top 16 bits of a, a1 = the top 16 bits of a - a0,
-//   a2 = a - a0 - a1.  Both subtractions are exact in fp32 (the remainders have <= 16 and <= 8 significand bits), so the
-//   pieces sum back to a exactly; truncation never rounds up, so a finite a near FLT_MAX has finite pieces.  Every piece
-//   product ai*bj has a 16-bit significand: exact in the fp32 accumulator.
-//   TERMS = 6 keeps i + j <= 2: what is dropped (a1b2 + a2b1 + a2b2) is < 2^-22 |ab|, one fp32 rounding of the product.
-//   TERMS = 9 keeps all: the exact fp32 product; only the order of the fp32 additions differs from the fma chain.
-//   Within a k-step the terms are issued smallest first (i + j descending), so the low-order terms meet before a0b0.
-//   Denormals / tiny inputs: the pieces of |a| < 2^-110 reach below the bf16 denormal step 2^-133 and lose those bits
-//   (absolute error < 2^-133 |b|, and the matrix unit may flush denormal pieces): invisible at fp32 scale.  Inf / NaN
-//   inputs: a - a0 = NaN, the outputs that read them are NaN (the fp32 kernel gives Inf for Inf inputs).
-// Everything else is conv_igemm_bx3's: the fp32 gather, the chunk walk, the register ring, the XOR-swizzled 64-byte LDS
-// rows (three planes per operand: 96 KiB at 128 x 128, one block per CU), plus the fp32 kernel's 16-byte epilogue.
-// Weights (seam_pack_conv_weight_sx): [n_slab][chunk][plane 0..2][slab_bn rows][32 bf16] -- 192 B per row-chunk.
-// The split itself (top16, split3_bf16) lives in seam_split.h, shared with conv1x1_sxpc (seam_pwsx.hip).
 template <int BM, int BN, int TERMS>
 __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 1 : 2) void conv_igemm_sx(const ConvArgs p) {
-    static_assert(TERMS == 6 || TERMS == 9, "six or nine piece products");
-    constexpr int NW = 4, ES = 4, EPV = 4, BKE = 32;
-    constexpr int WM = BM / 2, WN = BN / 2;
-    constexpr int MT = WM / 32, NT = WN / 32;
-    constexpr int RP = 8 * NW;
-    constexpr int AI = BM / RP;
-    constexpr int VPP = BN * 4;                  // 16-byte vectors of one weight plane of the tile
-    constexpr int BI = 3 * VPP / 256;            // weight vectors per thread per chunk
-    constexpr int Q = TERMS * MT * NT;           // MFMAs per k-step (16 k-values)
-    constexpr int PA = BM * 64 + 64;             // bytes of one A plane
-    constexpr int PB = BN * 64 + 64;
-
-    __shared__ __attribute__((aligned(16))) char As[2][3 * PA];     // [buffer][plane 0 | 1 | 2]
-    __shared__ __attribute__((aligned(16))) char Bs[2][3 * PB];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm0 = (wid >> 1) * WM;
-    const int wn0 = (wid & 1) * WN;
-
-    const int nblk = gridDim.x;
-    const int b = blockIdx.x;
-    const int xcd = b & 7;
-    const int q8 = nblk >> 3, rem = nblk & 7;
-    const int tile = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + (b >> 3);
-    const int tm = tile / p.tiles_n;
-    const int tn = tile - tm * p.tiles_n;
-    const int m0 = tm * BM;
-    const int n0 = tn * BN;
-
-    const int nk = p.kred / BKE;
-    const int lcol = tid & 7;
-    const int lrow = tid >> 3;
-    const int HoWo = p.Ho * p.Wo;
-    const int n_first = m0 / HoWo;
-    const size_t img_elems = (size_t)p.H * p.W * p.C;
-    const size_t rem_bytes = ((size_t)(p.N - n_first) * img_elems) * ES;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.x + (size_t)n_first * img_elems * ES), 0,
-        (int)(rem_bytes > kOob ? kOob : (unsigned)rem_bytes), 0x00020000);
-    const int slab_stride = p.slab_bn * 192;                 // one chunk of a slab: three planes of slab_bn 64-byte rows
-    const int n_in_slab = n0 % p.slab_bn;
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.w + (size_t)(n0 - n_in_slab) * p.kred * 6), 0,
-        (int)((unsigned)nk * (unsigned)slab_stride), 0x00020000);
-
-    int arow[AI], ahi[AI], awi[AI];
-#pragma unroll
-    for (int i = 0; i < AI; ++i) {
-        const int m = m0 + lrow + RP * i;
-        if (m < p.M) {
-            const int n = m / HoWo;
-            const int rm = m - n * HoWo;
-            const int ho = rm / p.Wo;
-            const int wo = rm - ho * p.Wo;
-            ahi[i] = ho * p.stride - p.pad;
-            awi[i] = wo * p.stride - p.pad;
-            arow[i] = ((((n - n_first) * p.H + ahi[i]) * p.W + awi[i]) * p.C) * ES;
-        } else {
-            ahi[i] = -(1 << 28);
-            awi[i] = 0;
-            arow[i] = 0;
-        }
-    }
-    // weight vector v = tid + 256 i of the tile's [plane][BN rows][4 slots]: the plane is a compile-time function of i
-    int brow[BI];
-#pragma unroll
-    for (int i = 0; i < BI; ++i) {
-        const int pl = (256 * i) / VPP, within = tid + (256 * i) % VPP;
-        brow[i] = pl * p.slab_bn * 64 + (n_in_slab + (within >> 2)) * 64 + (within & 3) * 16;
-    }
-
-    int kc, kr, ks, tapoff;
-    {
-        const int kk = lcol * EPV;
-        const int pos = kk / p.C;
-        kc = kk - pos * p.C;
-        kr = pos / p.S;
-        ks = pos - kr * p.S;
-        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
-    }
-    int uq = 0;
-
-    constexpr int D = 2;
-    f32x4 areg[D][AI], breg[D][BI];
-    auto load_a = [&](f32x4 (&ar)[AI], int i) {
-        const bool ok = (unsigned)(ahi[i] + kr) < (unsigned)p.H && (unsigned)(awi[i] + ks) < (unsigned)p.W && kr < p.R;
-        const unsigned off = ok ? (unsigned)(arow[i] + tapoff) : kOob;
-        if (!(SEAM_BX3_ABL & 1)) ar[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0));
-    };
-    auto load_b = [&](f32x4 (&br)[BI], int i) {
-        const int so = uq < nk ? uq * slab_stride : (int)kOob;
-        if (!(SEAM_BX3_ABL & 1)) br[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, brow[i], so, 0));
-    };
-    auto advance_k = [&]() {
-        ++uq;
-        if (p.C >= BKE) {
-            if (++ks == p.S) {
-                ks = 0;
-                kc += BKE;
-                if (kc >= p.C) { kc -= p.C; ++kr; }
-            }
-        } else {
-            kc += BKE;
-            while (kc >= p.C) {
-                kc -= p.C;
-                if (++ks == p.S) { ks = 0; ++kr; }
-            }
-        }
-        tapoff = ((kr * p.W + ks) * p.C + kc) * ES;
-    };
-    auto load_chunk = [&](f32x4 (&ar)[AI], f32x4 (&br)[BI]) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) load_a(ar, i);
-#pragma unroll
-        for (int i = 0; i < BI; ++i) load_b(br, i);
-        advance_k();
-    };
-    // A: 4 floats -> 8 B in each of the three planes at bf16 index 4*lcol of the row; B: 16 B of one plane's row
-    auto store_row = [&](const f32x4 (&ar)[AI], const f32x4 (&br)[BI], int buf, int r) {
-        if (SEAM_BX3_ABL & 2) return;
-        if (r < AI) {
-            const int row = lrow + RP * r;
-            const int off = row * 64 + ((((lcol >> 1) ^ (row >> 2)) & 3) << 4) + (lcol & 1) * 8;
-            u32x2 q0, q1, q2;
-            if (SEAM_BX3_ABL & 4) { q0[0] = __builtin_bit_cast(unsigned, ar[r][0]); q0[1] = __builtin_bit_cast(unsigned, ar[r][1]);
-                                    q1[0] = __builtin_bit_cast(unsigned, ar[r][2]); q1[1] = __builtin_bit_cast(unsigned, ar[r][3]); q2 = q0; }
-            else split3_bf16(ar[r], q0, q1, q2);
-            *reinterpret_cast<u32x2*>(&As[buf][off]) = q0;
-            *reinterpret_cast<u32x2*>(&As[buf][PA + off]) = q1;
-            *reinterpret_cast<u32x2*>(&As[buf][2 * PA + off]) = q2;
-        } else {
-            const int i = r - AI;
-            const int pl = (256 * i) / VPP, within = tid + (256 * i) % VPP;
-            const int row = within >> 2;
-            *reinterpret_cast<f32x4*>(&Bs[buf][pl * PB + row * 64 + ((((within & 3) ^ (row >> 2)) & 3) << 4)]) = br[i];
-        }
-    };
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // fragment addresses: lane reads 16 B (8 bf16 of k) of row (l & 31) at slot 2*step + (l >> 5), swizzled
-    const int arow0 = wm0 + (lane & 31), brow0 = wn0 + (lane & 31);
-    struct Frag { f32x4 a[3][MT], b[3][NT]; };
-    Frag f0, f1;
-    auto read_frags = [&](Frag& f, int buf, int step) {
-        if (SEAM_BX3_ABL & 16) return;
-        const int slot = 2 * step + (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int row = arow0 + i * 32;
-            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) f.a[pl][i] = *reinterpret_cast<const f32x4*>(&As[buf][pl * PA + off]);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int row = brow0 + j * 32;
-            const int off = row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) f.b[pl][j] = *reinterpret_cast<const f32x4*>(&Bs[buf][pl * PB + off]);
-        }
-    };
-    auto mf = [&](const Frag& f, int idx) {       // idx in [0, Q): term-major, the smallest terms of a tile first
-        // (piece of a) * 4 + (piece of b), by descending i + j; the six-term form starts at i + j = 2
-        constexpr int T9[9] = {2 * 4 + 2, 2 * 4 + 1, 1 * 4 + 2, 2 * 4 + 0, 1 * 4 + 1, 0 * 4 + 2, 1 * 4 + 0, 0 * 4 + 1, 0};
-        const int term = T9[idx / (MT * NT) + (9 - TERMS)], i = (idx / NT) % MT, j = idx % NT;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.a[term >> 2][i]),
-                                                            __builtin_bit_cast(bf16x8, f.b[term & 3][j]), acc[i][j], 0, 0, 0);
-    };
-
-    auto chunk = [&](int buf, f32x4 (&lda)[AI], f32x4 (&ldb)[BI], const f32x4 (&sta)[AI], const f32x4 (&stb)[BI]) {
-        // k-step 0 (+ the gathers and weight rows of chunk t+D)
-        read_frags(f1, buf, 1);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            mf(f0, q);
-#pragma unroll
-            for (int i = 0; i < AI + BI; ++i)
-                if ((i * Q) / (AI + BI) == q) {
-                    if (i < AI) load_a(lda, i);
-                    else load_b(ldb, i - AI);
-                }
-            if (q == Q - 1) advance_k();
-        }
-        // k-step 1: chunk t+1 goes to the other LDS buffer behind the first two thirds of the MFMAs, then the barrier
-        // and the first fragments of the next chunk; the last third covers their latency
-        constexpr int QS = (2 * Q) / 3;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            mf(f1, q);
-#pragma unroll
-            for (int r = 0; r < AI + BI; ++r)
-                if ((r * QS) / (AI + BI) == q) store_row(sta, stb, buf ^ 1, r);
-            if (q == QS - 1) {
-                if (!(SEAM_BX3_ABL & 8)) __syncthreads();
-                read_frags(f0, buf ^ 1, 0);
-            }
-        }
-    };
-
-    load_chunk(areg[0], breg[0]);
-#pragma unroll
-    for (int r = 0; r < AI + BI; ++r) store_row(areg[0], breg[0], 0, r);
-    load_chunk(areg[1], breg[1]);
-    __syncthreads();
-    read_frags(f0, 0, 0);
-
-    for (int t = 0; t < nk; t += 2) {
-        chunk(0, areg[0], breg[0], areg[1], breg[1]);
-        if (t + 1 < nk) chunk(1, areg[1], breg[1], areg[0], breg[0]);
-    }
-    __syncthreads();                 // every wave is done with the LDS buffers: the epilogue's transpose reuses them
-
-    // ---- epilogue (the fp32 kernel's: 16-byte form through a wave-private LDS transpose when K % 4 == 0) ----------
-    const size_t tile_off = (size_t)m0 * p.K;
-    const unsigned rows_here = (unsigned)min(BM, p.M - m0);
-    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((char*)p.y + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)(p.res ? p.res : p.y) + tile_off * 4), 0, (int)(rows_here * (unsigned)p.K * 4), 0x00020000);
-    if ((p.K & 3) == 0) {
-        constexpr int EW = WN + 4;                 // padded row, floats
-        constexpr int LPR = WN / 4;                // lanes per row
-        constexpr int RPI = 64 / LPR;              // rows per 16-byte pass of the wave
-        constexpr int NP = 32 / RPI;               // passes per 32-row MFMA tile
-        static_assert(4 * 32 * EW * 4 <= 2 * 3 * (BM >= BN ? PA : PB), "the transpose fits the operand's LDS");
-        float* eb = reinterpret_cast<float*>(BM >= BN ? &As[0][0] : &Bs[0][0]) + wid * 32 * EW;
-        const int er = lane / LPR, ec = (lane % LPR) * 4;
-        const int n = n0 + wn0 + ec;
-        const bool nok = n < p.K;
-        f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-        if (p.scale && nok) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
-        if (p.shift && nok) sh = *reinterpret_cast<const f32x4*>(p.shift + n);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            unsigned eo[NP];
-            f32x4 rv[NP];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int row = wm0 + i * 32 + k * RPI + er;
-                eo[k] = nok ? (unsigned)(row * p.K + n) * 4u : kOob;
-            }
-            if (p.res) {
-#pragma unroll
-                for (int k = 0; k < NP; ++k)
-                    rv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, eo[k], 0, 0));
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    eb[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * EW + j * 32 + (lane & 31)] = acc[i][j][r];
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                f32x4 v = *reinterpret_cast<const f32x4*>(&eb[(k * RPI + er) * EW + ec]) * sc + sh;
-                if (p.res) {
-                    if (p.relu == 2) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = rv[k][e] > 0.f ? v[e] : 0.f;
-                    } else {
-                        v += rv[k];
-                    }
-                }
-                if (p.relu == 1) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, eo[k], 0, 0);
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int n = n0 + wn0 + j * 32 + (lane & 31);
-        const bool nok = n < p.K;
-        const float sc = (p.scale && nok) ? p.scale[n] : 1.f;
-        const float sh = (p.shift && nok) ? p.shift[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            unsigned eo[16];
-            float rv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                eo[r] = (unsigned)(row * p.K + n);
-            }
-            if (p.res) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, nok ? eo[r] * 4u : kOob, 0, 0));
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = acc[i][j][r] * sc + sh;
-                if (p.res) v = p.relu == 2 ? (rv[r] > 0.f ? v : 0.f) : v + rv[r];
-                if (p.relu == 1) v = fmaxf(v, 0.f);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rsrc, nok ? eo[r] * 4u : kOob, 0, 0);
-            }
-        }
-    }
+    using Form = FormSx<TERMS>;
+    constexpr int NW = 4;
+#include "seam_igemm_split_tile.h"
 }
 
 // fp32-packed weights [slab][chunk][row][32 floats] -> [slab][chunk][plane][row][32 bf16], the truncation split of split3_bf16
@@ -1301,15 +800,16 @@ inline void set_row_split(ConvArgs& a) {
                   seam_fastdiv::exact((unsigned long long)a.Wo, howo)) ? 1 : 0;
 }
 
+// What every launcher of the family starts with: the argument checks (T = the element type of x) and the pointer and geometry fields
+// of ConvArgs, with the second source and the coarse residual off.  y_f32, vec_epi and epi_prio are the caller's.
 template <typename T>
-int conv2d(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
-           int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, int y_f32, void* stream,
-           int rH = 0, int rW = 0, const DualSrc* dual = nullptr, int ho_crop = 0, int wo_crop = 0) {
+int fill_conv_args(ConvArgs& a, const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual,
+                   void* y, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, int ho_crop = 0,
+                   int wo_crop = 0) {
     constexpr int BKE = CHUNK_BYTES / (int)sizeof(T), EPV = 16 / (int)sizeof(T);
     if ((C % EPV) || (C >= BKE && C % BKE) || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
     // a kernel larger than the padded input has no output (under a stride the division below would round the negative extent to 0)
     if (stride < 1 || R < 1 || S < 1 || H + 2 * pad < R || W + 2 * pad < S) return (int)hipErrorInvalidValue;
-    ConvArgs a;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
     a.N = N; a.H = H; a.W = W; a.C = C;
     a.Ho = (H + 2 * pad - R) / stride + 1;
@@ -1322,13 +822,33 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
     a.kred = kred_of<T>(C, R, S);
     a.M = N * a.Ho * a.Wo;
     a.relu = relu;
+    a.rH = a.rW = 0;
+    a.x2 = nullptr; a.H2 = a.W2 = a.C2 = a.stride2 = 0;
+    set_row_split(a);
+    return a.Ho <= 0 || a.Wo <= 0 ? (int)hipErrorInvalidValue : 0;
+}
+
+// ... and ends with: the slab height of the pack, the tile choose_tile() picks for `prec`, and the tile counts
+inline void set_conv_tile(ConvArgs& a, int prec, int taps, int& bm, int& bn) {
+    const int rows = ((a.K + 63) / 64) * 64;
+    a.slab_bn = rows % 128 == 0 ? 128 : 64;
+    choose_tile(prec, a.M, a.K, bm, bn, taps);
+    a.tiles_m = (a.M + bm - 1) / bm;
+    a.tiles_n = rows / bn;
+}
+
+template <typename T>
+int conv2d(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
+           int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, int y_f32, void* stream,
+           int rH = 0, int rW = 0, const DualSrc* dual = nullptr, int ho_crop = 0, int wo_crop = 0) {
+    constexpr int BKE = CHUNK_BYTES / (int)sizeof(T);
+    ConvArgs a;
+    if (const int rc = fill_conv_args<T>(a, x, w_packed, scale, shift, residual, y, N, H, W, C, K, R, S, stride, pad, relu, ho_crop, wo_crop))
+        return rc;
     a.y_f32 = y_f32;
     a.vec_epi = seam_opt::get(seam_opt::F16_VEC_EPILOGUE);
     a.epi_prio = seam_opt::get(seam_opt::EPI_PRIO);
-
     a.rH = rH; a.rW = rW;
-    a.x2 = nullptr; a.H2 = a.W2 = a.C2 = a.stride2 = 0;
-    set_row_split(a);
     if (dual) {
         if (R != 1 || S != 1 || stride != 1 || pad != 0 || (C % BKE) || (dual->C2 % BKE) || dual->stride2 < 1 ||
             (a.Ho - 1) * dual->stride2 >= dual->H2 || (a.Wo - 1) * dual->stride2 >= dual->W2 || !dual->x2)
@@ -1336,14 +856,9 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
         a.x2 = dual->x2; a.H2 = dual->H2; a.W2 = dual->W2; a.C2 = dual->C2; a.stride2 = dual->stride2;
         a.kred = C + dual->C2;
     }
-    if (a.Ho <= 0 || a.Wo <= 0) return (int)hipErrorInvalidValue;
     if (rH > 0 && (sizeof(T) != 4 || (K & 3) || rW <= 0 || !residual || relu == 2)) return (int)hipErrorInvalidValue;
-    const int rows = ((K + 63) / 64) * 64;
-    a.slab_bn = rows % 128 == 0 ? 128 : 64;
     int best_bm, best_bn;
-    choose_tile(sizeof(T) == 2 ? P_F16 : P_F32, a.M, K, best_bm, best_bn, R * S);
-    a.tiles_m = (a.M + best_bm - 1) / best_bm;
-    a.tiles_n = rows / best_bn;
+    set_conv_tile(a, sizeof(T) == 2 ? P_F16 : P_F32, R * S, best_bm, best_bn);
     // persistent blocks: one per resident slot (256 CUs x 2 blocks of 4 waves, or x 1 block of 8 waves); a multiple of 8 so
     // that a block's tiles stay on its XCD
     const int slots4 = 512;
@@ -1379,34 +894,19 @@ int conv2d(const void* x, const void* w_packed, const float* scale, const float*
 // terms: 3 = conv_igemm_bx3 (two planes), 6 / 9 = conv_igemm_sx (three planes)
 int conv2d_bx3(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual, void* y,
                int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int relu, void* stream, int terms = 3) {
-    if ((C % 4) || (C >= 32 && C % 32) || N <= 0 || K <= 0) return (int)hipErrorInvalidValue;
-    if (stride < 1 || R < 1 || S < 1 || H + 2 * pad < R || W + 2 * pad < S) return (int)hipErrorInvalidValue;
     ConvArgs a;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.C = C;
-    a.Ho = (H + 2 * pad - R) / stride + 1;
-    a.Wo = (W + 2 * pad - S) / stride + 1;
-    a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-    a.kred = kred_of<float>(C, R, S);
-    a.M = N * a.Ho * a.Wo;
-    a.relu = relu;
+    if (const int rc = fill_conv_args<float>(a, x, w_packed, scale, shift, residual, y, N, H, W, C, K, R, S, stride, pad, relu)) return rc;
     a.y_f32 = 1;
     a.vec_epi = 0;
     a.epi_prio = 0;
-    a.rH = 0; a.rW = 0;
-    a.x2 = nullptr; a.H2 = a.W2 = a.C2 = a.stride2 = 0;
-    set_row_split(a);
-    if (a.Ho <= 0 || a.Wo <= 0) return (int)hipErrorInvalidValue;
-    const int rows = ((K + 63) / 64) * 64;
-    a.slab_bn = rows % 128 == 0 ? 128 : 64;
     int best_bm, best_bn;
-    choose_tile(terms == 3 ? P_BX3 : P_SX, a.M, K, best_bm, best_bn);
-    a.tiles_m = (a.M + best_bm - 1) / best_bm;
-    a.tiles_n = rows / best_bn;
+    set_conv_tile(a, terms == 3 ? P_BX3 : P_SX, 1, best_bm, best_bn);
+    if (terms != 3 && terms != 6 && terms != 9) return (int)hipErrorInvalidValue;
     const dim3 grid(a.tiles_m * a.tiles_n);
     hipStream_t st = (hipStream_t)stream;
+    // (the kernels are named in this order on purpose: it is the order in which they are emitted, which the block labels of the
+    //  assembly carry -- tools/isa_same.py against an earlier commit compares them too)
     if (terms != 3) {
-        if (terms != 6 && terms != 9) return (int)hipErrorInvalidValue;
 #define SEAM_SX_LAUNCH(BM_, BN_)                                                                          \
         do {                                                                                              \
             if (terms == 6) hipLaunchKernelGGL((conv_igemm_sx<BM_, BN_, 6>), grid, dim3(256), 0, st, a);  \
