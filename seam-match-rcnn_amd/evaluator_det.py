@@ -204,7 +204,7 @@ class DetectionEvaluator:
         truths -- in the order of ``gt["images"]``; a result for an unknown image id raises ValueError.  Boxes: ``bbIou`` on the
         stored xywh values, detection area ``w*h``.  Masks: the detections' RLEs become bitmaps straight from their run lists,
         ground-truth polygons are rasterised (``mask_utils.masks_from_annotations``) and bit-packed by the encoder's values
-        stage, and one pair-intersection launch serves as many images as ``ops.RLE_BITS_BUDGET_BYTES`` holds (one host copy
+        stage, and one pair-intersection launch serves as many images as ``ops_masks.RLE_BITS_BUDGET_BYTES`` holds (one host copy
         each); the detection area is the mask's popcount.  No model and no dense detection mask is involved."""
         from . import mask_utils as M
         gt, results = _load_json(gt), _load_json(results)

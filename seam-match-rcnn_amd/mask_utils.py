@@ -27,7 +27,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ops_masks
 
 
 def rle_from_string(s) -> list:
@@ -388,12 +388,12 @@ def frPyObjects(pyobj, h, w):
 
 def rle_inter_tables(dt_counts: Sequence, gt_counts: Sequence, size):
     """Detections and ground truths of one ``size`` as counts arrays -> (inter int64 [D,G], det_area int64 [D], gt_area int64 [G]):
-    bitmaps from the run lists and pair-wise popcounts, the detections in chunks of ``ops.RLE_BITS_BUDGET_BYTES`` (every chunk
+    bitmaps from the run lists and pair-wise popcounts, the detections in chunks of ``ops_masks.RLE_BITS_BUDGET_BYTES`` (every chunk
     carries the ground truths), one host copy per chunk."""
     nd, ng = len(dt_counts), len(gt_counts)
     per = 4 * ops.rle_bits_cells([size])[0]
     inter, d_area, g_area = np.zeros((nd, ng), np.int64), np.zeros(nd, np.int64), np.zeros(ng, np.int64)
-    budget = max(ops.RLE_BITS_BUDGET_BYTES - per * ng, per)
+    budget = max(ops_masks.RLE_BITS_BUDGET_BYTES - per * ng, per)
     for lo, hi in ops.budget_chunks([per] * nd, budget) or [(0, 0)]:
         k = hi - lo
         ws, lay = ops.rle_bits(list(dt_counts[lo:hi]) + list(gt_counts), [size] * (k + ng))

@@ -2,7 +2,7 @@
 the kernels, built from its tensors -- and reads it through ``packed()``.  The cache key is a pair ``(tensors, switches)``:
   tensors    one ``(data_ptr, _version)`` per entry of ``_pack_tensors()``: a tensor replaced, moved or edited in place misses
   switches   ``_pack_switches()``: everything else ``_build_packs`` reads (the compute dtype, split twins, pack-time knobs)
-``ops.PackPlan`` reads the two parts by name.  The state is ``_pk`` / ``_pk_key`` on the module itself (``module._pk = None`` drops
+``pack_plan.PackPlan`` reads the two parts by name.  The state is ``_pk`` / ``_pk_key`` on the module itself (``module._pk = None`` drops
 the packs), so a copied or unpickled module misses and rebuilds against its own tensors."""
 from __future__ import annotations
 

@@ -3,7 +3,7 @@ stuffs/engine.py:62-64).
 
 ``step()`` is one launch of ``seam_sgd_step_f32`` over every parameter that has a gradient (csrc/seam_optim.hip: torch's arithmetic,
 each multiply and add rounded on its own), then one version bump per updated parameter (every pack cache keyed on versions
-invalidates by its usual rule) and, when ``model`` is given, ``ops.PackPlan.refresh``: the cached packs of the ResNet body, the FPN
+invalidates by its usual rule) and, when ``model`` is given, ``pack_plan.PackPlan.refresh``: the cached packs of the ResNet body, the FPN
 and the RPN head are rewritten in place in one more launch, so the next forward finds them valid.  Everything else that caches a
 pack (the eval-mode heads, the match heads) repacks lazily as before.
 
@@ -23,7 +23,7 @@ import math
 import torch
 from torch.optim.optimizer import Optimizer
 
-from . import _native, ops
+from . import _native, ops, pack_plan
 
 MAX_GROUPS = _native.SGD_MAX_SLOTS // 2      # a group takes two kernel slots: buffers that exist, buffers created this step
 
@@ -77,7 +77,7 @@ class SGD(Optimizer):
                         maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
         super().__init__(params, defaults)
         self.refresh_packs = bool(refresh_packs)
-        self.plan = ops.PackPlan(model) if model is not None else None
+        self.plan = pack_plan.PackPlan(model) if model is not None else None
         if self.plan is not None and self.refresh_packs:
             with torch.no_grad():
                 self.plan.build()

@@ -76,13 +76,13 @@ def test_scatter_and_merge_references_equal_autograd():
 
 
 def test_new_entry_points_are_bound_and_wrapped():
-    from seam_match_rcnn_amd import _native, ops
+    from seam_match_rcnn_amd import _native, ops, ops_train
     for name in ("seam_roi_align_bwd_workspace_bytes", "seam_roi_align_bwd_f32", "seam_rpn_scatter_patches_f32",
                  "seam_upsample_add_bwd_f32", "seam_subsample_add_bwd_f32"):
         assert name in _native.SIGNATURES, name
     for name in ("roi_align_bwd", "rpn_scatter_patches", "upsample_add_bwd", "subsample_add_bwd", "conv_wgrad_chunked"):
         assert callable(getattr(ops, name)), name
-    assert isinstance(ops.WGRAD_MAX_OPERAND_BYTES, int) and ops.WGRAD_MAX_OPERAND_BYTES < 2 ** 31
+    assert isinstance(ops_train.WGRAD_MAX_OPERAND_BYTES, int) and ops_train.WGRAD_MAX_OPERAND_BYTES < 2 ** 31
     from seam_match_rcnn_amd import autograd
     for name in ("RoIAlignFunction", "RPNPatchesFunction", "FPNFunction"):
         assert issubclass(getattr(autograd, name), torch.autograd.Function), name

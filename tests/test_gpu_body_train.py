@@ -95,16 +95,16 @@ def test_conv3x3s2_dgrad_vs_float64(shape, with_scale, with_mask, selector):
 
 
 def test_conv3x3s2_dgrad_splits_a_large_batch_over_images(monkeypatch):
-    from seam_match_rcnn_amd import ops
+    from seam_match_rcnn_amd import ops, ops_train
     shape = SHAPES[0]
     n, h, w, c, k = shape
     cs = case(shape)
     pk = ops.pack_conv3x3s2_dgrad(cs["w"].to(DEV), cs["scale"].to(DEV))
     whole = ops.conv3x3s2_dgrad(cs["dy"].to(DEV), pk, (h, w), mask=cs["mask"].to(DEV))
-    monkeypatch.setattr(ops, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4)                  # one image per launch
+    monkeypatch.setattr(ops_train, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4)                  # one image per launch
     parts = ops.conv3x3s2_dgrad(cs["dy"].to(DEV), pk, (h, w), mask=cs["mask"].to(DEV))
     assert torch.equal(whole, parts)
-    monkeypatch.setattr(ops, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4 - 1)
+    monkeypatch.setattr(ops_train, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4 - 1)
     with pytest.raises(ValueError):
         ops.conv3x3s2_dgrad(cs["dy"].to(DEV), pk, (h, w))
 

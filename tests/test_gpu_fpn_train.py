@@ -269,22 +269,22 @@ def test_subsample_add_bwd_is_exact():
 
 # ------------------------------------------------------------------------------ chunked weight gradient
 def test_chunked_conv_wgrad_splits_and_is_reproducible():
-    from seam_match_rcnn_amd import ops
+    from seam_match_rcnn_amd import ops, ops_train
     x, dy = randn(1, 5, 9, 11, 32).to(DEV), randn(2, 5, 9, 11, 64).to(DEV)
     whole = ops.conv_wgrad(x, dy, 3, 3, 1, 1)
     assert torch.equal(ops.conv_wgrad_chunked(x, dy, 3, 3, 1, 1), whole)           # within the limit: the plain call
     calls, plain = [], ops.conv_wgrad
-    old = ops.WGRAD_MAX_OPERAND_BYTES
+    old = ops_train.WGRAD_MAX_OPERAND_BYTES
     try:
-        ops.WGRAD_MAX_OPERAND_BYTES = 2 * dy[0].numel() * 4 + 100                  # two images per chunk: 2 + 2 + 1
-        ops.conv_wgrad = lambda a, b, *r: (calls.append(a.shape[0]), plain(a, b, *r))[1]
+        ops_train.WGRAD_MAX_OPERAND_BYTES = 2 * dy[0].numel() * 4 + 100                  # two images per chunk: 2 + 2 + 1
+        ops_train.conv_wgrad = lambda a, b, *r: (calls.append(a.shape[0]), plain(a, b, *r))[1]
         one = ops.conv_wgrad_chunked(x, dy, 3, 3, 1, 1)
         two = ops.conv_wgrad_chunked(x, dy, 3, 3, 1, 1)
-        ops.WGRAD_MAX_OPERAND_BYTES = dy[0].numel() * 4 - 4
+        ops_train.WGRAD_MAX_OPERAND_BYTES = dy[0].numel() * 4 - 4
         with pytest.raises(ValueError):
             ops.conv_wgrad_chunked(x, dy, 3, 3, 1, 1)
     finally:
-        ops.WGRAD_MAX_OPERAND_BYTES, ops.conv_wgrad = old, plain
+        ops_train.WGRAD_MAX_OPERAND_BYTES, ops_train.conv_wgrad = old, plain
     assert calls == [2, 2, 1, 2, 2, 1]
     assert torch.equal(one, two)
     FR.wgrad_close(one, whole)

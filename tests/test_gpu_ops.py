@@ -395,6 +395,7 @@ def test_nlb_attnpool_mfma_vs_valu_and_oracle(ops):
     256-vectors) against the VALU kernel and the oracle: every row-tile boundary (1 ... 96 rows), both memory layouts
     (sequence-major and the reference's time-major x3_1_seq), z / attention outputs, use_nlb = 0 / 1 / 2."""
     d = dev()
+    from seam_match_rcnn_amd import ops_heads
     from seam_match_rcnn_amd.models.match_head import pack_nlb_from_state
     p = to_torch(synth.temporal_aggregator_state(12))
     pk = pack_nlb_from_state({k: v.to(d) for k, v in p.items()})
@@ -406,11 +407,11 @@ def test_nlb_attnpool_mfma_vs_valu_and_oracle(ops):
     for use in (1, 2, 0):
         res = {}
         for flag in (True, False):
-            ops.NLB_MFMA = flag
+            ops_heads.NLB_MFMA = flag
             try:
                 res[flag] = ops.nlb_attnpool(x.to(d), 256, tmax * 256, ld, len(lens), tmax, pk, use, True, True)
             finally:
-                ops.NLB_MFMA = True
+                ops_heads.NLB_MFMA = True
         (o1, a1, z1), (o0, a0, z0) = res[True], res[False]
         assert_close(o1, o0, rtol=1e-4, atol_scale=1e-5)
         assert_close(a1, a0, rtol=1e-4, atol_scale=1e-5)
@@ -428,11 +429,11 @@ def test_nlb_attnpool_mfma_vs_valu_and_oracle(ops):
     xt = rnd(52, (t_, s_, 256), "tm")
     lt = torch.tensor([(i % t_) + 1 for i in range(s_)], dtype=torch.int32, device=d)
     o1, _ = ops.nlb_attnpool(xt.to(d), s_ * 256, 256, lt, s_, t_, pk)
-    ops.NLB_MFMA = False
+    ops_heads.NLB_MFMA = False
     try:
         o0, _ = ops.nlb_attnpool(xt.to(d), s_ * 256, 256, lt, s_, t_, pk)
     finally:
-        ops.NLB_MFMA = True
+        ops_heads.NLB_MFMA = True
     assert_close(o1, o0, rtol=1e-4, atol_scale=1e-5)
     ref, _ = OH.aggregate_sequences([xt[:int(lt[i]), i] for i in range(s_)], p)
     assert_close(o1, ref)

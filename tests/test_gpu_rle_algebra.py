@@ -295,13 +295,13 @@ def test_iou_equals_the_restatement_and_the_dense_route(dg):
 
 def test_iou_in_chunks_gives_the_same_table(monkeypatch):
     from seam_match_rcnn_amd import mask_utils as M
-    from seam_match_rcnn_amd import ops
+    from seam_match_rcnn_amd import ops, ops_masks
     h, w = 65, 7
     rng = np.random.default_rng(8)
     dt = [{"size": [h, w], "counts": MR.random_counts(rng, h, w, zero_runs=False)} for _ in range(7)]
     gt = [{"size": [h, w], "counts": MR.random_counts(rng, h, w, zero_runs=False)} for _ in range(3)]
     whole = M.iou(dt, gt, [0, 1, 0])
-    monkeypatch.setattr(ops, "RLE_BITS_BUDGET_BYTES", 4 * cells_of(h, w) * 5)      # two detections per chunk beside the ground truths
+    monkeypatch.setattr(ops_masks, "RLE_BITS_BUDGET_BYTES", 4 * cells_of(h, w) * 5)      # two detections per chunk beside the ground truths
     assert ops.budget_chunks([10, 10, 10, 50, 10], 25) == [(0, 2), (2, 3), (3, 4), (4, 5)]
     assert np.array_equal(M.iou(dt, gt, [0, 1, 0]), whole) and whole.any()
 
@@ -481,14 +481,14 @@ def test_evaluate_results_equals_update_on_the_same_outputs(tmp_path):
     # from paths, and in several chunks
     (tmp_path / "gt.json").write_text(gt_text)
     (tmp_path / "dt.json").write_text(res_text)
-    from seam_match_rcnn_amd import ops
-    old = ops.RLE_BITS_BUDGET_BYTES
-    ops.RLE_BITS_BUDGET_BYTES = 40000
+    from seam_match_rcnn_amd import ops, ops_masks
+    old = ops_masks.RLE_BITS_BUDGET_BYTES
+    ops_masks.RLE_BITS_BUDGET_BYTES = 40000
     try:
         assert len(ops.budget_chunks([4 * cells_of(h, w) * (a + b) + h * w * a for (h, w), a, b in zip(sizes, n_gt, n_dt)])) > 2
         assert E.evaluate_results(str(tmp_path / "gt.json"), str(tmp_path / "dt.json"), verbose=False) == want_stats
     finally:
-        ops.RLE_BITS_BUDGET_BYTES = old
+        ops_masks.RLE_BITS_BUDGET_BYTES = old
     assert E.evaluate_results(json.loads(gt_text), json.loads(res_text), iou_types=("bbox",), verbose=False) == {"bbox": want_stats["bbox"]}
     with pytest.raises(ValueError):
         E.evaluate_results(json.loads(gt_text), json.loads(res_text) + [dict(results[0], image_id=7)], verbose=False)

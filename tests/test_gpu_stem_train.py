@@ -69,18 +69,18 @@ def test_pool_adjoint_equals_torch(shape):
 
 
 def test_pool_adjoint_splits_a_large_batch_over_images(monkeypatch):
-    from seam_match_rcnn_amd import ops
+    from seam_match_rcnn_amd import ops, ops_train
     shape = POOL_SHAPES[-1]
     n, h, w, c = shape
     cs = pool_case(shape)
     y, dpool = cs["y"].to(DEV), cs["dpool"].to(DEV)
     whole = ops.maxpool3s2_relu_bwd(y, dpool)
-    monkeypatch.setattr(ops, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4)                  # one image per launch
+    monkeypatch.setattr(ops_train, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4)                  # one image per launch
     assert torch.equal(ops.maxpool3s2_relu_bwd(y, dpool), whole)
-    monkeypatch.setattr(ops, "WGRAD_MAX_OPERAND_BYTES", 2 * h * w * c * 4 + 5)          # two images, then one
+    monkeypatch.setattr(ops_train, "WGRAD_MAX_OPERAND_BYTES", 2 * h * w * c * 4 + 5)          # two images, then one
     assert torch.equal(ops.maxpool3s2_relu_bwd(y, dpool), whole)
     assert torch.equal(whole.cpu(), cs["want"])
-    monkeypatch.setattr(ops, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4 - 1)
+    monkeypatch.setattr(ops_train, "WGRAD_MAX_OPERAND_BYTES", h * w * c * 4 - 1)
     with pytest.raises(ValueError):
         ops.maxpool3s2_relu_bwd(y, dpool)
 

@@ -13,7 +13,7 @@ import torch
 
 import df2_fixture as FX
 from conftest import ROOT
-from seam_match_rcnn_amd import ops
+from seam_match_rcnn_amd import ops, ops_input
 from seam_match_rcnn_amd.datasets.DF2Dataset import DeepFashion2Dataset, RandomSampler
 from seam_match_rcnn_amd.datasets.MultiDF2Dataset import (MultiDeepFashion2Dataset, MultiDF2BatchSampler,       # the feature: absent,
                                                          get_dataloader)                                       # no import
@@ -206,7 +206,7 @@ def test_dataloader_collates_products(files):
 
 
 def test_noise_tables_follow_the_last_image(monkeypatch):
-    monkeypatch.setattr(ops, "_staging", lambda nbytes, device: torch.full((nbytes + 64,), 0xEE, dtype=torch.uint8))   # unpinned
+    monkeypatch.setattr(ops_input, "_staging", lambda nbytes, device: torch.full((nbytes + 64,), 0xEE, dtype=torch.uint8))   # unpinned
     rng = np.random.RandomState(0)
     imgs = [torch.from_numpy(rng.randint(0, 256, (5, 7, 3)).astype(np.uint8)), torch.from_numpy(rng.randint(0, 256, (4, 3, 3)).astype(np.uint8))]
     args = (imgs, [(10, 14), (8, 6)], 32, 32, [True, False], "cuda:0")

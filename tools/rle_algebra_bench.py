@@ -28,7 +28,7 @@ from mask_raster_bench import garment
 from rle_encode_bench import make_detections
 from seam_match_rcnn_amd import evaluator_det as E
 from seam_match_rcnn_amd import mask_utils as M
-from seam_match_rcnn_amd import ops
+from seam_match_rcnn_amd import ops, ops_masks
 
 
 def iou_dense(dt, gt, iscrowd):
@@ -157,7 +157,7 @@ def main():
     chunks = ops.budget_chunks([cells * (e_d + e_g) + h * w * e_g] * n_img)
     t = [timed(lambda: [M.results_inter_tables(anns[lo:hi], dets[lo:hi], [(h, w)] * (hi - lo)) for lo, hi in chunks])
          for _ in range(2 + 10)][2:]
-    out.append(line(f"  the mask tables alone ({len(chunks)} chunks of at most {ops.RLE_BITS_BUDGET_BYTES >> 20} MiB)", t))
+    out.append(line(f"  the mask tables alone ({len(chunks)} chunks of at most {ops_masks.RLE_BITS_BUDGET_BYTES >> 20} MiB)", t))
     out.append(f"bytes written on the device per chunk image: {(e_d + e_g) * cells} bitmap bytes + {e_g * h * w} dense ground-truth bytes "
                f"(polygons are rasterised densely, then bit-packed); no dense detection mask ({e_d * h * w} bytes per image) exists")
     text = "\n".join(out) + "\n"
